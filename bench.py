@@ -2,19 +2,22 @@
 """Benchmark: Schnorr-on-JubJub batch verification throughput on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scheme all|single|double|vargen]
-                    [--log2-items-per-gpu L] [--no-cpu-baseline] [--wire]
+                    [--log2-items-per-gpu L] [--no-cpu-baseline] [--wire] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the verify hot path over one batch of synthetic signatures that is
 already resident in HBM.  The headline (`value`) is BASELINE.json configs[1]: 2^20 single signatures on
-one MI355X; the same invocation then times configs[2] (2^20 double) and configs[4] (2^20 var-generator)
-with the same protocol and reports them under `schemes`.  For N > 1 there is one process per GPU: started by
+one MI355X.  A plain run sets up, warms up, times the K steps and prints the line; with --full the same
+invocation then times configs[2] (2^20 double) and configs[4] (2^20 var-generator) with the same protocol,
+reports them under `schemes`, and adds every secondary record (CPU baseline, clock sample, two streams, host
+buffers, unique keys, 2^21 items, all valid, multisig, small host calls).  For N > 1 there is one process per GPU: started by
 the driver (torch.distributed.run), or -- `python3 bench.py --gpus N` with WORLD_SIZE unset -- by bench.py itself as
 a child process, before it has made any GPU call.  Every rank verifies its own shard -- 2^20 items per GPU at
 N = 2, 4 and 2^21 per GPU at N = 8, which is configs[3] (2^24 single signatures over 8 GPUs) exactly; the N = 1
-run also times 2^21 (`single_2p21`), the same-size base of that point -- and the only exchange is an RCCL
+--full run also times 2^21 (`single_2p21`), the same-size base of that point -- and the only exchange is an RCCL
 all-reduce of the 4-counter tally, inside the timed region.  `config.distributed` lists every rank's device
 (ordinal, PCI bus id, uuid) and checks the all-reduced tally against the sum of the ranks' known tallies.
-Rank 0 prints ONE compact JSON line; the whole record goes to gpurun_out/bench_full_n<N>.json.
+Rank 0 prints ONE compact JSON line; with --full the whole record goes to the file its `full_record` names.
+--dump-outputs DIR writes what the timed path returned in its last step (see dump_outputs).
 
 Synthetic inputs: seed 0x6a6a73, 4096 distinct keys, item i signed with key i mod
 4096 by the library's own GPU signer (tests pin it bit-exact to the oracle), then 15/16 valid,
@@ -365,9 +368,11 @@ def workload_name(scheme: str, n: int, world: int) -> str:
     return f"2^{lg} {scheme} signatures per GPU, resident in HBM{exact}(BASELINE.json configs[{cfg}] per GPU)"
 
 
-def run_scheme(eng, scheme: str, n: int, args, dist, rank: int, world: int, with_cpu: bool, n_keys: int = N_KEYS, mix: bool = True):
+def run_scheme(eng, scheme: str, n: int, args, dist, rank: int, world: int, with_cpu: bool, n_keys: int = N_KEYS, mix: bool = True,
+               outputs: dict = None):
     """W warm-up steps, then exactly K timed steps between two barrier + synchronize fences; returns the record of
-    this scheme (rank 0) and whether every bit-exact check held (every rank)."""
+    this scheme (rank 0) and whether every bit-exact check held (every rank).  `outputs`, when given, receives what the
+    last timed step returned: this rank's statuses and the (all-reduced) tally."""
     import torch
     from jubjub_schnorr_amd.sharding import allreduce_tally
     arrays, expect = make_inputs(eng, scheme, n, rank, n_keys, mix)
@@ -428,11 +433,13 @@ def run_scheme(eng, scheme: str, n: int, args, dist, rank: int, world: int, with
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if outputs is not None:
+        outputs.update(status=st, tally=tally)
     kernel_ms = sum(a.elapsed_time(b) for a, b in evs) / max(1, len(evs))
     # The shader clock under this load, for the ALU roofline: sampled beside an untimed repetition of the same K steps,
     # not beside the timed ones -- the query itself (SMU round trip) costs the loop 3 % (profiles/r03_clock_sampling_ab.txt)
     clocks = None
-    if rank == 0 and not args.no_clock_sampling:
+    if rank == 0 and args.full and not args.no_clock_sampling:
         from jubjub_schnorr_amd.tools.clocks import ClockSampler
         with ClockSampler(torch.cuda.current_device()) as sampler:
             for _ in range(args.steps):
@@ -488,7 +495,7 @@ def run_scheme(eng, scheme: str, n: int, args, dist, rank: int, world: int, with
         "alu_roofline": alu,
         "clocks": clocks,
     }
-    if world == 1 and not (args.wire or args.ext or args.no_two_streams) and scheme == "single" and n_keys == N_KEYS:
+    if args.full and world == 1 and not (args.wire or args.ext or args.no_two_streams) and scheme == "single" and n_keys == N_KEYS:
         # Secondary figure, never `value`: the same K batches issued on two streams in turn.  Two big calls in flight
         # sit in two call slots and fill each other's latency-bound stretches (key dedup, per-key chains, resolve pass).
         streams = [torch.cuda.Stream(), torch.cuda.Stream()]
@@ -508,7 +515,7 @@ def run_scheme(eng, scheme: str, n: int, args, dist, rank: int, world: int, with
                                         "bit_exact": bool(ok2),
                                         "note": "same K batches, issued alternately on two streams (two in flight); not the headline value"}
         ok = ok and ok2
-    if world == 1 and not (args.wire or args.ext or args.no_host_buffers) and n_keys == N_KEYS:
+    if args.full and world == 1 and not (args.wire or args.ext or args.no_host_buffers) and n_keys == N_KEYS:
         rec["host_buffer"], okh = host_buffer_rates(eng, scheme, arrays, expect)
         ok = ok and okh
     if with_cpu:
@@ -521,7 +528,7 @@ MSIG_BYTES_PER_SHARE = 32 + 3 * 64 + 1             # z, PK, R, S in; share statu
 MSIG_BYTES_PER_TRANSCRIPT = 32 + 64 + 32 + 64 + 1  # m in; aggregate key, u, R, transcript status out
 
 
-def run_multisig(eng, args, with_cpu: bool, log2_shares: int = 17):
+def run_multisig(eng, args, with_cpu: bool, log2_shares: int = 17, outputs: dict = None):
     """Secondary record (never `value`): batch `verify_share` / `combine` / `aggregate_pk` (reference src/multisig.rs:154-156,
     284-387) on VALID transcripts -- tests/golden/multisig_valid_transcripts.npz (32 transcripts of 8 participants signed as
     sign_round_2 does, made by tests/golden/make_multisig_fixture.py), tiled to 2^17 shares, one share in 16 then spoilt
@@ -564,6 +571,8 @@ def run_multisig(eng, args, with_cpu: bool, log2_shares: int = 17):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kernel_ms = sum(a.elapsed_time(b) for a, b in evs) / len(evs)
+    if outputs is not None:
+        outputs.update(zip(("share_status", "aggregate_pk", "signature_u", "signature_R", "transcript_status"), out))
     st, agg, su, sr, ts = (t.cpu().numpy() for t in out)
     ok = bool((st == want_share).all() and (ts == want_t).all() and (agg == want_agg).all() and (su == want_u).all() and (sr == want_R).all())
     algo = MSIG_BYTES_PER_SHARE * n + MSIG_BYTES_PER_TRANSCRIPT * B
@@ -575,19 +584,20 @@ def run_multisig(eng, args, with_cpu: bool, log2_shares: int = 17):
            "workload": "verify_share + combine + aggregate_pk over %d transcripts of %d participants (fixture tiled %d x), resident in HBM" % (B, per, reps),
            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
                         "traffic": None, "algorithmic_bytes_per_launch": algo, "kernel": "msig_kernel, seven passes", "kernel_ms": kernel_ms}}
-    # a long transcript: the call's time is that of its longest sponge chain (timing only: random shares, statuses not
-    # compared here; tests/test_gpu_parity.py checks 257 and 1 000 participants against the oracle)
-    long_ms = {}
-    for parts in (256, 1000):
-        k = {"z": dev["z"][:parts], "PK": dev["PK"][:parts], "R": dev["R"][:parts], "S": dev["S"][:parts], "m": dev["m"][:1]}
-        o1 = np.array([0, parts], np.uint32)
-        eng.multisig_combine(k["z"], k["PK"], k["R"], k["S"], k["m"], o1)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        eng.multisig_combine(k["z"], k["PK"], k["R"], k["S"], k["m"], o1)
-        torch.cuda.synchronize()
-        long_ms[str(parts)] = round((time.perf_counter() - t1) * 1e3, 2)
-    rec["one_transcript_ms"] = long_ms
+    if args.full:
+        # a long transcript: the call's time is that of its longest sponge chain (timing only: random shares, statuses not
+        # compared here; tests/test_gpu_parity.py checks 257 and 1 000 participants against the oracle)
+        long_ms = {}
+        for parts in (256, 1000):
+            k = {"z": dev["z"][:parts], "PK": dev["PK"][:parts], "R": dev["R"][:parts], "S": dev["S"][:parts], "m": dev["m"][:1]}
+            o1 = np.array([0, parts], np.uint32)
+            eng.multisig_combine(k["z"], k["PK"], k["R"], k["S"], k["m"], o1)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            eng.multisig_combine(k["z"], k["PK"], k["R"], k["S"], k["m"], o1)
+            torch.cuda.synchronize()
+            long_ms[str(parts)] = round((time.perf_counter() - t1) * 1e3, 2)
+        rec["one_transcript_ms"] = long_ms
     if with_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import jjs_oracle_c as oc
@@ -617,6 +627,26 @@ def run_multisig(eng, args, with_cpu: bool, log2_shares: int = 17):
                                          "algorithm, src/multisig.rs:326-387, 393-500), %d threads, %.1f s" % (sample_t, sample_t * per, threads, dt),
                                "outputs_equal_gpu": same}
     return rec, ok
+
+
+DUMP_MAX_VALUES = 1 << 21       # per output: 8 MB as float32 (plus 16 MB of row indices when sampled)
+
+
+def dump_outputs(directory: str, outputs: dict) -> None:
+    """--dump-outputs: every output of the timed path's last step as <name>.npy, float32 for bytes and statuses and float64
+    for wider integers (both exact), so that two builds can be compared output for output on the same seeded inputs.  An
+    output of more than DUMP_MAX_VALUES values keeps a fixed, seeded sample of its rows, whose indices go to <name>_rows.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in outputs.items():
+        a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+        a = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        if a.size > DUMP_MAX_VALUES:
+            keep = max(1, DUMP_MAX_VALUES // (a.size // len(a)))
+            rows = np.sort(np.random.default_rng(SEED).choice(len(a), keep, replace=False))
+            np.save(os.path.join(directory, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def write_full_record(full: dict):
@@ -771,11 +801,17 @@ def device_identity(rank: int, local_rank: int, device_index: int) -> dict:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--scheme", default="all", choices=["all", "single", "double", "vargen", "multisig"],
-                    help="all (default): headline = single, plus double and vargen in `schemes` (and the multisig batch as a secondary "
-                         "record); multisig: only the multisignature batch, SURVEY.md 8(f-1), as a line of its own")
+                    help="all (default): headline = single (with --full, plus double and vargen in `schemes` and the multisig batch "
+                         "as a secondary record); multisig: only the multisignature batch, SURVEY.md 8(f-1), as a line of its own")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (other schemes and sizes, CPU baselines, clock sample, "
+                         "two streams, host buffers, multisig, small host calls) and write the whole record to a file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (rank 0: its own statuses and "
+                         "the all-reduced tally; --scheme multisig: the five outputs of the combine call)")
     ap.add_argument("--log2-items-per-gpu", type=int, default=None,
                     help="override the BASELINE sizes (2^20 per GPU; 2^21 for single at --gpus 8)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -796,6 +832,8 @@ def main():
                          "fewer GPUs than ranks (ranks then share devices; the line says so and is not a measurement)")
     ap.add_argument("--lib", default=None, help="another in-tree build of the engine (A/B timing of kernel variants)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # N > 1 from a plain command line (`python3 bench.py --gpus 8`): this process has made no GPU call yet (torch is not even
     # imported), so it starts the ranks as a CHILD process, relays rank 0's one JSON line and leaves with the child's code.
@@ -837,31 +875,41 @@ def main():
     if args.scheme == "multisig":
         if world != 1:
             raise SystemExit("--scheme multisig is a one-GPU record")
-        rec, ok = run_multisig(eng, args, not args.no_cpu_baseline)
+        outputs = {}
+        rec, ok = run_multisig(eng, args, args.full and not args.no_cpu_baseline, outputs=outputs)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         line = {"metric": "multisig shares verified/sec (verify_share + combine)", "value": rec["value"], "unit": rec["unit"], "n_gpus": 1,
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": rec["ms_per_step"], "higher_is_better": True, "scaling": "weak",
                 "vs_baseline": None, "dtype": "u32 limbs (29-bit), u64 accumulators", "data": "fixture (valid transcripts), tiled",
                 "config": {"workload": rec["workload"]}, "bit_exact": rec["bit_exact"], "roofline": rec["roofline"],
-                "one_transcript_ms": rec["one_transcript_ms"], "invalid_shares": rec["invalid_shares"]}
-        if "cpu_baseline" in rec:
-            line["cpu_baseline"] = rec["cpu_baseline"]
+                "invalid_shares": rec["invalid_shares"]}
+        for k in ("one_transcript_ms", "cpu_baseline"):
+            if k in rec:
+                line[k] = rec[k]
         print(json.dumps(line), flush=True)
         if not ok:
             raise SystemExit("bit-exact check failed")
         return
-    schemes = ["single", "double", "vargen"] if args.scheme == "all" else [args.scheme]
-    with_cpu = (not args.no_cpu_baseline) and world == 1
+    if args.scheme == "all":
+        schemes = ["single", "double", "vargen"] if args.full else ["single"]
+    else:
+        schemes = [args.scheme]
+    with_cpu = args.full and (not args.no_cpu_baseline) and world == 1
     records, all_ok = {}, True
-    for scheme in schemes:
+    for i, scheme in enumerate(schemes):
         n = items_per_gpu(scheme, world, args.log2_items_per_gpu)
-        rec, ok = run_scheme(eng, scheme, n, args, dist, rank, world, with_cpu, args.keys)
+        outputs = {} if i == 0 else None
+        rec, ok = run_scheme(eng, scheme, n, args, dist, rank, world, with_cpu, args.keys, outputs=outputs)
+        if outputs is not None and rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         records[scheme] = rec
         all_ok = all_ok and ok
         torch.cuda.empty_cache()
     extras = {}
     unique = None
     base_2p21 = None
-    if args.scheme == "all" and not (args.wire or args.ext):
+    if args.full and args.scheme == "all" and not (args.wire or args.ext):
         # the same size with every signature under its own key: no key repeats, so the engine's key tables cannot
         # engage and every public key is a fresh variable point (the worst case for the path; round 1's number)
         n = items_per_gpu("single", world, args.log2_items_per_gpu)
@@ -882,11 +930,11 @@ def main():
             extras["single_all_valid"] = {k: all_valid[k] for k in ("value", "unit", "ms_per_step", "workload", "items_per_gpu", "bit_exact")}
             torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and args.scheme == "all" and not (args.wire or args.ext):
+    if args.full and rank == 0 and world == 1 and args.scheme == "all" and not (args.wire or args.ext):
         # the multisignature batch under the same measurement contract (secondary record)
         extras["multisig"], ok = run_multisig(eng, args, with_cpu)
         all_ok = all_ok and ok
-    if rank == 0 and world == 1 and args.scheme == "all" and not (args.wire or args.ext or args.no_host_buffers):
+    if args.full and rank == 0 and world == 1 and args.scheme == "all" and not (args.wire or args.ext or args.no_host_buffers):
         # the reference's own call pattern: few signatures per blocking call, several host threads (secondary record)
         from jubjub_schnorr_amd.tools import small_host_calls
         try:
@@ -945,7 +993,7 @@ def main():
             full["single_2p21"] = {k: base_2p21[k] for k in ("value", "unit", "ms_per_step", "workload", "items_per_gpu", "bit_exact")}
         for k, v in extras.items():
             full[k] = v
-        path = write_full_record(full)
+        path = write_full_record(full) if args.full else None
         print(json.dumps(compact_line(full, path)), flush=True)
     if dist is not None:
         dist.barrier()

@@ -2,12 +2,13 @@
 # Copies the summaries of one profiling pass (scripts/profile_round.sh <tag>, merged back under gpurun_out/) into
 # profiles/.  Usage: bash scripts/collect_profiles.sh <tag>
 T=${1:?tag}; cd "$(dirname "$0")/.."
+O=${BENCH_OUT:-bench_records}     # where profile_round.sh put its bench lines
 cp gpurun_out/pmc_latest.json gpurun_out/${T}_pmc_summary*.json profiles/
-cp gpurun_out/bench_$T.json profiles/${T}_bench.json
-cp gpurun_out/bench_${T}_full.json profiles/${T}_bench_full.json
-cp gpurun_out/bench_${T}_wire.json profiles/${T}_bench_wire.json
-cp gpurun_out/bench_${T}_ext.json profiles/${T}_bench_ext.json
-cp gpurun_out/bench_${T}_multisig.json profiles/${T}_bench_multisig.json
+cp $O/bench_$T.json profiles/${T}_bench.json
+cp $O/bench_${T}_full.json profiles/${T}_bench_full.json
+cp $O/bench_${T}_wire.json profiles/${T}_bench_wire.json
+cp $O/bench_${T}_ext.json profiles/${T}_bench_ext.json
+cp $O/bench_${T}_multisig.json profiles/${T}_bench_multisig.json
 for s in single double vargen single_unique; do cp gpurun_out/${T}_kernel_stats_$s.csv profiles/; done
 cp gpurun_out/phase_profile_$T.jsonl profiles/${T}_phase_profile.jsonl
 for s in single double vargen; do cp gpurun_out/batch_size_curve_${T}_$s.jsonl profiles/${T}_batch_size_curve_$s.jsonl; done

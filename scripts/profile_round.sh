@@ -6,6 +6,7 @@
 # PART=1: the counter passes and benches only; PART=2: the small-call records, the timeline and the clock sample only (a pass
 # is longer than one gpurun call allows; part 2 needs part 1's files under gpurun_out/ only for the last two lines of output)
 R=${GRAFT_REPO_ROOT:-$(pwd)}; T=${1:-r04}; SCHEMES=${2:-"single double vargen"}; cd /tmp && export TMPDIR=/tmp
+O=${BENCH_OUT:-$R/bench_records}; mkdir -p $O      # the bench lines of the pass (BENCH_OUT: another directory)
 if [ "${PART:-0}" != 2 ]; then
 for S in $SCHEMES single_unique; do
   KEYS=""; U=0; SS=$S
@@ -21,12 +22,13 @@ for S in $SCHEMES single_unique; do
 done
 cd $R
 cp profiles/${T}_pmc_summary*.json profiles/pmc_latest.json gpurun_out/
-# the bench line the driver will record (all three schemes, CPU baselines, multisig, small host calls), then wire / ext inputs
-timeout -k 10 500 python bench.py > gpurun_out/bench_${T}.json 2> gpurun_out/bench_${T}.err
-cp gpurun_out/bench_full_n1.json gpurun_out/bench_${T}_full.json
-timeout -k 10 200 python bench.py --wire --no-cpu-baseline > gpurun_out/bench_${T}_wire.json 2>/dev/null
-timeout -k 10 200 python bench.py --ext --no-cpu-baseline > gpurun_out/bench_${T}_ext.json 2>/dev/null
-timeout -k 10 200 python bench.py --scheme multisig > gpurun_out/bench_${T}_multisig.json 2>/dev/null
+# the bench line the driver records with --full (all three schemes, CPU baselines, multisig, small host calls), then wire / ext
+# inputs: into $O with the whole record beside it
+timeout -k 10 500 python bench.py --full > $O/bench_${T}.json 2> $O/bench_${T}.err
+cp "$(python3 -c 'import json, sys; print(json.load(sys.stdin)["full_record"])' < $O/bench_${T}.json)" $O/bench_${T}_full.json
+timeout -k 10 200 python bench.py --full --wire --no-cpu-baseline > $O/bench_${T}_wire.json 2>/dev/null
+timeout -k 10 200 python bench.py --full --ext --no-cpu-baseline > $O/bench_${T}_ext.json 2>/dev/null
+timeout -k 10 200 python bench.py --full --scheme multisig > $O/bench_${T}_multisig.json 2>/dev/null
 for s in single double vargen; do timeout -k 10 200 python jubjub_schnorr_amd/tools/phase_profile.py $s 20 2>/dev/null >> gpurun_out/phase_profile_${T}.jsonl; done
 for s in single double vargen; do timeout -k 10 200 python jubjub_schnorr_amd/tools/batch_size_curve.py $s > gpurun_out/batch_size_curve_${T}_$s.jsonl 2>/dev/null; done
 timeout -k 10 200 python jubjub_schnorr_amd/tools/concurrent_calls.py > gpurun_out/concurrent_calls_${T}.jsonl 2>/dev/null
@@ -38,4 +40,4 @@ bash scripts/r04_small_calls.sh ${T} full
 bash scripts/timeline.sh ${T} single
 bash scripts/clock_sample.sh $T
 fi
-cut -c1-200 gpurun_out/bench_${T}.json; tail -3 gpurun_out/pmc_${T}_single.log
+cut -c1-200 $O/bench_${T}.json; tail -3 "$(find $R -name "pmc_${T}_single.log" | head -1)"

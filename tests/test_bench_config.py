@@ -1,7 +1,13 @@
 """bench.py runs the BASELINE.json configurations it claims: shard sizes per GPU count, workload names, and the
-hash that ties a committed PMC profile to the kernel sources (no GPU needed)."""
+hash that ties a committed PMC profile to the kernel sources (no GPU needed); and what a plain run does and dumps
+(one test on the GPU)."""
 import json
 import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
 
 import bench
 
@@ -58,3 +64,46 @@ def test_thread_choice_prefers_the_fastest_probe():
     info = {"affinity_cores": 256, "cgroup_cpu_quota_cores": 16.0}
     t, _, seen = bench.pick_threads(lambda k: 1000.0 * k, info, 128)
     assert t == 16 and max(seen) == 16
+
+
+def test_dumped_outputs_are_exact_floats_and_bounded(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_MAX_VALUES", 1 << 12)
+    status = np.arange(1 << 13, dtype=np.uint8) % 4
+    tally = np.array([5, 0, 3, (1 << 40) + 1], np.int64)
+    keys = (np.arange(50 * 64) % 251).astype(np.uint8).reshape(50, 64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"status": status, "tally": tally, "keys": keys})
+    got = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["keys.npy", "status.npy", "status_rows.npy", "tally.npy"]
+    assert got["tally.npy"].dtype == np.float64 and got["tally.npy"].tolist() == tally.tolist()
+    assert got["keys.npy"].dtype == np.float32 and (got["keys.npy"] == keys).all()
+    rows = got["status_rows.npy"].astype(np.int64)            # a sample of the larger output, rows in order, no repeats
+    assert len(rows) == 1 << 12 and (np.diff(rows) > 0).all()
+    assert got["status.npy"].dtype == np.float32 and (got["status.npy"] == status[rows]).all()
+    for f, a in got.items():                                  # the same sample every time
+        assert (np.load(tmp_path / "b" / f) == a).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_and_dumps_what_it_computed(tmp_path):
+    """A plain run: the contract's keys for the K timed steps of the headline only, and the statuses and tally of its last
+    step, the same in two runs with the same arguments."""
+    n, dumps = 1 << 14, []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--log2-items-per-gpu", "14", "--dump-outputs", str(tmp_path / d)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["metric"] == "Schnorr verifications/sec" and line["unit"] == "verifications/s" and line["higher_is_better"] is True
+        assert line["config"]["items_per_gpu"] == n and all(line["bit_exact"].values())
+        assert not {"schemes", "cpu_baseline", "unique_keys", "multisig", "small_host_calls"} & set(line)
+        assert line["full_record"] is None
+        dumps.append({f.name: np.load(f) for f in (tmp_path / d).iterdir()})
+    a, b = dumps
+    assert sorted(a) == ["status.npy", "tally.npy"] and a["status.npy"].shape == (n,)
+    assert a["tally.npy"].tolist() == [float((a["status.npy"] == k).sum()) for k in range(4)]
+    assert all((a[f] == b[f]).all() for f in a)

@@ -20,7 +20,7 @@ def _env_without_ranks():
 @pytest.mark.gpu
 def test_two_ranks_share_one_gpu_over_gloo():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--log2-items-per-gpu", "17", "--no-cpu-baseline"]
+           "--backend", "gloo", "--log2-items-per-gpu", "17", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=_env_without_ranks())
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
