@@ -174,6 +174,60 @@ int jjs_trim(void);
 #define JJS_MEMORY_STATS 4
 int jjs_memory_stats(uint64_t out[JJS_MEMORY_STATS]);
 
+/* ---- registered key sets ----------------------------------------------------------------------------------
+ * Callers that know their keys ahead of time (a validator set, a wallet's accounts, the signers of a contract) register
+ * them once and then verify against them by index: each key is decoded or normalised, gets its `is_valid` test and its
+ * window tables {0 .. 2^(w-1)} * 2^(w i) * PK (w = 6) on every driven device, once; a call then carries a 4-byte index per
+ * item instead of the key, and no per-call dedup, chains or tables run, whatever the call's size and however often its keys
+ * repeat within it (measured against the inline calls: profiles/r05_keyset.jsonl).
+ *   jjs_keyset_create(scheme, format, keys, keys2, n_keys, key_status, out): scheme JJS_SCHEME_*, key format JJS_FORMAT_*.
+ *     The set holds the public-key type of its scheme: PublicKey, PublicKeyDouble (pk, pk') or PublicKeyVarGen (pk, generator).
+ *     Affine / extended keys: keys = the first point column (n x 64 / n x 96), keys2 = the second (NULL for single).  Wire
+ *     keys: keys = the layout of the _wire calls (n x 32 single, n x 64 pk || pk' or pk || generator), keys2 = NULL.  The
+ *     bytes are copied.  key_status[k] (nullable): 0 valid, 1 not `is_valid` (extended Z = 0 included), 3 a non-canonical
+ *     coordinate or an encoding that does not decode; the worse of the two points wins.  Invalid keys stay registered.
+ *     Blocking: the set is built before the call returns, outside the engine's mutex and on streams of its own (other
+ *     threads' calls go on meanwhile); it is published under the mutex once every device's copy is complete.
+ *   jjs_keyset_verify(_dev)(ks, format, key_idx, s0, s1, s2, m, n, ...): signature columns by format: affine s0 = u (n x 32),
+ *     s1 = R (n x 64), s2 = R' (double only); ext s0 = u, s1 = R (n x 96), s2 = R'; wire s0 = sig (n x 64, n x 96 double),
+ *     s1 = s2 = NULL.  key_idx: n x uint32.  The status of an item is the one the inline entry point of the signature's
+ *     format returns for it given the registered key as its affine point, combined with key_status[key_idx[i]] (Malformed >
+ *     InvalidPoint > InvalidSignature); key_idx[i] >= n_keys gives 3 (checked on the device).  _dev: device pointers
+ *     (key_idx 4-byte, the others 16-byte aligned), asynchronous on `stream`, like the other _dev calls.  Host buffers: blocking,
+ *     on the calling thread's current device, one such call at a time per device (they share the device's staging and
+ *     its large host-call lock): the columns are uploaded whole, then verified, with no overlap of uploads and work and no
+ *     combining of several threads' small calls.  profiles/r05_keyset.jsonl measures what that costs: a 2^20-item host call
+ *     1.16x the inline one, eight threads of 64-signature calls 0.29x the inline rate.
+ *     Calls of at most 16 384 items take the latency variant (eight hash lanes per item and the R points' subgroup tests
+ *     beside them, then 4-16 lanes per equation over the tables); larger ones group the items by key (a cursor per key of
+ *     the SET is cleared and scanned by every large call, and every slot's index buffer holds one: a per-call cost that
+ *     grows with the set, not with the call) and take one lane per item.
+ *   jjs_keyset_destroy(ks): the handle becomes stale (-1 from then on).  Launches already queued still read the set's
+ *     device memory, which jjs_trim or jjs_shutdown frees; jjs_trim never frees a live set, jjs_shutdown frees every set.
+ *   jjs_keyset_info(ks, out): JJS_KEYSET_* words below.
+ * Memory per key on each device: 64 B + 1 B + 43 x 33 x 144 B = 204 KB per point column (twice that for double and var-gen).
+ * Threading: every keyset call may come from any thread; the registry is read and changed under the engine's mutex, which
+ * no keyset call holds while it waits for the device.
+ * Return codes: -4 before jjs_init; -1 for an unknown or destroyed handle, a bad scheme or format, a NULL column the
+ * format needs or n_keys == 0; -2 when the set cannot be allocated (no partial set is left behind). */
+typedef uint64_t jjs_keyset;                      /* 0 is never a valid handle */
+#define JJS_KEYSET_SCHEME 0
+#define JJS_KEYSET_KEYS 1
+#define JJS_KEYSET_VALID_KEYS 2
+#define JJS_KEYSET_WINDOW_BITS 3
+#define JJS_KEYSET_DEVICE_BYTES 4                 /* per device */
+#define JJS_KEYSET_SMALL_CALLS 5                  /* calls served by the latency variant */
+#define JJS_KEYSET_LARGE_CALLS 6                  /* ... and by the large one */
+#define JJS_KEYSET_INFO 7
+int jjs_keyset_create(int scheme, int format, const uint8_t* keys, const uint8_t* keys2, size_t n_keys, uint8_t* key_status,
+                      jjs_keyset* out);
+int jjs_keyset_destroy(jjs_keyset ks);
+int jjs_keyset_info(jjs_keyset ks, uint64_t out[JJS_KEYSET_INFO]);
+int jjs_keyset_verify(jjs_keyset ks, int format, const uint32_t* key_idx, const uint8_t* s0, const uint8_t* s1, const uint8_t* s2,
+                      const uint8_t* m, size_t n, uint8_t* status, uint64_t tally[4]);
+int jjs_keyset_verify_dev(jjs_keyset ks, int format, const void* key_idx, const void* s0, const void* s1, const void* s2,
+                          const void* m, size_t n, void* status, void* tally, void* stream);
+
 /* ---- wire formats (reference `to_bytes` / `from_bytes`), device buffers, asynchronous ------------------
  * Points travel compressed (32 bytes: little-endian v, parity of u in bit 255) and are decoded on the
  * device; an item with any undecodable point (v >= q, no square root, or u = 0 with the sign bit set)

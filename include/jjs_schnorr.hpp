@@ -17,6 +17,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "jjs_gpu.h"
@@ -266,6 +267,84 @@ class PublicKeyVarGen {
     }
   private:
     AffinePoint pk_, generator_;
+};
+
+// Registered key sets (include/jjs_gpu.h jjs_keyset_*): keys validated and tabled once on the device, then verified against by
+// index.  Move-only; the destructor destroys the set (calls already queued on a stream still complete).
+class KeySet {
+  public:
+    // raw form: scheme JJS_SCHEME_*, key format JJS_FORMAT_* and the key columns of jjs_keyset_create
+    KeySet(int scheme, int format, const uint8_t* keys, const uint8_t* keys2, size_t n_keys) : scheme_(scheme), status_(n_keys) {
+        int rc = jjs_keyset_create(scheme, format, keys, keys2, n_keys, status_.data(), &handle_);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_create");
+    }
+    explicit KeySet(const std::vector<PublicKey>& keys) : KeySet(JJS_SCHEME_SINGLE, column(keys, [](const PublicKey& k) { return k.as_ref(); }), keys.size()) {}
+    explicit KeySet(const std::vector<PublicKeyDouble>& keys)
+        : KeySet(JJS_SCHEME_DOUBLE, column(keys, [](const PublicKeyDouble& k) { return k.pk(); }),
+                 column(keys, [](const PublicKeyDouble& k) { return k.pk_prime(); }), keys.size()) {}
+    explicit KeySet(const std::vector<PublicKeyVarGen>& keys)
+        : KeySet(JJS_SCHEME_VARGEN, column(keys, [](const PublicKeyVarGen& k) { return k.public_key(); }),
+                 column(keys, [](const PublicKeyVarGen& k) { return k.generator(); }), keys.size()) {}
+    KeySet(KeySet&& o) noexcept : scheme_(o.scheme_), handle_(o.handle_), status_(std::move(o.status_)) { o.handle_ = 0; }
+    KeySet& operator=(KeySet&& o) noexcept {
+        if (this != &o) { reset(); scheme_ = o.scheme_; handle_ = o.handle_; status_ = std::move(o.status_); o.handle_ = 0; }
+        return *this;
+    }
+    KeySet(const KeySet&) = delete;
+    KeySet& operator=(const KeySet&) = delete;
+    ~KeySet() { reset(); }
+
+    jjs_keyset handle() const { return handle_; }
+    // per key: 0 valid, 1 not `is_valid`, 3 malformed
+    const std::vector<uint8_t>& key_status() const { return status_; }
+    std::array<uint64_t, JJS_KEYSET_INFO> info() const {
+        std::array<uint64_t, JJS_KEYSET_INFO> out{};
+        int rc = jjs_keyset_info(handle_, out.data());
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_info");
+        return out;
+    }
+    // raw form: the signature columns of jjs_keyset_verify for `format`; blocking
+    void verify(int format, const uint32_t* key_idx, const uint8_t* s0, const uint8_t* s1, const uint8_t* s2, const uint8_t* m, size_t n,
+                uint8_t* status, uint64_t tally[4] = nullptr) const {
+        int rc = jjs_keyset_verify(handle_, format, key_idx, s0, s1, s2, m, n, status, tally);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_verify");
+    }
+    // (key index, signature, message): the signature type of the set's scheme
+    template <typename Sig>
+    struct Item { uint32_t index; Sig sig; BlsScalar message; };
+    std::vector<VerifyResult> verify_batch(const std::vector<Item<Signature>>& items) const { return batch(items, JJS_SCHEME_SINGLE); }
+    std::vector<VerifyResult> verify_batch(const std::vector<Item<SignatureDouble>>& items) const { return batch(items, JJS_SCHEME_DOUBLE); }
+    std::vector<VerifyResult> verify_batch(const std::vector<Item<SignatureVarGen>>& items) const { return batch(items, JJS_SCHEME_VARGEN); }
+
+  private:
+    KeySet(int scheme, const detail::Soa& a, size_t n) : KeySet(scheme, JJS_FORMAT_AFFINE, a.data(), nullptr, n) {}
+    KeySet(int scheme, const detail::Soa& a, const detail::Soa& b, size_t n) : KeySet(scheme, JJS_FORMAT_AFFINE, a.data(), b.data(), n) {}
+    template <typename K, typename F>
+    static detail::Soa column(const std::vector<K>& keys, F get) {
+        detail::Soa c(keys.size(), 64);
+        for (size_t i = 0; i < keys.size(); ++i) c.put(i, 0, get(keys[i]));
+        return c;
+    }
+    template <typename Sig>
+    std::vector<VerifyResult> batch(const std::vector<Item<Sig>>& items, int scheme) const {
+        if (scheme != scheme_) throw std::invalid_argument("signature type does not match the key set's scheme");
+        const size_t n = items.size();
+        const bool dbl = scheme == JJS_SCHEME_DOUBLE;
+        std::vector<uint32_t> idx(n);
+        detail::Soa u(n, 32), r(n, 64), rp(dbl ? n : 0, 64), m(n, 32);
+        for (size_t i = 0; i < n; ++i) {
+            idx[i] = items[i].index;
+            u.put(i, 0, items[i].sig.u); r.put(i, 0, items[i].sig.R); m.put(i, 0, items[i].message);
+            if constexpr (std::is_same<Sig, SignatureDouble>::value) rp.put(i, 0, items[i].sig.R_prime);
+        }
+        std::vector<uint8_t> status(n);
+        verify(JJS_FORMAT_AFFINE, idx.data(), u.data(), r.data(), dbl ? rp.data() : nullptr, m.data(), n, status.data());
+        return detail::results(status);
+    }
+    void reset() { if (handle_) { (void)jjs_keyset_destroy(handle_); handle_ = 0; } }
+    int scheme_ = 0;
+    jjs_keyset handle_ = 0;
+    std::vector<uint8_t> status_;
 };
 
 }  // namespace jjs

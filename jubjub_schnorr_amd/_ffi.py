@@ -64,6 +64,11 @@ SIGNATURES = {
     "jjs_debug_comb_table": [_I, _P],
     "jjs_debug_rccl_selftest": [],
     "jjs_public_keys_dev": [_P, _Z, _P, _P, _P, _P],
+    "jjs_keyset_create": [_I, _I, _P, _P, _Z, _P, _P],
+    "jjs_keyset_destroy": [ctypes.c_uint64],
+    "jjs_keyset_info": [ctypes.c_uint64, _P],
+    "jjs_keyset_verify": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P],
+    "jjs_keyset_verify_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P],
 }
 # include/jjs_gpu_profiling.h: present in libjjs_gpu_prof.so only
 PROFILING_SIGNATURES = {

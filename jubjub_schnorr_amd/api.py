@@ -164,6 +164,12 @@ class Engine:
 
     _WIRE_WIDTHS = {"single": (64, 32, 32), "double": (96, 64, 32), "vargen": (64, 64, 32)}
 
+    def keyset(self, scheme: str, keys, keys2=None, fmt: str = "affine") -> "KeySet":
+        """Register keys once (jjs_keyset_create): validity and window tables are built on every driven device and kept
+        until the set is closed.  affine / ext: `keys` (n, 64 | 96) is the first point column, `keys2` the second (PK' for
+        double, the generator for vargen); wire: `keys` in the layout of `verify_wire`'s pk, `keys2` None."""
+        return KeySet(self, scheme, keys, keys2, fmt)
+
     def verify_wire(self, scheme: str, sig, pk, m, want_status: bool = True):
         """Batch verify from the reference's wire formats (torch CUDA uint8 tensors): sig (n, 64|96|64) =
         u || R [|| R'], pk (n, 32|64|64) compressed, m (n, 32).  Points are decoded on the device; an
@@ -437,3 +443,121 @@ class PublicKeyVarGen:
             _rows([k.pk for k, _, _ in items], 64), _rows([k.generator for k, _, _ in items], 64),
             _rows([m for _, _, m in items], 32))
         return st
+
+
+# ------------------------------------------------------------------------------------------------
+# registered key sets (include/jjs_gpu.h jjs_keyset_*)
+# ------------------------------------------------------------------------------------------------
+class KeySet:
+    """Keys registered once, verified against by index (`Engine.keyset`).  `key_status[k]`: 0 valid, 1 not `is_valid`,
+    3 malformed.  Usable as a context manager; `close()` destroys the set (queued device calls still complete)."""
+    INFO_NAMES = ("scheme", "keys", "valid_keys", "window_bits", "device_bytes", "small_calls", "large_calls")
+    _SIG_WIDTHS = {  # (s0, s1, s2) per format; 0: the column is not used
+        ("single", "affine"): (32, 64, 0), ("double", "affine"): (32, 64, 64), ("vargen", "affine"): (32, 64, 0),
+        ("single", "ext"): (32, 96, 0), ("double", "ext"): (32, 96, 96), ("vargen", "ext"): (32, 96, 0),
+        ("single", "wire"): (64, 0, 0), ("double", "wire"): (96, 0, 0), ("vargen", "wire"): (64, 0, 0),
+    }
+
+    def __init__(self, eng: Engine, scheme: str, keys, keys2=None, fmt: str = "affine"):
+        self._eng, self._lib, self.scheme = eng, eng._lib, scheme
+        two = scheme != "single"
+        if fmt == "wire":
+            if keys2 is not None:
+                raise ValueError("wire keys come in one column (pk || pk' or pk || generator): keys2 must be None")
+            k1, k2 = eng._host(keys, 64 if two else 32), None
+        else:
+            w = 96 if fmt == "ext" else 64
+            k1 = eng._host(keys, w)
+            k2 = eng._host(keys2, w) if two else None
+            if two and k2.shape[0] != k1.shape[0]:
+                raise ValueError("both key columns must have the same number of keys")
+        n = k1.shape[0]
+        self.key_status = np.zeros(n, np.uint8)
+        h = ctypes.c_uint64(0)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+        _ffi.check(self._lib.jjs_keyset_create(Engine._SCHEME_IDS[scheme], Engine._FORMAT_IDS[fmt], p(k1), p(k2), n,
+                                                p(self.key_status), ctypes.byref(h)), "jjs_keyset_create")
+        self.handle = h.value
+        self.n_keys = n
+
+    @classmethod
+    def from_public_keys(cls, keys: Sequence) -> "KeySet":
+        """A set of reference-shaped keys, all `PublicKey`, all `PublicKeyDouble` or all `PublicKeyVarGen`."""
+        if not keys:
+            raise ValueError("a key set needs at least one key")
+        if all(isinstance(k, PublicKey) for k in keys):
+            return engine().keyset("single", _rows([k.point for k in keys], 64))
+        if all(isinstance(k, PublicKeyDouble) for k in keys):
+            return engine().keyset("double", _rows([k.pk for k in keys], 64), _rows([k.pk_prime for k in keys], 64))
+        if all(isinstance(k, PublicKeyVarGen) for k in keys):
+            return engine().keyset("vargen", _rows([k.pk for k in keys], 64), _rows([k.generator for k in keys], 64))
+        raise TypeError("keys must all be PublicKey, all PublicKeyDouble or all PublicKeyVarGen")
+
+    def verify_batch(self, items: Sequence[tuple]) -> np.ndarray:
+        """items: (key index, Signature | SignatureDouble | SignatureVarGen, message bytes).  Status byte per item."""
+        if not items:
+            return np.zeros(0, np.uint8)
+        idx = np.array([i for i, _, _ in items], np.uint32)
+        cols = [_rows([s.u for _, s, _ in items], 32), _rows([s.R for _, s, _ in items], 64)]
+        if self.scheme == "double":
+            cols.append(_rows([s.R_prime for _, s, _ in items], 64))
+        st, _ = self.verify(idx, *cols, _rows([m for _, _, m in items], 32))
+        return st
+
+    def verify(self, idx, *cols, fmt: str = "affine", want_status: bool = True):
+        """Verify against the set: `idx` (n,) uint32 key indices, then the signature columns of `fmt` and the messages:
+        affine (u, R[, R'], m), ext (u, R_ext[, R'_ext], m), wire (sig, m).  Torch CUDA tensors run asynchronously on the
+        current stream (idx an int32 / uint32-sized tensor); numpy arrays block.  Returns (status, tally)."""
+        if self.handle == 0:
+            raise _ffi.JjsError("the key set is closed")
+        widths = [w for w in self._SIG_WIDTHS[(self.scheme, fmt)] if w] + [32]
+        if len(cols) != len(widths):
+            raise ValueError(f"{self.scheme} {fmt} keyset verify takes {len(widths)} columns after the indices")
+        fmt_id = Engine._FORMAT_IDS[fmt]
+        slots = [None, None, None, None]          # s0, s1, s2, m
+        positions = [0, 1, 2][:len(widths) - 1] + [3]
+        if _is_torch(idx):
+            import torch
+            n = idx.shape[0]
+            if not (idx.is_cuda and idx.is_contiguous() and idx.dim() == 1 and idx.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+                raise ValueError("expected a contiguous 1-d CUDA tensor of int32 / uint32 indices")
+            for pos, c, w in zip(positions, cols, widths):
+                slots[pos] = self._eng._dev_ptr(c, w, n)
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=idx.device)[:n] if want_status else None
+            tally = torch.empty(4, dtype=torch.int64, device=idx.device)
+            _ffi.check(self._lib.jjs_keyset_verify_dev(self.handle, fmt_id, ctypes.c_void_p(idx.data_ptr()), *slots, n,
+                                                       ctypes.c_void_p(status.data_ptr()) if want_status and n else None,
+                                                       ctypes.c_void_p(tally.data_ptr()), self._eng._stream()),
+                       "jjs_keyset_verify_dev")
+            return status, tally
+        hidx = np.asarray(idx)
+        if hidx.dtype.kind not in "iu":
+            raise ValueError("key indices must be integers")
+        hidx = np.ascontiguousarray(hidx, dtype=np.uint32)
+        n = hidx.shape[0]
+        host = [self._eng._host(c, w) for c, w in zip(cols, widths)]
+        if any(h.shape[0] != n for h in host):
+            raise ValueError("all columns must have the same number of items as idx")
+        for pos, h in zip(positions, host):
+            slots[pos] = h.ctypes.data_as(ctypes.c_void_p)
+        status, tally = np.empty(n, np.uint8), np.zeros(4, np.uint64)
+        _ffi.check(self._lib.jjs_keyset_verify(self.handle, fmt_id, hidx.ctypes.data_as(ctypes.c_void_p), *slots, n,
+                                               status.ctypes.data_as(ctypes.c_void_p), tally.ctypes.data_as(ctypes.c_void_p)),
+                   "jjs_keyset_verify")
+        return status, tally
+
+    def info(self) -> dict:
+        out = (ctypes.c_uint64 * len(self.INFO_NAMES))()
+        _ffi.check(self._lib.jjs_keyset_info(self.handle, out), "jjs_keyset_info")
+        return dict(zip(self.INFO_NAMES, (int(v) for v in out)))
+
+    def close(self) -> None:
+        if self.handle:
+            h, self.handle = self.handle, 0
+            _ffi.check(self._lib.jjs_keyset_destroy(h), "jjs_keyset_destroy")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -593,3 +593,73 @@ __global__ __launch_bounds__(BLOCK) void dbg_half_scalars_kernel(const uint8_t* 
     reinterpret_cast<u32x4*>(b_out)[i] = u32x4{h.b.w[0], h.b.w[1], h.b.w[2], h.b.w[3]};
     neg_out[i] = h.b_neg ? 1 : 0;
 }
+
+// ---- registered key sets (keyset.h) ----------------------------------------------------------------------
+// The index pass of a keyset call (ks_index_item), and the clearing of the cursors of the grouping kernels (large calls).
+struct keyset_index_params {
+    const uint32_t* key_idx;
+    uint32_t n_keys, n_cols;
+    const uint8_t* keys[2];   // the set's affine keys, n_keys x 64
+    uint8_t* out[2];          // gathered per-item key columns, n x 64
+    uint32_t* keyid;          // [n]
+    uint8_t* bad;             // [n] malformed flags of the call
+    uint64_t n;
+    uint32_t* cursor;         // nullable: words cleared for key_count / key_scan / key_scatter
+    uint64_t cursor_words;
+};
+__global__ __launch_bounds__(BLOCK) void keyset_index_kernel(keyset_index_params X) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK, t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (X.cursor)
+        for (uint64_t i = t; i < X.cursor_words; i += total) X.cursor[i] = 0u;
+    for (uint64_t item = t; item < X.n; item += total)
+        ks_index_item(X.key_idx, X.n_keys, item, X.keyid, X.bad, X.n_cols, X.keys[0], X.keys[1], X.out[0], X.out[1]);
+}
+// A set's flags after its keys' validity lanes: an encoding that did not decode (wire) or a coordinate >= q (ext) makes the
+// key malformed, whatever the point it left behind.
+__global__ __launch_bounds__(BLOCK) void keyset_flags_kernel(uint8_t* flags0, uint8_t* flags1, const uint8_t* bad, uint32_t n_keys) {
+    const uint32_t id = blockIdx.x * BLOCK + threadIdx.x;
+    if (id >= n_keys || !bad[id]) return;
+    flags0[id] |= (uint8_t)KT_KEY_MALFORMED;
+    if (flags1) flags1[id] |= (uint8_t)KT_KEY_MALFORMED;
+}
+// Latency variant, phase A: the challenge hash of an item on eight adjacent lanes, in keyed mode (no half-size scalars, no
+// subgroup test of the key: the set has them), and in the blocks behind them the subgroup test of every R point on a lane
+// of its own (r_ok[2 item + j]), beside the hash instead of in a resolve pass behind the equations.  Whole groups of eight
+// lanes: the shuffles of a group stay inside it.
+__global__ __launch_bounds__(BLOCK, 2) void keyset_hash_kernel(verify_params P, uint32_t hash_blocks, uint8_t* r_ok) {
+    if (blockIdx.x >= hash_blocks) {
+        const uint64_t r = (uint64_t)(blockIdx.x - hash_blocks) * BLOCK + threadIdx.x, per = P.resolve_lanes_keyed;
+        if (r < P.n * per) r_ok[2 * (r / per) + r % per] = resolve_point(P, r / per, (uint32_t)(r % per)) ? 1 : 0;
+        return;
+    }
+    __builtin_amdgcn_s_setprio(3);                // the critical path: ahead of the co-resident point waves
+    const uint64_t idx = (uint64_t)blockIdx.x * BLOCK + threadIdx.x, item = idx / SB_HASH_LANES;
+    const int j = (int)(idx % SB_HASH_LANES);
+    const bool active = item < P.n;
+    const prep_record r = prepare_item(P, active ? item : P.n - 1, false, j);
+    if (j == 0 && active) store_prep(P.prep, P.n, item, r);
+}
+// Latency variant, phase B: `positions` adjacent lanes per equation (ks_piece), their sums added across the lanes with the
+// shuffle tree of small_b_kernel, the verdict written by the first lane of the item; for an item whose equation fails, the
+// subgroup tests of its R points from phase A decide between InvalidPoint and InvalidSignature (resolve_status).
+__global__ __launch_bounds__(BLOCK, 2) void keyset_small_b_kernel(verify_params P, key_params K, uint32_t positions, const uint8_t* r_ok) {
+    const uint64_t n = P.n;
+    const uint32_t lanes_per_item = positions * P.n_eq;
+    const uint64_t total = n * lanes_per_item;
+    const uint64_t idx = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool active = idx < total;              // groups are whole: total is a multiple of the group size
+    const uint64_t ii = active ? idx : total - 1;
+    const uint64_t item = ii / lanes_per_item;
+    const uint32_t sub = (uint32_t)(ii % lanes_per_item), e = sub / positions, k = sub % positions;
+    const prep_record r = load_prep(P.prep, n, item);
+    ext_pt acc = ks_piece(P, K, item, e, k, positions, r);
+    acc = sb_add(acc, dpp_quad<0xB1>(acc));       // partner lane ^ 1
+    acc = sb_add(acc, dpp_quad<0x4E>(acc));       // partner lane ^ 2
+    if (positions >= 8) acc = sb_add(acc, shfl_xor_ext(acc, 4));
+    if (positions == 16) acc = sb_add(acc, shfl_xor_ext(acc, 8));
+    bool eq_ok = ks_equation_holds(P, item, e, acc);
+    if (P.n_eq == 2) eq_ok = (__shfl_xor((int)eq_ok, (int)positions) != 0) && eq_ok;
+    uint32_t st = ks_small_status(P, K, item, r, eq_ok);
+    if (st == ST_PENDING_EQ_FAILED) st = resolve_status(r_ok[2 * item] != 0 && (P.resolve_lanes_keyed < 2 || r_ok[2 * item + 1] != 0), false);
+    publish_status(P, item, active && sub == 0, st);
+}

@@ -263,6 +263,9 @@ struct device_state {
     std::chrono::steady_clock::time_point lane_last_done[3][3] = {};   // come back, and the next lane waits for them (COMBINE_WINDOW_US)
     std::vector<retired_buffer> retired; // replaced buffers, freed by jjs_trim / jjs_shutdown
     size_t retired_bytes = 0;
+    hipStream_t ks_stream = nullptr;     // host-buffer calls on a registered key set (jjs_keyset_verify): uploads, launch, statuses
+    uint8_t* ks_stage = nullptr;         // ... their device copies of the inputs and outputs (grow-only; under host_mu)
+    size_t ks_stage_bytes = 0;
 };
 
 // RCCL is needed only when one process drives several devices, so it is loaded on demand.
@@ -287,7 +290,35 @@ struct library_state {
     ncclComm_t comms[MAX_DEVICES] = {};
     bool comms_up = false;
 };
+
+// Registered key sets (keyset.h; jjs_keyset_*).  A set is immutable once built and has one copy per driven device: its
+// affine keys (64 B per point, the challenge hash reads them), the flags of its points, their window tables (KEYSET_WINDOW bits)
+// and three device words (n_keys, n_keys, the window width: the counters the grouping kernels read, and the key-table flag
+// of verify_params).  Handles are (generation << 32) | (registry index + 1): a destroyed set's index may be reused, its
+// generation never is, so a stale handle finds nothing (JJS_ERR_ARG) and never reaches freed memory.  The registry is only
+// read or changed under the engine's mutex; a destroyed set's device memory is retired (retire()), so that launches already
+// queued on a stream still read valid tables, and freed by jjs_trim / jjs_shutdown.
+struct keyset_copy {
+    device_state* dev = nullptr;
+    uint8_t* mem = nullptr;                // one allocation: the regions below
+    size_t bytes = 0;
+    uint8_t* keys[2] = {};                 // n_keys x 64 affine, per point column
+    uint8_t* flags[2] = {};                // n_keys KT_KEY_* flags, per point column
+    uint32_t* tables[2] = {};              // n_keys x kt_positions(w) x kt_table_words(w), per point column
+    uint32_t* words = nullptr;             // [0], [1] n_keys, [2] the window width
+};
+struct keyset_entry {
+    uint32_t generation = 0;
+    int scheme = 0;
+    uint32_t n_keys = 0, n_cols = 0, valid = 0;
+    std::vector<keyset_copy> copies;       // one per device of L.devs, in that order
+    uint64_t small_calls = 0, large_calls = 0;
+};
 library_state L;
+std::vector<std::unique_ptr<keyset_entry>> g_keysets;   // the registry (under L.mu)
+uint32_t g_keyset_generation = 0;                       // never reset: a handle from before jjs_shutdown stays stale
+uint32_t g_keyset_host_calls = 0;                       // host-buffer keyset calls between their first and last use of L.mu:
+                                                        // jjs_shutdown waits for them before it frees a device (under L.mu)
 // Device bound to the work in progress on THIS host thread: set by check_ready for an entry point and by each
 // per-device worker of run_host for its own block (the workers run concurrently, one device each).
 thread_local device_state* g = nullptr;

@@ -31,6 +31,7 @@
 #include <dlfcn.h>
 #include <chrono>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <random>
 #include <sched.h>
@@ -52,6 +53,7 @@
 #include "normalize.h"
 #include "small_batch.h"
 #include "key_tables.h"
+#include "keyset.h"
 #include "sign_core.h"
 #include "multisig_core.h"
 #include "jjs_sponge_tags_long.inc"
@@ -89,6 +91,7 @@ int init_device(device_state& d, int ordinal) {
     for (hipStream_t& side : d.side) HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&d.host_begin, hipEventDisableTiming));
     HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&d.ks_stream, hipStreamNonBlocking));
     {   // the per-key kernels are few, long waves that must finish before the challenge hashes do: dispatch them first
         int lo = 0, hi = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
@@ -186,7 +189,8 @@ void free_device(device_state& d) {
     if (d.device < 0) return;
     (void)hipSetDevice(d.device);
     if (d.stream) (void)hipStreamSynchronize(d.stream);
-    void* bufs[] = {d.comb_g, d.comb_gn, d.tag, d.tally, d.msig, d.tags_long, d.dlog_pow, d.dlog_hash, d.stage};
+    if (d.ks_stream) { (void)hipStreamSynchronize(d.ks_stream); (void)hipStreamDestroy(d.ks_stream); }
+    void* bufs[] = {d.comb_g, d.comb_gn, d.tag, d.tally, d.msig, d.tags_long, d.dlog_pow, d.dlog_hash, d.stage, d.ks_stage};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (call_slot& c : d.slots) {
@@ -274,9 +278,18 @@ int allreduce_tallies() {
     return JJS_OK;
 }
 
+void retire_keyset(keyset_entry& k) {      // under L.mu; the devices of its copies are alive
+    device_state* const keep = g;
+    for (keyset_copy& c : k.copies) { g = c.dev; retire(c.mem, false, c.bytes); c.mem = nullptr; }
+    g = keep;
+}
+
 void shutdown_locked() {
     int prev = -1;
     (void)hipGetDevice(&prev);
+    for (std::unique_ptr<keyset_entry>& k : g_keysets)       // freed with the other retired buffers by free_device
+        if (k) retire_keyset(*k);
+    g_keysets.clear();
     for (device_state* d : L.devs)
         if (d->stream) { (void)hipSetDevice(d->device); (void)hipStreamSynchronize(d->stream); }
     if (L.comms_up) {
@@ -353,6 +366,7 @@ void jjs_shutdown(void) {
     std::unique_lock<std::mutex> lock(L.mu);
     // host-buffer calls that hold a lane finish first (they wait for the device outside the mutex)
     L.lane_cv.wait(lock, [] {
+        if (g_keyset_host_calls) return false;          // keyset host calls that hold a device pointer outside the mutex
         for (device_state* d : L.devs)
             for (const host_lane& l : d->lanes)
                 if (l.state != host_lane::FREE) return false;
@@ -566,6 +580,7 @@ static const call_shape SHAPES[3][3] = {       // [JJS_SCHEME_*][JJS_FORMAT_*]
 };
 
 #include "host_lanes.h"
+#include "keyset_calls.h"
 
 // a host-buffer call: blocking
 static int host_call(int scheme, int format, const uint8_t* const* ptrs, size_t n, uint8_t* status, uint64_t tally[4]) {

@@ -1,0 +1,421 @@
+// Part of jjs_gpu.hip (included among the extern "C" entry points): registered key sets (keyset.h, include/jjs_gpu.h
+// jjs_keyset_*) -- building a set on every driven device, the registry, and the calls against a set.
+
+static keyset_entry* find_keyset(jjs_keyset h) {            // under L.mu
+    const uint32_t idx = (uint32_t)(h & 0xffffffffu), gen = (uint32_t)(h >> 32);
+    if (idx == 0 || idx > g_keysets.size()) return nullptr;
+    keyset_entry* k = g_keysets[idx - 1].get();
+    return k && k->generation == gen ? k : nullptr;
+}
+static const keyset_copy* keyset_copy_for(const keyset_entry& k, const device_state* d) {
+    for (const keyset_copy& c : k.copies)
+        if (c.dev == d) return &c;
+    return nullptr;
+}
+static uint32_t keyset_cols(int scheme) { return scheme == JJS_SCHEME_SINGLE ? 1u : 2u; }
+
+// One device's copy of a set (g is that device): the keys uploaded and decoded / normalised into the copy, their flags, the
+// chains of bases (freed with the upload area) and the window tables of the valid keys -- the key-table path's own kernels
+// with a key_params whose "distinct keys" are the set's keys in order.  `flags_out` receives the flags of every point column.
+static int keyset_build_copy(keyset_entry& k, keyset_copy& c, int format, const uint8_t* keys, const uint8_t* keys2,
+                             std::vector<uint8_t>& flags_out, hipStream_t s) {
+    const uint32_t n = k.n_keys, cols = k.n_cols;
+    const int w = KEYSET_WINDOW;
+    const size_t key_bytes = pad256((size_t)n * 64), flag_bytes = pad256(n);
+    const size_t table_bytes = (size_t)n * kt_positions(w) * kt_table_words(w) * 4;
+    c.dev = g;
+    c.bytes = 256 + cols * (key_bytes + flag_bytes + pad256(table_bytes));
+    if (hipMalloc(&c.mem, c.bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c.mem = nullptr;
+        return fail(JJS_ERR_HIP, "hipMalloc of a key set (%zu bytes) failed", c.bytes);
+    }
+    uint8_t* p = c.mem;
+    c.words = reinterpret_cast<uint32_t*>(p); p += 256;
+    for (uint32_t i = 0; i < cols; ++i) {
+        c.keys[i] = p; p += key_bytes;
+        c.flags[i] = p; p += flag_bytes;
+        c.tables[i] = reinterpret_cast<uint32_t*>(p); p += pad256(table_bytes);
+    }
+    // the build area: the uploaded encodings, the chains of bases, key_item, the valid-key lists, the malformed flags
+    const size_t in_width = format == JJS_FORMAT_EXT ? 96 : (format == JJS_FORMAT_WIRE ? 32 : 0);
+    const size_t in_bytes = pad256((size_t)n * in_width * cols), base_bytes = pad256((size_t)n * kt_positions(w) * KT_BASE_WORDS * 4);
+    const size_t item_bytes = pad256((size_t)n * 4), valid_bytes = pad256(((size_t)n + 1) * 4), scratch_bytes = pad256((size_t)n * 48);
+    const size_t tmp_bytes = in_bytes + cols * (base_bytes + valid_bytes) + item_bytes + flag_bytes + scratch_bytes;
+    uint8_t* tmp = nullptr;
+    if (hipMalloc(&tmp, tmp_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(c.mem); c.mem = nullptr;
+        return fail(JJS_ERR_HIP, "hipMalloc of a key set's build area (%zu bytes) failed", tmp_bytes);
+    }
+    // host memory the queued copies read or write: it outlives every return path below (the stream is drained first)
+    std::vector<uint32_t> host(64 > n ? 64 : n);
+    for (uint32_t i = 0; i < n; ++i) host[i] = i;
+    uint32_t words[64] = {n, n, (uint32_t)w};
+    flags_out.assign((size_t)cols * n, 0);
+    int rc = [&]() -> int {
+        uint8_t* q = tmp;
+        uint8_t* in = q; q += in_bytes;
+        uint32_t* key_item = reinterpret_cast<uint32_t*>(q); q += item_bytes;
+        uint8_t* bad = q; q += flag_bytes;
+        uint32_t* scratch = reinterpret_cast<uint32_t*>(q); q += scratch_bytes;
+        key_params K{};
+        K.n_cols = cols; K.max_keys = n; K.max_keys_wide = n; K.quad_chains = 1; K.n = n; K.counters = c.words;
+        for (uint32_t i = 0; i < cols; ++i) {
+            key_column& C = K.col[i];
+            C.src = fe_src{c.keys[i], 64, 0};
+            C.key_item = key_item;
+            C.key_flags = c.flags[i];
+            C.bases = reinterpret_cast<uint32_t*>(q); q += base_bytes;
+            C.valid_ids = reinterpret_cast<uint32_t*>(q); q += valid_bytes;
+            C.tables = c.tables[i];
+        }
+        HIP_TRY(hipMemcpyAsync(key_item, host.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c.words, words, sizeof(words), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(bad, 0, flag_bytes, s));
+        for (uint32_t i = 0; i < cols; ++i) HIP_TRY(hipMemsetAsync(c.tables[i], 0, table_bytes, s));   // invalid keys get no tables
+        const uint8_t* src[2] = {keys, keys2};
+        if (format == JJS_FORMAT_AFFINE) {
+            for (uint32_t i = 0; i < cols; ++i) HIP_TRY(hipMemcpyAsync(c.keys[i], src[i], (size_t)n * 64, hipMemcpyHostToDevice, s));
+        } else if (format == JJS_FORMAT_EXT) {
+            normalize_params N{};
+            for (uint32_t i = 0; i < cols; ++i) {
+                HIP_TRY(hipMemcpyAsync(in + (size_t)i * n * 96, src[i], (size_t)n * 96, hipMemcpyHostToDevice, s));
+                N.src[i] = fe_src{in + (size_t)i * n * 96, 96, 0};
+                N.out[i] = c.keys[i];
+            }
+            N.n_src = cols; N.bad = bad; N.scratch = scratch;
+            if (int e = launch_normalize(N, 0, n, n, s)) return e;
+        } else {
+            HIP_TRY(hipMemcpyAsync(in, keys, (size_t)n * 32 * cols, hipMemcpyHostToDevice, s));     // n x 32, or n x (pk || pk')
+            decode_params D{};
+            D.n_src = cols; D.n = n; D.bad = bad;
+            for (uint32_t i = 0; i < cols; ++i) { D.src[i] = fe_src{in, 32 * cols, 32 * i}; D.out[i] = c.keys[i]; }
+            D.dlog = dlog_tables{g->dlog_pow, g->dlog_hash};
+            hipLaunchKernelGGL(decode_kernel, dim3((unsigned)grid_for(8192, n)), dim3(BLOCK), 0, s, D);
+        }
+        hipLaunchKernelGGL(key_chain_kernel, dim3((unsigned)((5ull * cols * n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, K);
+        hipLaunchKernelGGL(keyset_flags_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, c.flags[0], cols > 1 ? c.flags[1] : nullptr,
+                           (const uint8_t*)bad, n);
+        hipLaunchKernelGGL(key_table_kernel, dim3((unsigned)(((uint64_t)cols * n * KT_MAX_POSITIONS + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, K);
+        HIP_TRY(hipGetLastError());
+        for (uint32_t i = 0; i < cols; ++i)
+            HIP_TRY(hipMemcpyAsync(flags_out.data() + (size_t)i * n, c.flags[i], n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return JJS_OK;
+    }();
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(tmp);
+    if (rc) { (void)hipFree(c.mem); c.mem = nullptr; }
+    return rc;
+}
+
+// The launches of one call against a set's copy `c` on stream s (g is c's device).  d = key_idx, s0, s1, s2, m (device).
+static int keyset_launch(keyset_entry& k, const keyset_copy& c, int format, const void* const* d, size_t n, void* status, void* tally,
+                         hipStream_t s) {
+    const int scheme = k.scheme;
+    const bool small = n <= KEYSET_SMALL_MAX_ITEMS;
+    pick_slot(n, s);
+    if (int rc = ensure_wire(n)) return rc;
+    if (int rc = ensure_prep(n)) return rc;
+    if (int rc = ensure_pending(n)) return rc;
+    if (small)
+        if (int rc = ensure_small(2 * n + 64)) return rc;      // the subgroup tests of the R points (keyset_hash_kernel)
+    const size_t cursor_words = (size_t)k.n_keys + 1 > (size_t)CURSOR_DENSE_FROM * CURSOR_STRIDE ? (size_t)k.n_keys + 1
+                                                                                                  : (size_t)CURSOR_DENSE_FROM * CURSOR_STRIDE;
+    if (int rc = ensure_key_index(2 * pad256(n * 4) + pad256(cursor_words * 4))) return rc;
+    // the verification descriptor: R (R') as the format gives them, the keys gathered per item into wire_pts(2) (3)
+    const uint8_t* u = (const uint8_t*)d[1];
+    const uint8_t *R = (const uint8_t*)d[2], *Rp = (const uint8_t*)d[3];
+    const uint32_t n_r = scheme == JJS_SCHEME_DOUBLE ? 2u : 1u;
+    if (format != JJS_FORMAT_AFFINE) { R = wire_pts(0); Rp = wire_pts(1); }
+    out_ptrs o{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace};
+    verify_params P{};
+    if (scheme == JJS_SCHEME_SINGLE) P = params_single(u, R, wire_pts(2), (const uint8_t*)d[4], n, g->comb_g, o);
+    else if (scheme == JJS_SCHEME_DOUBLE) P = params_double(u, R, Rp, wire_pts(2), wire_pts(3), (const uint8_t*)d[4], n, g->tag, g->comb_g, g->comb_gn, o);
+    else P = params_vargen(u, R, wire_pts(2), wire_pts(3), (const uint8_t*)d[4], n, o);
+    const uint32_t sig_stride = scheme == JJS_SCHEME_DOUBLE ? 96u : 64u;
+    if (format == JJS_FORMAT_WIRE) { P.u = fe_src{(const uint8_t*)d[1], sig_stride, 0}; P.decoded_points = 1; }
+    P.pre_malformed = wire_bad();
+    P.key_flag = c.words + 2;
+    P.prep = sl->prep;
+    P.pending_count = reinterpret_cast<unsigned long long*>(sl->pending);
+    P.pending = sl->pending + 2;
+    key_params K{};
+    K.n_cols = k.n_cols; K.max_keys = k.n_keys; K.max_keys_wide = k.n_keys; K.n = n; K.counters = c.words;
+    uint8_t* q = sl->keys;
+    uint32_t* keyid = reinterpret_cast<uint32_t*>(q); q += pad256(n * 4);
+    K.order = reinterpret_cast<uint32_t*>(q); q += pad256(n * 4);
+    K.key_cursor = reinterpret_cast<uint32_t*>(q);
+    for (uint32_t i = 0; i < k.n_cols; ++i) {
+        K.col[i].src = fe_src{c.keys[i], 64, 0};
+        K.col[i].keyid = keyid; K.col[i].key_flags = c.flags[i]; K.col[i].tables = c.tables[i];
+    }
+
+    if (int rc = begin_shared(s)) return rc;
+    clear_params Z{};
+    Z.p[0] = tally; Z.bytes[0] = tally ? 4 * sizeof(unsigned long long) : 0;
+    Z.p[1] = wire_bad(); Z.bytes[1] = n;
+    Z.p[2] = sl->pending; Z.bytes[2] = sizeof(uint64_t);
+    const uint64_t units = n / 16 / BLOCK + 1;
+    hipLaunchKernelGGL(clear_kernel, dim3((unsigned)(units < 256 ? units : 256)), dim3(BLOCK), 0, s, Z);
+    if (format == JJS_FORMAT_EXT) {
+        normalize_params N{};
+        N.n_src = n_r;
+        N.src[0] = fe_src{(const uint8_t*)d[2], 96, 0}; N.out[0] = wire_pts(0);
+        N.src[1] = fe_src{(const uint8_t*)d[3], 96, 0}; N.out[1] = wire_pts(1);
+        N.bad = wire_bad(); N.scratch = wire_scratch(0);
+        if (int rc = launch_normalize(N, 0, n, n, s)) return rc;
+    } else if (format == JJS_FORMAT_WIRE) {
+        decode_params D{};
+        D.n_src = n_r; D.n = n; D.first = 0; D.bad = wire_bad();
+        for (uint32_t i = 0; i < n_r; ++i) { D.src[i] = fe_src{(const uint8_t*)d[1], sig_stride, 32 + 32 * i}; D.out[i] = wire_pts((int)i); }
+        D.dlog = dlog_tables{g->dlog_pow, g->dlog_hash};
+        if (small) {       // one lane per point: the call waits for one square root (job_hash)
+            D.split = 1;
+            hipLaunchKernelGGL(decode_points_kernel, dim3((unsigned)grid_for(8192, n * n_r)), dim3(BLOCK), 0, s, D);
+        } else {
+            hipLaunchKernelGGL(decode_kernel, dim3((unsigned)grid_for(8192, n)), dim3(BLOCK), 0, s, D);
+        }
+    }
+    keyset_index_params X{};
+    X.key_idx = (const uint32_t*)d[0]; X.n_keys = k.n_keys; X.n_cols = k.n_cols;
+    X.keys[0] = c.keys[0]; X.keys[1] = c.keys[1]; X.out[0] = wire_pts(2); X.out[1] = wire_pts(3);
+    X.keyid = keyid; X.bad = wire_bad(); X.n = n;
+    X.cursor = small ? nullptr : K.key_cursor; X.cursor_words = small ? 0 : cursor_words;
+    hipLaunchKernelGGL(keyset_index_kernel, dim3((unsigned)grid_for(8192, n > cursor_words ? n : cursor_words)), dim3(BLOCK), 0, s, X);
+    if (small) {
+        ++k.small_calls;
+        const uint32_t hash_blocks = (uint32_t)((n * SB_HASH_LANES + BLOCK - 1) / BLOCK);
+        const uint32_t point_blocks = (uint32_t)((n * P.resolve_lanes_keyed + BLOCK - 1) / BLOCK);
+        hipLaunchKernelGGL(keyset_hash_kernel, dim3(hash_blocks + point_blocks), dim3(BLOCK), 0, s, P, hash_blocks, sl->small);
+        const uint32_t positions = ks_small_positions(n);
+        hipLaunchKernelGGL(keyset_small_b_kernel, dim3((unsigned)((n * positions * P.n_eq + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, P, K,
+                           positions, (const uint8_t*)sl->small);
+        HIP_TRY(hipGetLastError());
+        return end_shared(s);                  // nothing is left to the resolve pass
+    } else {
+        ++k.large_calls;
+        const unsigned item_blocks = (unsigned)grid_for(8192, n);
+        hipLaunchKernelGGL(key_count_kernel, dim3(item_blocks), dim3(BLOCK), 0, s, K);
+        hipLaunchKernelGGL(key_scan_kernel, dim3(1), dim3(1024), 0, s, K);
+        hipLaunchKernelGGL(key_scatter_kernel, dim3(item_blocks), dim3(BLOCK), 0, s, K);
+        hipLaunchKernelGGL(prepare_kernel, dim3(grid_for(g->grid_prepare, n)), dim3(BLOCK), 0, s, P, (int)PREP_ALL, (uint64_t)0, (uint64_t)n);
+        hipLaunchKernelGGL(key_verify_kernel, dim3(grid_for(g->grid_key_verify, n)), dim3(BLOCK), 0, s, P, K);
+    }
+    hipLaunchKernelGGL(resolve_kernel, dim3(grid_for(g->grid_resolve, n * P.resolve_lanes_keyed)), dim3(BLOCK), 0, s, P);
+    HIP_TRY(hipGetLastError());
+    return end_shared(s);
+}
+
+// bytes per item of the signature columns s0, s1, s2 of a call (0: the column is not used)
+static void keyset_sig_widths(int scheme, int format, size_t w[3]) {
+    const bool dbl = scheme == JJS_SCHEME_DOUBLE;
+    if (format == JJS_FORMAT_WIRE) { w[0] = dbl ? 96 : 64; w[1] = 0; w[2] = 0; return; }
+    w[0] = 32;
+    w[1] = format == JJS_FORMAT_EXT ? 96 : 64;
+    w[2] = dbl ? w[1] : 0;
+}
+static int keyset_check_cols(int scheme, int format, const void* key_idx, const void* s0, const void* s1, const void* s2, const void* m,
+                             bool device) {
+    if (format < 0 || format > 2) return fail(JJS_ERR_ARG, "format out of range");
+    size_t w[3];
+    keyset_sig_widths(scheme, format, w);
+    const void* cols[3] = {s0, s1, s2};
+    if (!key_idx || !m || (device && ((reinterpret_cast<uintptr_t>(key_idx) & 3u) || !aligned16(m))))
+        return fail(JJS_ERR_ARG, "null or misaligned key index or message column");
+    for (int i = 0; i < 3; ++i)
+        if (w[i] && (!cols[i] || (device && !aligned16(cols[i])))) return fail(JJS_ERR_ARG, "null or misaligned signature column %d", i);
+    return JJS_OK;
+}
+
+extern "C" {
+
+// The set is built outside the engine's mutex, on a stream of its own per device (other threads' calls go on meanwhile), and
+// published in the registry under the mutex once every copy is complete.  While it is being built the call counts among the
+// keyset calls jjs_shutdown waits for, so the devices it uses stay alive.
+int jjs_keyset_create(int scheme, int format, const uint8_t* keys, const uint8_t* keys2, size_t n_keys, uint8_t* key_status,
+                      jjs_keyset* out) {
+    std::vector<device_state*> devs;
+    {
+        std::lock_guard<std::mutex> lock(L.mu);
+        if (int rc = check_ready()) return rc;
+        if (scheme < 0 || scheme > 2 || format < 0 || format > 2) return fail(JJS_ERR_ARG, "scheme / format out of range");
+        if (!out || !keys || n_keys == 0 || n_keys > KEYSET_MAX_KEYS) return fail(JJS_ERR_ARG, "a key set needs 1 .. 2^24 keys and an output handle");
+        if (keyset_cols(scheme) > 1 && format != JJS_FORMAT_WIRE && !keys2) return fail(JJS_ERR_ARG, "the second key column is missing");
+        devs = L.devs;
+        ++g_keyset_host_calls;
+    }
+    struct leave {
+        ~leave() {
+            std::lock_guard<std::mutex> lock(L.mu);
+            --g_keyset_host_calls;
+            L.lane_cv.notify_all();
+        }
+    } leave_on_every_way_out;
+    const uint32_t cols = keyset_cols(scheme);
+    std::unique_ptr<keyset_entry> k(new keyset_entry());
+    k->scheme = scheme; k->n_keys = (uint32_t)n_keys; k->n_cols = cols;
+    device_restore restore;
+    auto free_copies = [&] {               // nothing has been published: no launch of anybody else reads these
+        for (keyset_copy& c : k->copies)
+            if (c.mem) { (void)hipSetDevice(c.dev->device); (void)hipFree(c.mem); c.mem = nullptr; }
+    };
+    std::vector<uint8_t> flags;
+    int rc = no_throw([&]() -> int {
+        for (device_state* d : devs) {
+            g = d;
+            HIP_TRY(hipSetDevice(d->device));
+            hipStream_t s = nullptr;
+            HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+            k->copies.emplace_back();
+            std::vector<uint8_t> f;
+            const int brc = keyset_build_copy(*k, k->copies.back(), format, keys, keys2, f, s);
+            (void)hipStreamDestroy(s);
+            if (brc) { k->copies.pop_back(); return brc; }
+            if (flags.empty()) flags.swap(f);
+        }
+        return JJS_OK;
+    });
+    if (rc) { free_copies(); return rc; }
+    uint32_t valid = 0;
+    for (size_t i = 0; i < n_keys; ++i) {
+        const uint32_t st = ks_key_status(flags[i], cols > 1 ? flags[n_keys + i] : (uint32_t)KT_KEY_VALID);
+        if (key_status) key_status[i] = (uint8_t)st;
+        valid += st == ST_OK;
+    }
+    k->valid = valid;
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (L.devs != devs) { free_copies(); return fail(JJS_ERR_NOT_INIT, "the engine's devices changed while the key set was built"); }
+    rc = no_throw([&]() -> int {
+        size_t slot = 0;
+        while (slot < g_keysets.size() && g_keysets[slot]) ++slot;
+        if (slot == g_keysets.size()) g_keysets.emplace_back();
+        if (++g_keyset_generation == 0) ++g_keyset_generation;       // 0 is never a generation: no valid handle is 0
+        k->generation = g_keyset_generation;
+        *out = ((uint64_t)k->generation << 32) | (uint64_t)(slot + 1);
+        g_keysets[slot] = std::move(k);
+        return JJS_OK;
+    });
+    if (rc) free_copies();
+    return rc;
+}
+
+int jjs_keyset_destroy(jjs_keyset ks) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    keyset_entry* k = find_keyset(ks);
+    if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
+    retire_keyset(*k);         // launches already queued still read it: freed by jjs_trim / jjs_shutdown
+    g_keysets[(ks & 0xffffffffu) - 1].reset();
+    return JJS_OK;
+}
+
+int jjs_keyset_info(jjs_keyset ks, uint64_t out[JJS_KEYSET_INFO]) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    keyset_entry* k = find_keyset(ks);
+    if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
+    if (!out) return fail(JJS_ERR_ARG, "null pointer");
+    out[JJS_KEYSET_SCHEME] = (uint64_t)k->scheme;
+    out[JJS_KEYSET_KEYS] = k->n_keys;
+    out[JJS_KEYSET_VALID_KEYS] = k->valid;
+    out[JJS_KEYSET_WINDOW_BITS] = (uint64_t)KEYSET_WINDOW;
+    out[JJS_KEYSET_DEVICE_BYTES] = k->copies.empty() ? 0 : k->copies[0].bytes;
+    out[JJS_KEYSET_SMALL_CALLS] = k->small_calls;
+    out[JJS_KEYSET_LARGE_CALLS] = k->large_calls;
+    return JJS_OK;
+}
+
+int jjs_keyset_verify_dev(jjs_keyset ks, int format, const void* key_idx, const void* s0, const void* s1, const void* s2, const void* m,
+                          size_t n, void* status, void* tally, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    keyset_entry* k = find_keyset(ks);
+    if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
+    hipStream_t s = (hipStream_t)stream;
+    if (status && !aligned16(status)) return fail(JJS_ERR_ARG, "status must be 16-byte aligned");
+    if (n == 0) {
+        if (format < 0 || format > 2) return fail(JJS_ERR_ARG, "format out of range");
+        if (tally) HIP_TRY(hipMemsetAsync(tally, 0, 4 * sizeof(unsigned long long), s));
+        return JJS_OK;
+    }
+    if (int rc = keyset_check_cols(k->scheme, format, key_idx, s0, s1, s2, m, true)) return rc;
+    const keyset_copy* c = keyset_copy_for(*k, g);
+    if (!c) return fail(JJS_ERR_ARG, "the key set has no copy on this device");
+    const void* d[] = {key_idx, s0, s1, s2, m};
+    return no_throw([&] { return keyset_launch(*k, *c, format, d, n, status, tally, s); });
+}
+
+// A host-buffer call: the inputs go to the device's keyset staging area (4 bytes of index per item, no key), the call runs on
+// the device's keyset stream, the statuses come back.  One such call at a time per device (host_mu, which jjs_trim and
+// jjs_shutdown also take); the engine's mutex is held only to look the set up and to queue the launches, never while the
+// call waits for the device.
+int jjs_keyset_verify(jjs_keyset ks, int format, const uint32_t* key_idx, const uint8_t* s0, const uint8_t* s1, const uint8_t* s2,
+                      const uint8_t* m, size_t n, uint8_t* status, uint64_t tally[4]) {
+    device_state* dev = nullptr;
+    int scheme = 0;
+    {
+        std::lock_guard<std::mutex> lock(L.mu);
+        if (int rc = check_ready()) return rc;
+        keyset_entry* k = find_keyset(ks);
+        if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
+        if (format < 0 || format > 2) return fail(JJS_ERR_ARG, "format out of range");
+        if (n == 0) {
+            if (tally) for (int i = 0; i < 4; ++i) tally[i] = 0;
+            return JJS_OK;
+        }
+        if (int rc = keyset_check_cols(k->scheme, format, key_idx, s0, s1, s2, m, false)) return rc;
+        scheme = k->scheme;
+        dev = g;
+        ++g_keyset_host_calls;           // jjs_shutdown does not free `dev` before this call has left (see below)
+    }
+    struct leave {
+        ~leave() {
+            std::lock_guard<std::mutex> lock(L.mu);
+            --g_keyset_host_calls;
+            L.lane_cv.notify_all();
+        }
+    } leave_on_every_way_out;
+    std::lock_guard<std::mutex> big(dev->host_mu);
+    g = dev;
+    return no_throw([&]() -> int {
+        size_t w[3];
+        keyset_sig_widths(scheme, format, w);
+        const size_t widths[5] = {4, w[0], w[1], w[2], 32};
+        const void* src[5] = {key_idx, s0, s1, s2, m};
+        size_t off[7], total = 0;
+        for (int i = 0; i < 5; ++i) { off[i] = total; total += pad256(widths[i] * n); }
+        off[5] = total; total += pad256(n);                       // statuses
+        off[6] = total; total += 256;                             // tally
+        if (total > dev->ks_stage_bytes) {
+            const size_t cap = grown(total);
+            if (int rc = regrow(dev->ks_stage, dev->ks_stage_bytes, dev->ks_stage_bytes, cap, cap)) return rc;
+        }
+        HIP_TRY(hipSetDevice(dev->device));
+        hipStream_t s = dev->ks_stream;
+        const void* d[5] = {};
+        for (int i = 0; i < 5; ++i) {
+            if (!widths[i]) continue;
+            d[i] = dev->ks_stage + off[i];
+            HIP_TRY(hipMemcpyAsync(dev->ks_stage + off[i], src[i], widths[i] * n, hipMemcpyHostToDevice, s));
+        }
+        {
+            std::lock_guard<std::mutex> lock(L.mu);
+            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
+            keyset_entry* k = find_keyset(ks);
+            if (!k) return fail(JJS_ERR_ARG, "the key set was destroyed during the call");
+            const keyset_copy* c = keyset_copy_for(*k, dev);
+            if (!c) return fail(JJS_ERR_ARG, "the key set has no copy on this device");
+            if (int rc = keyset_launch(*k, *c, format, d, n, dev->ks_stage + off[5], dev->ks_stage + off[6], s)) return rc;
+        }
+        if (status) HIP_TRY(hipMemcpyAsync(status, dev->ks_stage + off[5], n, hipMemcpyDeviceToHost, s));
+        unsigned long long t[4] = {};
+        HIP_TRY(hipMemcpyAsync(t, dev->ks_stage + off[6], sizeof(t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (tally) for (int i = 0; i < 4; ++i) tally[i] = t[i];
+        return JJS_OK;
+    });
+}
+
+}  // extern "C"
