@@ -228,6 +228,40 @@ int jjs_keyset_verify(jjs_keyset ks, int format, const uint32_t* key_idx, const 
 int jjs_keyset_verify_dev(jjs_keyset ks, int format, const void* key_idx, const void* s0, const void* s1, const void* s2,
                           const void* m, size_t n, void* status, void* tally, void* stream);
 
+/* ---- one verdict per batch: randomized batch verification -------------------------------------
+ * Affine columns in the layouts of jjs_verify_*.  The verdict is 1 (accepted) or 0.
+ *   * It never rejects a valid batch: when every item would get status 0 from jjs_verify_* of the same scheme, the
+ *     verdict is 1.
+ *   * It never accepts a malformed encoding, an invalid point or an identity point: these are checked per item as the
+ *     inline entry points check them -- scalars u < r, every coordinate and m < q, every point on the curve, every point
+ *     torsion-free (its own pairing residue test, point by point), no point the identity.
+ *   * It accepts a batch that contains an item with a failing equation with probability at most 2^-128: the equations
+ *     are combined as sum_i z_i (u_i G + c_i PK_i - R_i) == O (z'_i for the double scheme's second equation) with z_i
+ *     uniform in [0, 2^128), drawn per call from a ChaCha20 keystream keyed with 32 bytes of getrandom; every
+ *     D_i = u_i G + c_i PK_i - R_i has order 1 or r ~ 2^252 once the points are torsion-free, so a non-zero D_j is
+ *     cancelled by at most one value of z_j.  The equation is not cofactored and torsion is not batched.
+ * The product library has no way to fix the weights (jjs_gpu_profiling.h jjs_debug_pin_hash_seed(2) does, in the profiling
+ * build only).  Where the verdict algorithm is not measured faster than the per-item path (the routing
+ * table), these calls run the per-item path and reduce its tally instead, so they are never slower than jjs_verify_*
+ * followed by a check of tally[0] == n.
+ *   Host buffers: blocking, on the calling thread's current device; n = 0 gives verdict 1.  status (nullable, n bytes)
+ *     receives the statuses of jjs_verify_* of the same scheme, byte for byte, whenever the verdict is 0 (they are then
+ *     computed by the per-item path); when the verdict is 1 it is all zero.  When the verdict algorithm runs, the columns
+ *     are uploaded whole to the device's key-set staging area (one such call at a time per device).
+ *   _dev: device pointers (16-byte aligned), asynchronous on `stream`; `verdict` is a 4-byte aligned device uint32
+ *     written by the call.  No statuses: a caller who gets 0 runs jjs_verify_*_dev for them. */
+int jjs_verify_all_single(const uint8_t* u, const uint8_t* R, const uint8_t* PK, const uint8_t* m, size_t n, uint8_t* status,
+                          int* verdict);
+int jjs_verify_all_double(const uint8_t* u, const uint8_t* R, const uint8_t* R_prime, const uint8_t* PK, const uint8_t* PK_prime,
+                          const uint8_t* m, size_t n, uint8_t* status, int* verdict);
+int jjs_verify_all_vargen(const uint8_t* u, const uint8_t* R, const uint8_t* PK, const uint8_t* Gen, const uint8_t* m, size_t n,
+                          uint8_t* status, int* verdict);
+int jjs_verify_all_single_dev(const void* u, const void* R, const void* PK, const void* m, size_t n, void* verdict, void* stream);
+int jjs_verify_all_double_dev(const void* u, const void* R, const void* R_prime, const void* PK, const void* PK_prime,
+                              const void* m, size_t n, void* verdict, void* stream);
+int jjs_verify_all_vargen_dev(const void* u, const void* R, const void* PK, const void* Gen, const void* m, size_t n,
+                              void* verdict, void* stream);
+
 /* ---- wire formats (reference `to_bytes` / `from_bytes`), device buffers, asynchronous ------------------
  * Points travel compressed (32 bytes: little-endian v, parity of u in bit 255) and are decoded on the
  * device; an item with any undecodable point (v >= q, no square root, or u = 0 with the sign bit set)

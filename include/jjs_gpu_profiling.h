@@ -23,7 +23,9 @@ int jjs_debug_skip_phases(unsigned mask);
  * point), 2 = the latency path for every single / double call of at most 16 384 items; 0x42 / 0x82 = the
  * latency path with the scalars cut into 4 / 8 pieces whatever the size; 0x500 = 5-bit windows whenever the key
  * tables engage (the product takes 6-bit windows from 128 signatures per key); 0x1000 = the key-table path takes the
- * items in the caller's order instead of grouping them by key. */
+ * items in the caller's order instead of grouping them by key; for jjs_verify_all_*: 0x2000 = the verdict algorithm at
+ * any size, 0x4000 = the per-item path and its tally at any size, plus (w << 16) = the MSM's window width w (8-16; 0 by
+ * size). */
 int jjs_debug_force_path(int which);
 /* Test mode for boxes with one GPU: a later jjs_init(k) with k above the visible device count creates k logical
  * devices (own stream, tables, workspace, staging each) that share the visible cards round-robin; the tallies are
@@ -33,7 +35,9 @@ int jjs_debug_allow_virtual_devices(int allow);
  * memory takes): they run the throughput path; 0 restores the product behaviour. */
 int jjs_debug_fail_key_arena(int on);
 /* on != 0: the dedup hash of the key tables runs with seed 0 instead of a fresh seed per call, so that a test can
- * present keys crafted to collide in it (what the seed keeps a sender from doing). */
+ * present keys crafted to collide in it (what the seed keeps a sender from doing).  on & 2, in addition: jjs_verify_all_*
+ * draw their weights from the fixed ChaCha20 key 00 01 02 .. 1f instead of 32 fresh bytes of getrandom per call, so that
+ * tests and A/B runs repeat. */
 int jjs_debug_pin_hash_seed(int on);
 /* Where the last host-buffer call on one device spent its host time, in seconds: out[0] waiting for the staging copy
  * of a piece to finish (it runs one piece ahead on helper threads), out[1] starting the next one (includes waiting for

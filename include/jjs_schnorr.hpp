@@ -269,6 +269,56 @@ class PublicKeyVarGen {
     AffinePoint pk_, generator_;
 };
 
+// One verdict per batch (include/jjs_gpu.h jjs_verify_all_*): true when every item would verify.  `status` (optional)
+// receives the statuses of verify_batch when the verdict is false.
+namespace detail {
+inline bool verdict(int rc, int v, const char* what) {
+    if (rc != JJS_OK) throw EngineError(rc, what);
+    return v == 1;
+}
+}  // namespace detail
+inline bool verify_all_single(const std::vector<PublicKey::Item>& items, std::vector<VerifyResult>* status = nullptr) {
+    const size_t n = items.size();
+    detail::Soa u(n, 32), r(n, 64), pk(n, 64), m(n, 32);
+    for (size_t i = 0; i < n; ++i) {
+        u.put(i, 0, items[i].sig.u); r.put(i, 0, items[i].sig.R); pk.put(i, 0, items[i].pk); m.put(i, 0, items[i].message);
+    }
+    std::vector<uint8_t> st(status ? n : 0);
+    int v = 0;
+    const bool ok = detail::verdict(jjs_verify_all_single(u.data(), r.data(), pk.data(), m.data(), n, status ? st.data() : nullptr, &v),
+                                    v, "jjs_verify_all_single");
+    if (status) *status = detail::results(st);
+    return ok;
+}
+inline bool verify_all_double(const std::vector<PublicKeyDouble::Item>& items, std::vector<VerifyResult>* status = nullptr) {
+    const size_t n = items.size();
+    detail::Soa u(n, 32), r(n, 64), rp(n, 64), pk(n, 64), pkp(n, 64), m(n, 32);
+    for (size_t i = 0; i < n; ++i) {
+        u.put(i, 0, items[i].sig.u); r.put(i, 0, items[i].sig.R); rp.put(i, 0, items[i].sig.R_prime);
+        pk.put(i, 0, items[i].pk); pkp.put(i, 0, items[i].pk_prime); m.put(i, 0, items[i].message);
+    }
+    std::vector<uint8_t> st(status ? n : 0);
+    int v = 0;
+    const bool ok = detail::verdict(jjs_verify_all_double(u.data(), r.data(), rp.data(), pk.data(), pkp.data(), m.data(), n,
+                                                          status ? st.data() : nullptr, &v), v, "jjs_verify_all_double");
+    if (status) *status = detail::results(st);
+    return ok;
+}
+inline bool verify_all_vargen(const std::vector<PublicKeyVarGen::Item>& items, std::vector<VerifyResult>* status = nullptr) {
+    const size_t n = items.size();
+    detail::Soa u(n, 32), r(n, 64), pk(n, 64), gen(n, 64), m(n, 32);
+    for (size_t i = 0; i < n; ++i) {
+        u.put(i, 0, items[i].sig.u); r.put(i, 0, items[i].sig.R); pk.put(i, 0, items[i].pk);
+        gen.put(i, 0, items[i].generator); m.put(i, 0, items[i].message);
+    }
+    std::vector<uint8_t> st(status ? n : 0);
+    int v = 0;
+    const bool ok = detail::verdict(jjs_verify_all_vargen(u.data(), r.data(), pk.data(), gen.data(), m.data(), n,
+                                                          status ? st.data() : nullptr, &v), v, "jjs_verify_all_vargen");
+    if (status) *status = detail::results(st);
+    return ok;
+}
+
 // Registered key sets (include/jjs_gpu.h jjs_keyset_*): keys validated and tabled once on the device, then verified against by
 // index.  Move-only; the destructor destroys the set (calls already queued on a stream still complete).
 class KeySet {

@@ -69,6 +69,12 @@ SIGNATURES = {
     "jjs_keyset_info": [ctypes.c_uint64, _P],
     "jjs_keyset_verify": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_keyset_verify_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P],
+    "jjs_verify_all_single": [_P, _P, _P, _P, _Z, _P, _P],
+    "jjs_verify_all_double": [_P, _P, _P, _P, _P, _P, _Z, _P, _P],
+    "jjs_verify_all_vargen": [_P, _P, _P, _P, _P, _Z, _P, _P],
+    "jjs_verify_all_single_dev": [_P, _P, _P, _P, _Z, _P, _P],
+    "jjs_verify_all_double_dev": [_P, _P, _P, _P, _P, _P, _Z, _P, _P],
+    "jjs_verify_all_vargen_dev": [_P, _P, _P, _P, _P, _Z, _P, _P],
 }
 # include/jjs_gpu_profiling.h: present in libjjs_gpu_prof.so only
 PROFILING_SIGNATURES = {

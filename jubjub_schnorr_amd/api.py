@@ -133,6 +133,36 @@ class Engine:
                       tally.ctypes.data_as(ctypes.c_void_p)), f"jjs_verify_{scheme}{suffix}")
         return status, tally
 
+    def verify_all(self, scheme: str, *arrays, statuses_on_failure: bool = True):
+        """One verdict for the whole batch (jjs_verify_all_*): True when every item would get status 0 from `verify`.
+        Same arguments as `verify` (affine columns).  numpy inputs: blocking, returns (bool, status or None) -- the
+        statuses of `verify`, byte for byte, when the verdict is False and `statuses_on_failure` is set.  torch CUDA
+        tensors: asynchronous on the current stream, returns a device uint32 tensor of one element (1 accepted, 0 not);
+        run `verify` for the statuses."""
+        widths = self._WIDTHS[scheme]
+        if len(arrays) != len(widths):
+            raise ValueError(f"{scheme} verify_all takes {len(widths)} arrays")
+        if _is_torch(arrays[0]):
+            import torch
+            n = arrays[0].shape[0]
+            ptrs = [self._dev_ptr(a, w, n) for a, w in zip(arrays, widths)]
+            verdict = torch.empty(1, dtype=torch.int32, device=arrays[0].device)
+            fn = getattr(self._lib, f"jjs_verify_all_{scheme}_dev")
+            _ffi.check(fn(*ptrs, n, ctypes.c_void_p(verdict.data_ptr()), self._stream()), f"jjs_verify_all_{scheme}_dev")
+            return verdict.view(torch.uint32) if hasattr(torch, "uint32") else verdict
+        host = [self._host(a, w) for a, w in zip(arrays, widths)]
+        n = host[0].shape[0]
+        if any(h.shape[0] != n for h in host):
+            raise ValueError("all arrays must have the same number of items")
+        status = np.empty(n, np.uint8) if statuses_on_failure else None
+        verdict = ctypes.c_int(-1)
+        fn = getattr(self._lib, f"jjs_verify_all_{scheme}")
+        _ffi.check(fn(*[h.ctypes.data_as(ctypes.c_void_p) for h in host], n,
+                      status.ctypes.data_as(ctypes.c_void_p) if status is not None else None, ctypes.byref(verdict)),
+                   f"jjs_verify_all_{scheme}")
+        ok = verdict.value == 1
+        return ok, (None if ok or status is None else status)
+
     PATH_STAT_NAMES = ("latency", "throughput", "key_tables_wide", "key_tables_narrow", "keys_do_not_repeat",
                        "keys_probe_limit", "keys_pool_too_small", "keys_no_memory", "key_pool_bytes", "lane_launches", "lane_calls")
 
@@ -402,6 +432,16 @@ class PublicKey:
                                 _rows([k.point for k, _, _ in items], 64), _rows([m for _, _, m in items], 32))
         return st
 
+    @staticmethod
+    def verify_all(items: Sequence[tuple]) -> bool:
+        """items: (PublicKey, Signature, message bytes).  True when every item verifies (one verdict: jjs_verify_all_single)."""
+        if not items:
+            return True
+        ok, _ = engine().verify_all("single", _rows([s.u for _, s, _ in items], 32), _rows([s.R for _, s, _ in items], 64),
+                                    _rows([k.point for k, _, _ in items], 64), _rows([m for _, _, m in items], 32),
+                                    statuses_on_failure=False)
+        return ok
+
 
 @dataclass(frozen=True)
 class PublicKeyDouble:
@@ -423,6 +463,17 @@ class PublicKeyDouble:
             _rows([k.pk_prime for k, _, _ in items], 64), _rows([m for _, _, m in items], 32))
         return st
 
+    @staticmethod
+    def verify_all(items: Sequence[tuple]) -> bool:
+        """True when every (PublicKeyDouble, SignatureDouble, message) item verifies (jjs_verify_all_double)."""
+        if not items:
+            return True
+        ok, _ = engine().verify_all(
+            "double", _rows([s.u for _, s, _ in items], 32), _rows([s.R for _, s, _ in items], 64),
+            _rows([s.R_prime for _, s, _ in items], 64), _rows([k.pk for k, _, _ in items], 64),
+            _rows([k.pk_prime for k, _, _ in items], 64), _rows([m for _, _, m in items], 32), statuses_on_failure=False)
+        return ok
+
 
 @dataclass(frozen=True)
 class PublicKeyVarGen:
@@ -443,6 +494,17 @@ class PublicKeyVarGen:
             _rows([k.pk for k, _, _ in items], 64), _rows([k.generator for k, _, _ in items], 64),
             _rows([m for _, _, m in items], 32))
         return st
+
+    @staticmethod
+    def verify_all(items: Sequence[tuple]) -> bool:
+        """True when every (PublicKeyVarGen, SignatureVarGen, message) item verifies (jjs_verify_all_vargen)."""
+        if not items:
+            return True
+        ok, _ = engine().verify_all(
+            "vargen", _rows([s.u for _, s, _ in items], 32), _rows([s.R for _, s, _ in items], 64),
+            _rows([k.pk for k, _, _ in items], 64), _rows([k.generator for k, _, _ in items], 64),
+            _rows([m for _, _, m in items], 32), statuses_on_failure=False)
+        return ok
 
 
 # ------------------------------------------------------------------------------------------------

@@ -90,6 +90,8 @@ struct call_slot {
     size_t wire_items = 0;
     uint8_t* small = nullptr;         // latency path: window tables of the chain lanes + per-point verdicts (grow-only)
     size_t small_bytes = 0;
+    uint8_t* verdict = nullptr;       // batch verdict (verdict_calls.h): MSM terms, sort, buckets, or the per-item route's tally (grow-only)
+    size_t verdict_bytes = 0;
     // key-table path (big and medium slots).  Two arenas, both grow-only: the index (hash tables, key ids, item order:
     // sized by the batch) and the pool of per-key bases and window tables, which is sized by the number of distinct keys
     // the slot's calls have carried -- KEY_POOL_INITIAL_BYTES to begin with, more once a call has shown that it needs more.

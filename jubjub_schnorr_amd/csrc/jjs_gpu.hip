@@ -37,7 +37,9 @@
 #include <sched.h>
 #include <climits>
 #include <linux/futex.h>
+#include <sys/random.h>
 #include <sys/syscall.h>
+#include <cerrno>
 #include <unistd.h>
 #include <thread>
 #include <vector>
@@ -56,6 +58,7 @@
 #include "keyset.h"
 #include "sign_core.h"
 #include "multisig_core.h"
+#include "batch_verdict.h"
 #include "jjs_sponge_tags_long.inc"
 
 using namespace jjs;
@@ -63,6 +66,7 @@ using namespace jjs;
 namespace {
 
 #include "device_kernels.h"
+#include "verdict_kernels.h"
 #include "engine_state.h"
 #include "verify_job.h"
 
@@ -196,7 +200,7 @@ void free_device(device_state& d) {
     for (call_slot& c : d.slots) {
         if (c.key_stream) { (void)hipStreamSynchronize(c.key_stream); (void)hipStreamDestroy(c.key_stream); }
         if (c.table_stream) { (void)hipStreamSynchronize(c.table_stream); (void)hipStreamDestroy(c.table_stream); }
-        void* sb[] = {c.workspace, c.pending, c.prep, c.wire, c.small, c.keys, c.key_pool};
+        void* sb[] = {c.workspace, c.pending, c.prep, c.wire, c.small, c.keys, c.key_pool, c.verdict};
         for (void* b : sb)
             if (b) (void)hipFree(b);
         if (c.seen) (void)hipHostFree(c.seen);
@@ -654,6 +658,9 @@ int jjs_verify_vargen(const uint8_t* u, const uint8_t* R, const uint8_t* PK, con
     return host_call(JJS_SCHEME_VARGEN, JJS_FORMAT_AFFINE, p, n, status, tally);
 }
 
+// ---- one verdict per batch (batch_verdict.h) -------------------------------------------------------------------
+#include "verdict_calls.h"
+
 // ---- wire formats: on-device decoding, then the same verify kernels -----------------------------------
 int jjs_verify_single_wire_dev(const void* sig, const void* pk, const void* m, size_t n, void* status, void* tally, void* stream) {
     const void* d[] = {sig, pk, m};
@@ -801,7 +808,7 @@ int jjs_memory_stats(uint64_t out[JJS_MEMORY_STATS]) {
     uint64_t pool = 0, slots = 0, lanes = 0;
     for (const call_slot& c : g->slots) {
         pool += c.key_pool_bytes;
-        slots += c.pending_items * 8 + c.prep_items * 65 + c.wire_items * (4 * 64 + 16 + 2 * 48) + c.small_bytes + c.keys_bytes;
+        slots += c.pending_items * 8 + c.prep_items * 65 + c.wire_items * (4 * 64 + 16 + 2 * 48) + c.small_bytes + c.keys_bytes + c.verdict_bytes;
     }
     for (const host_lane& l : g->lanes) lanes += l.dev_bytes + l.pinned_bytes;
     out[JJS_MEMORY_KEY_POOLS] = pool;
@@ -1089,6 +1096,8 @@ int jjs_debug_force_path(int which) {
     g_force_positions = ((which >> 4) & 15) == 4 || ((which >> 4) & 15) == 8 ? ((which >> 4) & 15) : (((which >> 4) & 15) == 15 ? 16 : 0);    // 0x42 / 0x82 / 0xF2: latency path, 4 / 8 / 16 pieces
     g_keep_order = (which & 0x1000) != 0;
     g_force_window = ((which >> 8) & 15) == KT_WINDOW_NARROW ? ((which >> 8) & 15) : 0;   // 0x500: narrow key-table windows whatever the keys
+    g_force_verdict = (which & 0x2000) ? 1 : ((which & 0x4000) ? 2 : 0);   // jjs_verify_all_*: 0x2000 the verdict algorithm, 0x4000 the per-item path
+    g_force_msm_window = (which >> 16) & 31;                                // ... and bits 16-20 its window width (8-16; 0 by size)
     return JJS_OK;
 }
 int jjs_debug_host_timing(double out[8]) {
@@ -1099,6 +1108,7 @@ int jjs_debug_host_timing(double out[8]) {
 int jjs_debug_pin_hash_seed(int on) {
     std::lock_guard<std::mutex> lock(L.mu);
     g_pin_hash_seed = on != 0;
+    g_pin_batch_seed = (on & 2) != 0;                // jjs_verify_all_*: weights from a fixed key (verdict_calls.h)
     return JJS_OK;
 }
 int jjs_debug_fail_key_arena(int on) {

@@ -1,0 +1,251 @@
+// Part of jjs_gpu.hip (included among the extern "C" entry points): the batch verdict (batch_verdict.h, msm.h;
+// include/jjs_gpu.h jjs_verify_all_*) -- the routing between the verdict algorithm and the per-item path, the launches
+// of the verdict algorithm (its kernels: verdict_kernels.h), and the entry points.
+
+// ---- routing --------------------------------------------------------------------------------------------------------------
+// The verdict algorithm runs where it was measured faster than the per-item path and a tally check (DESIGN.md 5f,
+// profiles/r06_verify_all.jsonl): from VERDICT_MIN_ITEMS[scheme] items on.  SIZE_MAX: nowhere.  It wins only on batches
+// whose keys do not repeat (1.22x single, 1.31x double, 1.43x var-gen at 2^20) and loses 1.7-2.1x at SURVEY 8(d)'s 4 096
+// keys; the key class of a batch is found on the device, after the call is queued, so no size alone is safe.
+constexpr size_t VERDICT_MIN_ITEMS[3] = {SIZE_MAX, SIZE_MAX, SIZE_MAX};
+#if defined(JJS_PROFILING)
+static int g_force_verdict = 0;          // jjs_debug_force_path 0x2000: the verdict algorithm at any size; 0x4000: never
+static int g_force_msm_window = 0;       // ... bits 16-20: the MSM's window width (0: by size)
+static bool g_pin_batch_seed = false;    // jjs_debug_pin_hash_seed(on) with on & 2: the key 00 01 .. 1f
+#endif
+static bool verdict_route(int scheme, size_t n) {
+    const size_t kinds = scheme == JJS_SCHEME_DOUBLE ? 4 : (scheme == JJS_SCHEME_SINGLE ? 2 : 3);
+    if (kinds * n >= 0x80000000ull) return false;        // term indices carry a sign bit
+#if defined(JJS_PROFILING)
+    if (g_force_verdict) return g_force_verdict == 1;
+#endif
+    return n >= VERDICT_MIN_ITEMS[scheme];
+}
+static int batch_seed(uint32_t seed[8]) {
+#if defined(JJS_PROFILING)
+    if (g_pin_batch_seed) {
+        for (int i = 0; i < 8; ++i) seed[i] = 0x03020100u + 0x04040404u * (uint32_t)i;
+        return JJS_OK;
+    }
+#endif
+    uint8_t* p = reinterpret_cast<uint8_t*>(seed);
+    size_t got = 0;
+    while (got < 32) {
+        const ssize_t r = getrandom(p + got, 32 - got, 0);
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            return fail(JJS_ERR_HIP, "getrandom failed: errno %d", errno);
+        }
+        got += (size_t)r;
+    }
+    return JJS_OK;
+}
+
+static int ensure_verdict(size_t bytes) {
+    if (bytes <= sl->verdict_bytes) return JJS_OK;
+    const size_t cap = grown(bytes);
+    return regrow(sl->verdict, sl->verdict_bytes, sl->verdict_bytes, cap, cap);
+}
+static verify_params verdict_params(int scheme, const void* const* d, size_t n) {
+    const out_ptrs o{nullptr, nullptr, nullptr, nullptr};
+    if (scheme == JJS_SCHEME_SINGLE)
+        return params_single((const uint8_t*)d[0], (const uint8_t*)d[1], (const uint8_t*)d[2], (const uint8_t*)d[3], n, g->comb_g, o);
+    if (scheme == JJS_SCHEME_DOUBLE)
+        return params_double((const uint8_t*)d[0], (const uint8_t*)d[1], (const uint8_t*)d[2], (const uint8_t*)d[3], (const uint8_t*)d[4],
+                             (const uint8_t*)d[5], n, g->tag, g->comb_g, g->comb_gn, o);
+    return params_vargen((const uint8_t*)d[0], (const uint8_t*)d[1], (const uint8_t*)d[2], (const uint8_t*)d[3], (const uint8_t*)d[4], n, o);
+}
+
+// The verdict algorithm on stream s (under L.mu; g is the device): d = the affine columns in the entry point's order.
+static int verdict_launch_msm(int scheme, const void* const* d, size_t n, uint32_t* verdict, hipStream_t s) {
+    bv_params B{};
+    B.V = verdict_params(scheme, d, n);
+    if (int rc = batch_seed(B.seed)) return rc;
+    B.n_kinds = bv_kinds(B.V);
+    msm_params M{};
+    M.n = n; M.N = (uint64_t)B.n_kinds * n;
+    for (uint32_t k = 0; k < B.n_kinds; ++k) M.neg_kinds |= bv_kind_negated(B.V, k) ? 1u << k : 0u;
+    M.c = msm_pick_window(M.N);
+#if defined(JJS_PROFILING)
+    if (g_force_msm_window >= 8 && g_force_msm_window <= MSM_MAX_WINDOW) M.c = g_force_msm_window;
+#endif
+    B.z_bits = msm_weight_bits(M.c);
+    M.W = msm_windows(M.c); M.B = msm_buckets(M.c); M.K = msm_segments(M.c); M.L = M.B / M.K;
+    const uint32_t blocks = (uint32_t)grid_for(g->grid_prepare, n);
+    const size_t nb = (size_t)M.W * M.B;
+    const size_t sz[] = {pad256(64 + 4 * ((nb + MSM_SCAN_SPAN - 1) / MSM_SCAN_SPAN + 1)), pad256((size_t)blocks * 64), pad256(M.N * MSM_TERM_WORDS * 4), pad256(M.N * 32), pad256((nb + 1) * 4),
+                         pad256(nb * 4), pad256(M.N * M.W * 4), pad256(nb * MSM_EXT_WORDS * 4), pad256((size_t)M.W * M.K * MSM_EXT_WORDS * 4),
+                         pad256((size_t)M.W * MSM_EXT_WORDS * 4)};
+    size_t total = 0;
+    for (size_t x : sz) total += x;
+    pick_slot(n, s);
+    if (int rc = ensure_verdict(total)) return rc;
+    uint8_t* p = sl->verdict;
+    uint8_t* q[10];
+    for (int i = 0; i < 10; ++i) { q[i] = p; p += sz[i]; }
+    B.fail = reinterpret_cast<uint32_t*>(q[0]);
+    B.partial = q[1];
+    B.terms = reinterpret_cast<uint32_t*>(q[2]);
+    B.scalars = q[3];
+    M.terms = B.terms; M.scalars = B.scalars;
+    M.off = reinterpret_cast<uint32_t*>(q[4]); M.cursor = reinterpret_cast<uint32_t*>(q[5]); M.order = reinterpret_cast<uint32_t*>(q[6]);
+    M.buckets = reinterpret_cast<uint32_t*>(q[7]); M.segs = reinterpret_cast<uint32_t*>(q[8]); M.win = reinterpret_cast<uint32_t*>(q[9]);
+    if (int rc = begin_shared(s)) return rc;
+    clear_params Z{};
+    Z.p[0] = B.fail; Z.bytes[0] = 4;
+    Z.p[1] = M.off; Z.bytes[1] = (nb + 1) * 4;
+    hipLaunchKernelGGL(clear_kernel, dim3((unsigned)grid_for(256, nb / 16 + 1)), dim3(BLOCK), 0, s, Z);
+    hipLaunchKernelGGL(bv_item_kernel, dim3(blocks), dim3(BLOCK), 0, s, B);
+    const unsigned term_blocks = (unsigned)grid_for(8192, M.N);
+    hipLaunchKernelGGL(msm_sort_kernel<false>, dim3(term_blocks), dim3(BLOCK), 0, s, M);
+    const unsigned spans = (unsigned)((nb + MSM_SCAN_SPAN - 1) / MSM_SCAN_SPAN);
+    uint32_t* span_sum = reinterpret_cast<uint32_t*>(q[0]) + 16;        // <= 4096 + 1 words behind the fail word
+    hipLaunchKernelGGL(msm_scan_kernel<0>, dim3(spans), dim3(1024), 0, s, M, span_sum);
+    hipLaunchKernelGGL(msm_scan_kernel<1>, dim3(1), dim3(1024), 0, s, M, span_sum);
+    hipLaunchKernelGGL(msm_scan_kernel<2>, dim3(spans), dim3(1024), 0, s, M, span_sum);
+    hipLaunchKernelGGL(msm_sort_kernel<true>, dim3(term_blocks), dim3(BLOCK), 0, s, M);
+    hipLaunchKernelGGL(msm_bucket_kernel, dim3((unsigned)((nb + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, M);
+    hipLaunchKernelGGL(msm_segment_kernel, dim3((unsigned)(((size_t)M.W * M.K + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, M);
+    hipLaunchKernelGGL(msm_window_kernel, dim3((unsigned)M.W), dim3(BLOCK), 0, s, M);
+    hipLaunchKernelGGL(bv_final_kernel, dim3(1), dim3(BLOCK), 0, s, B, M, blocks, verdict);
+    HIP_TRY(hipGetLastError());
+    return end_shared(s);
+}
+// The per-item route on stream s (under L.mu): the resident call with its tally in the slot, then the verdict from the tally.
+static int verdict_launch_items(int scheme, const void* const* d, size_t n, uint32_t* verdict, hipStream_t s) {
+    staged_call C;
+    if (int rc = SHAPES[scheme][JJS_FORMAT_AFFINE].build(d, n, nullptr, nullptr, s, C)) return rc;
+    if (int rc = ensure_verdict(256)) return rc;
+    unsigned long long* tally = reinterpret_cast<unsigned long long*>(sl->verdict);
+    C.P.tally = tally;
+    if (int rc = launch_staged(C, s)) return rc;
+    hipLaunchKernelGGL(tally_verdict_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long*)tally, (uint64_t)n, verdict);
+    HIP_TRY(hipGetLastError());
+    return end_shared(s);                       // the slot's tally is read until here
+}
+static size_t verdict_cols(int scheme) { return scheme == JJS_SCHEME_DOUBLE ? 6 : (scheme == JJS_SCHEME_SINGLE ? 4 : 5); }
+
+// a resident verdict call: device columns d[], the verdict word on the device, asynchronous on `stream`
+static int verdict_dev(int scheme, const void* const* d, size_t n, void* verdict, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (!verdict || (reinterpret_cast<uintptr_t>(verdict) & 3u)) return fail(JJS_ERR_ARG, "null or misaligned verdict word");
+    if (n == 0) {
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)verdict, 1, 1, s));
+        return JJS_OK;
+    }
+    for (size_t k = 0; k < verdict_cols(scheme); ++k)
+        if (!d[k] || !aligned16(d[k])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
+    return no_throw([&] {
+        return verdict_route(scheme, n) ? verdict_launch_msm(scheme, d, n, (uint32_t*)verdict, s)
+                                        : verdict_launch_items(scheme, d, n, (uint32_t*)verdict, s);
+    });
+}
+
+// a host-buffer verdict call: blocking.  The per-item route is the existing host call (its statuses are the caller's);
+// the verdict algorithm uploads the columns whole to the key-set staging area (one such call at a time per device,
+// host_mu), and on a verdict of 0 the statuses come from the existing host call.
+static int verdict_host(int scheme, const uint8_t* const* ptrs, size_t n, uint8_t* status, int* verdict) {
+    if (!verdict) return fail(JJS_ERR_ARG, "null verdict");
+    const size_t ncol = verdict_cols(scheme);
+    for (size_t k = 0; k < ncol; ++k)
+        if (n && !ptrs[k]) return fail(JJS_ERR_ARG, "null input pointer");
+    device_state* dev = nullptr;
+    bool msm = false;
+    {
+        std::lock_guard<std::mutex> lock(L.mu);
+        if (int rc = check_ready()) return rc;
+        if (n == 0) { *verdict = 1; return JJS_OK; }
+        msm = L.devs.size() == 1 && verdict_route(scheme, n);
+        dev = g;
+        if (msm) ++g_keyset_host_calls;       // jjs_shutdown does not free `dev` before this call has left
+    }
+    uint64_t tally[4] = {};
+    if (!msm) {
+        if (int rc = host_call(scheme, JJS_FORMAT_AFFINE, ptrs, n, status, tally)) return rc;
+        *verdict = tally[0] == n ? 1 : 0;
+        return JJS_OK;
+    }
+    int v = 0;
+    {
+        struct leave {
+            ~leave() {
+                std::lock_guard<std::mutex> lock(L.mu);
+                --g_keyset_host_calls;
+                L.lane_cv.notify_all();
+            }
+        } leave_on_every_way_out;
+        std::lock_guard<std::mutex> big(dev->host_mu);
+        g = dev;
+        int rc = no_throw([&]() -> int {
+            size_t off[7], total = 0;
+            for (size_t i = 0; i < ncol; ++i) { off[i] = total; total += pad256(SHAPES[scheme][JJS_FORMAT_AFFINE].col[i].width * n); }
+            off[ncol] = total; total += 256;                          // the verdict word
+            if (total > dev->ks_stage_bytes) {
+                const size_t cap = grown(total);
+                if (int r = regrow(dev->ks_stage, dev->ks_stage_bytes, dev->ks_stage_bytes, cap, cap)) return r;
+            }
+            HIP_TRY(hipSetDevice(dev->device));
+            hipStream_t s = dev->ks_stream;
+            const void* d[6] = {};
+            for (size_t i = 0; i < ncol; ++i) {
+                d[i] = dev->ks_stage + off[i];
+                HIP_TRY(hipMemcpyAsync(dev->ks_stage + off[i], ptrs[i], SHAPES[scheme][JJS_FORMAT_AFFINE].col[i].width * n, hipMemcpyHostToDevice, s));
+            }
+            uint32_t* vw = reinterpret_cast<uint32_t*>(dev->ks_stage + off[ncol]);
+            {
+                std::lock_guard<std::mutex> lock(L.mu);
+                if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
+                if (int r = verdict_launch_msm(scheme, d, n, vw, s)) return r;
+            }
+            uint32_t hv = 0;
+            HIP_TRY(hipMemcpyAsync(&hv, vw, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            v = hv ? 1 : 0;
+            return JJS_OK;
+        });
+        if (rc) return rc;
+    }
+    *verdict = v;
+    if (status) {
+        if (v) memset(status, 0, n);
+        else if (int rc = host_call(scheme, JJS_FORMAT_AFFINE, ptrs, n, status, tally)) return rc;
+    }
+    return JJS_OK;
+}
+
+extern "C" {
+
+int jjs_verify_all_single(const uint8_t* u, const uint8_t* R, const uint8_t* PK, const uint8_t* m, size_t n, uint8_t* status,
+                          int* verdict) {
+    const uint8_t* p[] = {u, R, PK, m};
+    return verdict_host(JJS_SCHEME_SINGLE, p, n, status, verdict);
+}
+int jjs_verify_all_double(const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* PK, const uint8_t* PKp,
+                          const uint8_t* m, size_t n, uint8_t* status, int* verdict) {
+    const uint8_t* p[] = {u, R, Rp, PK, PKp, m};
+    return verdict_host(JJS_SCHEME_DOUBLE, p, n, status, verdict);
+}
+int jjs_verify_all_vargen(const uint8_t* u, const uint8_t* R, const uint8_t* PK, const uint8_t* Gen, const uint8_t* m, size_t n,
+                          uint8_t* status, int* verdict) {
+    const uint8_t* p[] = {u, R, PK, Gen, m};
+    return verdict_host(JJS_SCHEME_VARGEN, p, n, status, verdict);
+}
+int jjs_verify_all_single_dev(const void* u, const void* R, const void* PK, const void* m, size_t n, void* verdict, void* stream) {
+    const void* d[] = {u, R, PK, m};
+    return verdict_dev(JJS_SCHEME_SINGLE, d, n, verdict, stream);
+}
+int jjs_verify_all_double_dev(const void* u, const void* R, const void* Rp, const void* PK, const void* PKp, const void* m, size_t n,
+                              void* verdict, void* stream) {
+    const void* d[] = {u, R, Rp, PK, PKp, m};
+    return verdict_dev(JJS_SCHEME_DOUBLE, d, n, verdict, stream);
+}
+int jjs_verify_all_vargen_dev(const void* u, const void* R, const void* PK, const void* Gen, const void* m, size_t n, void* verdict,
+                              void* stream) {
+    const void* d[] = {u, R, PK, Gen, m};
+    return verdict_dev(JJS_SCHEME_VARGEN, d, n, verdict, stream);
+}
+
+
+}  // extern "C"

@@ -1,0 +1,111 @@
+// CPU build of csrc/batch_verdict.h and csrc/msm.h (the batch verdict of jjs_verify_all_*) for tests/test_verify_all_host.py:
+// the device's steps run here in loops -- the per-item pass (bv_item), the counting sort of the MSM terms, one bucket, one
+// segment and one window at a time, Horner's rule -- with the same functions.  The comb tables and the double scheme's tag
+// come from host_harness.cpp.
+#include "host_harness.cpp"
+#include "batch_verdict.h"
+
+namespace {
+
+// sum of the terms (terms: N cached addends; scalars N x 32; neg: N flags) by the bucket method with c-bit windows
+ext_pt host_msm(const uint32_t* terms, const uint8_t* scalars, const uint8_t* neg, uint64_t N, int c) {
+    const int W = msm_windows(c);
+    const uint32_t B = msm_buckets(c), K = msm_segments(c), L = B / K;
+    std::vector<uint32_t> off((size_t)W * B + 1, 0), order;
+    for (int pass = 0; pass < 2; ++pass) {                     // 0: count, 1: scatter
+        std::vector<uint32_t> cursor;
+        if (pass) {
+            uint32_t sum = 0;
+            for (size_t i = 0; i < off.size(); ++i) { const uint32_t v = off[i]; off[i] = sum; sum += v; }
+            order.assign(sum, 0);
+            cursor.assign(off.begin(), off.end());
+        }
+        for (uint64_t t = 0; t < N; ++t) {
+            const words8 s = load_words(fe_src{scalars, 32, 0}, t);
+            uint32_t carry = 0;
+            for (int j = 0; j < W; ++j) {
+                const int32_t d = msm_digit_step(s, j, c, W, carry);
+                if (!d) continue;
+                const uint32_t id = (uint32_t)j * B + msm_slot(j, d, t, c, W);
+                if (!pass) ++off[id];
+                else order[cursor[id]++] = (uint32_t)t | (((d < 0) != (neg[t] != 0)) ? MSM_NEG : 0u);
+            }
+        }
+    }
+    std::vector<uint32_t> buckets((size_t)W * B * MSM_EXT_WORDS), win((size_t)W * MSM_EXT_WORDS);
+    for (uint32_t id = 0; id < (uint32_t)W * B; ++id) msm_store_ext(&buckets[(size_t)id * MSM_EXT_WORDS], msm_bucket(off.data(), order.data(), terms, id));
+    for (int j = 0; j < W; ++j) {
+        ext_pt acc = ext_identity();
+        for (uint32_t seg = 0; seg < K; ++seg) acc = msm_add_ext(acc, msm_segment(buckets.data(), B, (uint32_t)j, seg, L, j == W - 1 ? msm_top_split(c) : 0));
+        msm_store_ext(&win[(size_t)j * MSM_EXT_WORDS], acc);
+    }
+    return msm_combine(win.data(), W, c);
+}
+
+void to_affine_bytes(const ext_pt& p, uint8_t* out) {
+    const fe_n zi = fq_inverse(p.z);
+    store_words(out, 0, fq_to_words(fq_mul(p.x, zi)));
+    store_words(out, 1, fq_to_words(fq_mul(p.y, zi)));
+}
+
+}  // namespace
+
+extern "C" {
+
+int jjs_vh_chacha20_block(const uint8_t key[32], uint32_t counter, const uint8_t nonce[12], uint8_t out[64]) {
+    uint32_t k[8], nn[3], o[16];
+    memcpy(k, key, 32);
+    memcpy(nn, nonce, 12);
+    chacha20_block(k, counter, nn, o);
+    memcpy(out, o, 64);
+    return 0;
+}
+
+// points: N x 64 affine (u || v, canonical little-endian); scalars: N x 32 (< 2^252); neg: N flags; c: window width (0: by N).
+// out: the affine sum (64 bytes)
+int jjs_vh_msm(const uint8_t* points, const uint8_t* scalars, const uint8_t* neg, size_t N, int c, uint8_t* out) {
+    if (c == 0) c = msm_pick_window(N);
+    if (c < 2 || c > MSM_MAX_WINDOW) return -1;
+    std::vector<uint32_t> terms(N * MSM_TERM_WORDS + 4);
+    uint32_t* t = (uint32_t*)(((uintptr_t)terms.data() + 15) & ~(uintptr_t)15);
+    const fe_src src{points, 64, 0};
+    for (size_t i = 0; i < N; ++i) msm_store_term(t + i * MSM_TERM_WORDS, load_fq(src, i), load_fq(src, i, 32));
+    to_affine_bytes(host_msm(t, scalars, neg, N, c), out);
+    return 0;
+}
+
+// scheme 0 / 1 / 2, columns in the order of jjs_verify_*; p4 = PK' (double) or unused; seed: 32 bytes; c: window (0: by size)
+int jjs_vh_verify_all(int scheme, const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* PK, const uint8_t* PK2,
+                      const uint8_t* m, size_t n, const uint8_t seed[32], int c, int* verdict) {
+    if (scheme < 0 || scheme > 2 || !verdict) return -1;
+    if (n == 0) { *verdict = 1; return 0; }
+    ensure_tables();
+    const out_ptrs o{nullptr, nullptr, nullptr, nullptr};
+    bv_params B{};
+    B.V = scheme == 0 ? params_single(u, R, PK, m, n, g_comb_g.data(), o)
+        : scheme == 1 ? params_double(u, R, Rp, PK, PK2, m, n, (const uint8_t*)g_tag, g_comb_g.data(), g_comb_gn.data(), o)
+                      : params_vargen(u, R, PK, PK2, m, n, o);
+    memcpy(B.seed, seed, 32);
+    B.n_kinds = bv_kinds(B.V);
+    const size_t N = (size_t)B.n_kinds * n;
+    if (c == 0) c = msm_pick_window(N);
+    B.z_bits = msm_weight_bits(c);
+    std::vector<uint32_t> terms(N * MSM_TERM_WORDS + 4);
+    std::vector<uint8_t> scalars(N * 32 + 16), neg(N);
+    B.terms = (uint32_t*)(((uintptr_t)terms.data() + 15) & ~(uintptr_t)15);
+    B.scalars = (uint8_t*)(((uintptr_t)scalars.data() + 15) & ~(uintptr_t)15);
+    bool failed = false;
+    words8 sum[2] = {words_zero(), words_zero()};
+    for (uint64_t i = 0; i < n; ++i) {
+        words8 zu[2];
+        failed = !bv_item(B, i, zu) || failed;
+        sum[0] = fr_add(sum[0], zu[0]);
+        sum[1] = fr_add(sum[1], zu[1]);
+    }
+    for (size_t t = 0; t < N; ++t) neg[t] = bv_kind_negated(B.V, (uint32_t)(t / n)) ? 1 : 0;
+    const ext_pt total = host_msm(B.terms, B.scalars, neg.data(), N, c);
+    *verdict = bv_verdict(B.V, total, sum, failed) ? 1 : 0;
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,67 @@
+"""ctypes loader for tests/hostbuild/libjjs_verdict_hosttest.so: csrc/batch_verdict.h and csrc/msm.h compiled for the CPU
+(the recipe of hostlib.py)."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+SRC = os.path.join(HERE, "hostbuild", "verdict_harness.cpp")
+LIB = os.path.join(HERE, "hostbuild", "libjjs_verdict_hosttest.so")
+CSRC = os.path.join(ROOT, "jubjub_schnorr_amd", "csrc")
+SCHEMES = {"single": 0, "double": 1, "vargen": 2}
+_lib = None
+
+
+def _stale():
+    if not os.path.exists(LIB):
+        return True
+    t = os.path.getmtime(LIB)
+    deps = [SRC, os.path.join(HERE, "hostbuild", "host_harness.cpp")] + \
+        [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def load():
+    global _lib
+    if _lib is not None:
+        return _lib
+    if _stale():
+        san = ["-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=undefined"] if os.environ.get("JJS_HOST_SANITIZE") else ["-O2"]
+        subprocess.check_call(["g++", *san, "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas",
+                               "-I" + CSRC, "-o", LIB, SRC])
+    _lib = ctypes.CDLL(LIB)
+    return _lib
+
+
+def _p(a):
+    return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+
+
+def chacha20_block(key: bytes, counter: int, nonce: bytes) -> bytes:
+    out = ctypes.create_string_buffer(64)
+    assert load().jjs_vh_chacha20_block(key, ctypes.c_uint32(counter), nonce, out) == 0
+    return out.raw
+
+
+def msm(points, scalars, neg=None, c=0):
+    """points: (N, 64) affine; scalars: (N, 32) below 2^252; neg: N flags (the term is -P).  Returns the affine sum (64 bytes)."""
+    points = np.ascontiguousarray(points, np.uint8)
+    scalars = np.ascontiguousarray(scalars, np.uint8)
+    neg = np.ascontiguousarray(np.zeros(len(points), np.uint8) if neg is None else neg, np.uint8)
+    out = np.zeros(64, np.uint8)
+    assert load().jjs_vh_msm(_p(points), _p(scalars), _p(neg), ctypes.c_size_t(len(points)), c, _p(out)) == 0
+    return out
+
+
+def verify_all(scheme, b, seed=bytes(32), c=0):
+    """The batch verdict of the CPU build for a batch dict (helpers.make_batch): 1 or 0."""
+    cols = {k: np.ascontiguousarray(v, np.uint8) for k, v in b.items()}
+    second = cols.get("PKp") if scheme == "double" else cols.get("Gen")
+    verdict = ctypes.c_int(-1)
+    rc = load().jjs_vh_verify_all(SCHEMES[scheme], _p(cols["u"]), _p(cols["R"]), _p(cols.get("Rp")), _p(cols["PK"]), _p(second),
+                                  _p(cols["m"]), ctypes.c_size_t(len(cols["u"])), seed, c, ctypes.byref(verdict))
+    assert rc == 0
+    return verdict.value
