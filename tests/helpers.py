@@ -44,6 +44,49 @@ def rand_mod(rng: np.random.Generator, n: int, mod: int, nonzero=False) -> np.nd
     return out
 
 
+def limbs_val(row) -> int:
+    """The value of a radix-2^29 limb vector (limbs may exceed 29 bits)."""
+    return sum(int(x) << (29 * i) for i, x in enumerate(row))
+
+
+def edge_limb_vectors(rng: np.random.Generator, n: int, limb_units: int, value_units: int) -> np.ndarray:
+    """Limb vectors with every limb < limb_units * 2^29 and value < value_units * q: random, plus vectors
+    pushed against both bounds."""
+    out = []
+    while len(out) < n:
+        kind = len(out) % 4
+        cap = limb_units << 29
+        if kind == 0:
+            l = [int(rng.integers(0, cap)) for _ in range(9)]
+        elif kind == 1:
+            l = [cap - 1] * 9                       # every limb at its maximum
+        elif kind == 2:
+            l = [cap - 1 - int(rng.integers(0, 4)) for _ in range(9)]
+        else:
+            l = [int(rng.integers(0, cap)) for _ in range(8)] + [cap - 1]
+        # clamp the value below value_units * q by lowering the top limb
+        lim = value_units * o.Q - 1
+        low = sum(x << (29 * i) for i, x in enumerate(l[:8]))
+        l[8] = min(l[8], max(0, (lim - low) >> 232))
+        if limbs_val(l) <= lim:
+            out.append(l)
+    return np.array(out, np.uint64).astype(np.uint32)
+
+
+def const_table(name: str):
+    """A uint32 table of csrc/jjs_constants.inc as the text gives it: rows of nine limbs for a table of field elements,
+    else a flat list."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "jubjub_schnorr_amd", "csrc",
+                           "jjs_constants.inc")) as f:
+        text = f.read()
+    m = re.search(r"JJS_CONST uint32_t %s((?:\[[^\]]*\])+) = (.*?);" % name, text, re.S)
+    assert m, name
+    vals = [int(x, 0) for x in re.findall(r"\b(0x[0-9a-fA-F]+|\d+)u?\b", re.sub(r"//[^\n]*", "", m.group(2)))]
+    return [vals[i:i + 9] for i in range(0, len(vals), 9)] if m.group(1).endswith("[9]") and len(vals) > 9 else vals
+
+
 ORDER2 = pt_bytes(o.ORDER2)
 IDENT = pt_bytes(o.IDENTITY)
 

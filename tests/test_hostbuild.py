@@ -6,8 +6,8 @@ import pytest
 import hostlib as hl
 import jjs_oracle as o
 import jjs_oracle_c as oc
-from helpers import (edge_cases, fe_arr, fe_bytes, make_batch, oracle_verify, pt_arr, rand_mod, to_int, torsion_generator,
-                     torsion_grid)
+from helpers import (edge_cases, edge_limb_vectors, fe_arr, fe_bytes, limbs_val, make_batch, oracle_verify, pt_arr, rand_mod,
+                     to_int, torsion_generator, torsion_grid)
 
 
 def special_fq(rng, n):
@@ -328,34 +328,6 @@ def test_multisig_batch(reference_kat):
 
 # ---- the static bounds of fq29.h, exercised at their edges ------------------------------------------------
 RP = 1 << 261
-
-
-def limbs_val(row):
-    return sum(int(x) << (29 * i) for i, x in enumerate(row))
-
-
-def edge_limb_vectors(rng, n, limb_units, value_units):
-    """Limb vectors with every limb < limb_units * 2^29 and value < value_units * q: random, plus vectors
-    pushed against both bounds."""
-    out = []
-    while len(out) < n:
-        kind = len(out) % 4
-        cap = limb_units << 29
-        if kind == 0:
-            l = [int(rng.integers(0, cap)) for _ in range(9)]
-        elif kind == 1:
-            l = [cap - 1] * 9                       # every limb at its maximum
-        elif kind == 2:
-            l = [cap - 1 - int(rng.integers(0, 4)) for _ in range(9)]
-        else:
-            l = [int(rng.integers(0, cap)) for _ in range(8)] + [cap - 1]
-        # clamp the value below value_units * q by lowering the top limb
-        lim = value_units * o.Q - 1
-        low = sum(x << (29 * i) for i, x in enumerate(l[:8]))
-        l[8] = min(l[8], max(0, (lim - low) >> 232))
-        if limbs_val(l) <= lim:
-            out.append(l)
-    return np.array(out, np.uint64).astype(np.uint32)
 
 
 def check_product(res, want_mod):
