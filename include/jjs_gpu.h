@@ -262,6 +262,32 @@ int jjs_verify_all_double_dev(const void* u, const void* R, const void* R_prime,
 int jjs_verify_all_vargen_dev(const void* u, const void* R, const void* PK, const void* Gen, const void* m, size_t n,
                               void* verdict, void* stream);
 
+/* ---- one verdict per batch against a registered key set ---------------------------------------
+ * jjs_keyset_verify_all(_dev)(ks, format, key_idx, s0, s1, s2, m, n, ...): the columns, formats (affine / ext / wire
+ * signatures), alignment, threading and return codes of jjs_keyset_verify(_dev); the verdict contract of jjs_verify_all_*:
+ *   * The verdict is 1 exactly when jjs_keyset_verify would give every item status 0; such a batch is never rejected.
+ *   * It never accepts a malformed encoding, an invalid or identity R, an index >= n_keys, or an item that names a key
+ *     whose key_status is not 0: these are checked per item.
+ *   * It accepts a batch with a failing equation with probability at most 2^-128.  The verdict algorithm collapses the
+ *     key terms of the combined equation per key,
+ *         sum_i z_i (u_i G + c_i PK_k(i) - R_i) = (sum_i z_i u_i) G + sum_k S_k PK_k - sum_i z_i R_i,  S_k = sum_{k(i) = k} z_i c_i mod r,
+ *     multiplies each S_k over the window tables the set holds and runs the bucket method over the R terms alone; the
+ *     collapse is an identity in the group, so the argument above holds unchanged, also for two bad items under one key.
+ *   * n = 0 gives 1.
+ * Routing: the per-item route (jjs_keyset_verify(_dev) and a check of its tally) serves every call for which the verdict
+ * algorithm is not measured faster in profiles/r07_keyset_verify_all.jsonl (the table and the rule), so the
+ * call is never slower than jjs_keyset_verify followed by tally[0] == n.  Signatures in the ext and wire formats always
+ * take the per-item route.  Counters: a call served by the per-item route counts under JJS_KEYSET_SMALL_CALLS /
+ * JJS_KEYSET_LARGE_CALLS exactly as jjs_keyset_verify does; a call served by the verdict algorithm counts under neither
+ * (the per-item run that fetches the statuses after a verdict of 0 counts as the jjs_keyset_verify call it is).
+ *   Host buffers: blocking; status (nullable, n bytes) holds the statuses of jjs_keyset_verify, byte for byte, when the
+ *     verdict is 0, and is all zero when it is 1.
+ *   _dev: writes only the 4-byte aligned device uint32 `verdict`; asynchronous on `stream`. */
+int jjs_keyset_verify_all(jjs_keyset ks, int format, const uint32_t* key_idx, const uint8_t* s0, const uint8_t* s1,
+                          const uint8_t* s2, const uint8_t* m, size_t n, uint8_t* status, int* verdict);
+int jjs_keyset_verify_all_dev(jjs_keyset ks, int format, const void* key_idx, const void* s0, const void* s1, const void* s2,
+                              const void* m, size_t n, void* verdict, void* stream);
+
 /* ---- wire formats (reference `to_bytes` / `from_bytes`), device buffers, asynchronous ------------------
  * Points travel compressed (32 bytes: little-endian v, parity of u in bit 255) and are decoded on the
  * device; an item with any undecodable point (v >= q, no square root, or u = 0 with the sign bit set)

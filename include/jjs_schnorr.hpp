@@ -359,6 +359,15 @@ class KeySet {
         int rc = jjs_keyset_verify(handle_, format, key_idx, s0, s1, s2, m, n, status, tally);
         if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_verify");
     }
+    // one verdict for the batch (jjs_keyset_verify_all): true when every item verifies; `status` (nullable, n bytes) holds
+    // the statuses of verify() when the verdict is false and is all zero otherwise
+    bool verify_all(int format, const uint32_t* key_idx, const uint8_t* s0, const uint8_t* s1, const uint8_t* s2, const uint8_t* m, size_t n,
+                    uint8_t* status = nullptr) const {
+        int verdict = 0;
+        int rc = jjs_keyset_verify_all(handle_, format, key_idx, s0, s1, s2, m, n, status, &verdict);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_verify_all");
+        return verdict == 1;
+    }
     // (key index, signature, message): the signature type of the set's scheme
     template <typename Sig>
     struct Item { uint32_t index; Sig sig; BlsScalar message; };

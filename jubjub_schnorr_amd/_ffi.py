@@ -69,6 +69,8 @@ SIGNATURES = {
     "jjs_keyset_info": [ctypes.c_uint64, _P],
     "jjs_keyset_verify": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_keyset_verify_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P],
+    "jjs_keyset_verify_all": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P],
+    "jjs_keyset_verify_all_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_single": [_P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_double": [_P, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_vargen": [_P, _P, _P, _P, _P, _Z, _P, _P],

@@ -608,6 +608,61 @@ class KeySet:
                    "jjs_keyset_verify")
         return status, tally
 
+    def verify_all_batch(self, items: Sequence[tuple]) -> bool:
+        """items: as for `verify_batch`.  True when every item verifies (one verdict: jjs_keyset_verify_all)."""
+        if not items:
+            return True
+        idx = np.array([i for i, _, _ in items], np.uint32)
+        cols = [_rows([s.u for _, s, _ in items], 32), _rows([s.R for _, s, _ in items], 64)]
+        if self.scheme == "double":
+            cols.append(_rows([s.R_prime for _, s, _ in items], 64))
+        ok, _ = self.verify_all(idx, *cols, _rows([m for _, _, m in items], 32), statuses_on_failure=False)
+        return ok
+
+    def verify_all(self, idx, *cols, fmt: str = "affine", statuses_on_failure: bool = True):
+        """One verdict for the whole batch against the set (jjs_keyset_verify_all): True when every item would get status
+        0 from `verify`.  Same arguments as `verify`.  numpy inputs: blocking, returns (bool, status or None) -- the
+        statuses of `verify`, byte for byte, when the verdict is False and `statuses_on_failure` is set.  torch CUDA
+        tensors: asynchronous on the current stream, returns a device uint32 tensor of one element (1 accepted, 0 not);
+        run `verify` for the statuses."""
+        if self.handle == 0:
+            raise _ffi.JjsError("the key set is closed")
+        widths = [w for w in self._SIG_WIDTHS[(self.scheme, fmt)] if w] + [32]
+        if len(cols) != len(widths):
+            raise ValueError(f"{self.scheme} {fmt} keyset verify_all takes {len(widths)} columns after the indices")
+        fmt_id = Engine._FORMAT_IDS[fmt]
+        slots = [None, None, None, None]          # s0, s1, s2, m
+        positions = [0, 1, 2][:len(widths) - 1] + [3]
+        if _is_torch(idx):
+            import torch
+            n = idx.shape[0]
+            if not (idx.is_cuda and idx.is_contiguous() and idx.dim() == 1 and idx.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+                raise ValueError("expected a contiguous 1-d CUDA tensor of int32 / uint32 indices")
+            for pos, c, w in zip(positions, cols, widths):
+                slots[pos] = self._eng._dev_ptr(c, w, n)
+            verdict = torch.empty(1, dtype=torch.int32, device=idx.device)
+            _ffi.check(self._lib.jjs_keyset_verify_all_dev(self.handle, fmt_id, ctypes.c_void_p(idx.data_ptr()), *slots, n,
+                                                           ctypes.c_void_p(verdict.data_ptr()), self._eng._stream()),
+                       "jjs_keyset_verify_all_dev")
+            return verdict.view(torch.uint32) if hasattr(torch, "uint32") else verdict
+        hidx = np.asarray(idx)
+        if hidx.dtype.kind not in "iu":
+            raise ValueError("key indices must be integers")
+        hidx = np.ascontiguousarray(hidx, dtype=np.uint32)
+        n = hidx.shape[0]
+        host = [self._eng._host(c, w) for c, w in zip(cols, widths)]
+        if any(h.shape[0] != n for h in host):
+            raise ValueError("all columns must have the same number of items as idx")
+        for pos, h in zip(positions, host):
+            slots[pos] = h.ctypes.data_as(ctypes.c_void_p)
+        status = np.empty(n, np.uint8) if statuses_on_failure else None
+        verdict = ctypes.c_int(-1)
+        _ffi.check(self._lib.jjs_keyset_verify_all(self.handle, fmt_id, hidx.ctypes.data_as(ctypes.c_void_p), *slots, n,
+                                                   status.ctypes.data_as(ctypes.c_void_p) if status is not None else None,
+                                                   ctypes.byref(verdict)), "jjs_keyset_verify_all")
+        ok = verdict.value == 1
+        return ok, (None if ok or status is None else status)
+
     def info(self) -> dict:
         out = (ctypes.c_uint64 * len(self.INFO_NAMES))()
         _ffi.check(self._lib.jjs_keyset_info(self.handle, out), "jjs_keyset_info")

@@ -59,6 +59,7 @@
 #include "sign_core.h"
 #include "multisig_core.h"
 #include "batch_verdict.h"
+#include "keyset_verdict.h"
 #include "jjs_sponge_tags_long.inc"
 
 using namespace jjs;
@@ -67,6 +68,7 @@ namespace {
 
 #include "device_kernels.h"
 #include "verdict_kernels.h"
+#include "keyset_verdict_kernels.h"
 #include "engine_state.h"
 #include "verify_job.h"
 
@@ -660,6 +662,7 @@ int jjs_verify_vargen(const uint8_t* u, const uint8_t* R, const uint8_t* PK, con
 
 // ---- one verdict per batch (batch_verdict.h) -------------------------------------------------------------------
 #include "verdict_calls.h"
+#include "keyset_verdict_calls.h"
 
 // ---- wire formats: on-device decoding, then the same verify kernels -----------------------------------
 int jjs_verify_single_wire_dev(const void* sig, const void* pk, const void* m, size_t n, void* status, void* tally, void* stream) {

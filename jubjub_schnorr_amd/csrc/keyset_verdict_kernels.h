@@ -1,0 +1,117 @@
+// Part of jjs_gpu.hip (included inside its anonymous namespace, after verdict_kernels.h): the kernels of the batch verdict
+// against a registered key set (keyset_verdict.h; keyset_verdict_calls.h launches them, around the MSM kernels of
+// verdict_kernels.h for the R terms).
+#pragma once
+
+// the run sums and the key points: the sorted items, the per-item scalar columns, the set's point columns
+struct ksv_key_params {
+    ksv_runs R;
+    uint32_t n_cols;
+    const uint8_t* a[2];              // [n] x 32: the items' scalars of point column 0 / 1
+    uint8_t* head[2];                 // [n_keys] x 32
+    uint8_t* cell[2];                 // [ksv_cells(n)] x 32
+    const uint8_t* key_flags[2];
+    const uint32_t* tables[2];
+    uint32_t* points;                 // one extended point per block of ksv_key_kernel
+};
+
+// The keyed per-item pass: one lane per item (grid-stride), the sums of z u (z' u) per block, a failed check clears the
+// verdict (one atomic per wave, from the ballot).
+__global__ __launch_bounds__(BLOCK, 2) void ksv_item_kernel(ksv_params B) {
+    __shared__ words8 red[2][BLOCK];
+    words8 acc[2] = {words_zero(), words_zero()};
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t base = 0; base < B.V.n; base += total) {
+        const uint64_t item = base + (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+        const bool active = item < B.V.n;
+        bool ok = true;
+        if (active) {
+            words8 zu[2];
+            ok = ksv_item(B, item, zu);
+            acc[0] = fr_add(acc[0], zu[0]);
+            acc[1] = fr_add(acc[1], zu[1]);
+        }
+        if (__ballot(!ok) && (threadIdx.x & 63) == 0) atomicOr(B.fail, 1u);
+    }
+    red[0][threadIdx.x] = acc[0];
+    red[1][threadIdx.x] = acc[1];
+    __syncthreads();
+    for (int step = BLOCK / 2; step > 0; step >>= 1) {
+        if ((int)threadIdx.x < step)
+            for (int e = 0; e < 2; ++e) red[e][threadIdx.x] = fr_add(red[e][threadIdx.x], red[e][threadIdx.x + step]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        store_words(B.partial, 2 * blockIdx.x, red[0][0]);
+        store_words(B.partial, 2 * blockIdx.x + 1, red[1][0]);
+    }
+}
+
+// the pieces of the runs: per point column, one lane per key (its head) and one per line (its cell)
+__global__ __launch_bounds__(BLOCK) void ksv_run_kernel(ksv_key_params S) {
+    const uint32_t cells = ksv_cells(S.R.n), units = S.R.n_keys + cells;
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t id = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; id < (uint64_t)S.n_cols * units; id += total) {
+        const bool second = id >= units;
+        const uint32_t unit = (uint32_t)(second ? id - units : id);
+        const uint8_t* a = second ? S.a[1] : S.a[0];
+        if (unit < S.R.n_keys) store_words(second ? S.head[1] : S.head[0], unit, ksv_head(S.R, a, unit));
+        else store_words(second ? S.cell[1] : S.cell[0], unit - S.R.n_keys, ksv_cell(S.R, a, unit - S.R.n_keys));
+    }
+}
+
+// S_k * P_k: one lane per (point column, key); the points of a block added by a tree, one point per block
+__global__ __launch_bounds__(BLOCK, 2) void ksv_key_kernel(ksv_key_params S) {
+    __shared__ uint32_t red[BLOCK * MSM_EXT_WORDS];
+    const uint64_t id = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    ext_pt acc = ext_identity();
+    if (id < (uint64_t)S.n_cols * S.R.n_keys) {
+        const bool second = id >= S.R.n_keys;
+        key_column C{};
+        C.key_flags = const_cast<uint8_t*>(second ? S.key_flags[1] : S.key_flags[0]);
+        C.tables = const_cast<uint32_t*>(second ? S.tables[1] : S.tables[0]);
+        acc = ksv_key_point(S.R, C, second ? S.head[1] : S.head[0], second ? S.cell[1] : S.cell[0],
+                            (uint32_t)(second ? id - S.R.n_keys : id));
+    }
+    msm_store_ext(red + threadIdx.x * MSM_EXT_WORDS, acc);
+    __syncthreads();
+    for (int step = BLOCK / 2; step > 0; step >>= 1) {
+        if ((int)threadIdx.x < step)
+            msm_store_ext(red + threadIdx.x * MSM_EXT_WORDS,
+                          msm_add_ext(msm_load_ext(red + threadIdx.x * MSM_EXT_WORDS), msm_load_ext(red + (threadIdx.x + step) * MSM_EXT_WORDS)));
+        __syncthreads();
+    }
+    if (threadIdx.x < MSM_EXT_WORDS) S.points[(size_t)blockIdx.x * MSM_EXT_WORDS + threadIdx.x] = red[threadIdx.x];
+}
+
+// one block: the per-block sums of z u added, the blocks' key points added, the windows of the R terms combined, the
+// fixed-base part, the verdict word
+__global__ __launch_bounds__(BLOCK) void ksv_final_kernel(ksv_params B, msm_params M, uint32_t blocks, const uint32_t* points,
+                                                          uint32_t point_blocks, uint32_t* verdict) {
+    __shared__ words8 red[2][BLOCK];
+    __shared__ uint32_t pts[BLOCK * MSM_EXT_WORDS];
+    words8 acc[2] = {words_zero(), words_zero()};
+    for (uint32_t b = threadIdx.x; b < blocks; b += BLOCK) {
+        acc[0] = fr_add(acc[0], load_words(fe_src{B.partial, 32, 0}, 2 * b));
+        acc[1] = fr_add(acc[1], load_words(fe_src{B.partial, 32, 0}, 2 * b + 1));
+    }
+    ext_pt sum = ext_identity();
+    for (uint32_t b = threadIdx.x; b < point_blocks; b += BLOCK) sum = msm_add_ext(sum, msm_load_ext(points + (size_t)b * MSM_EXT_WORDS));
+    red[0][threadIdx.x] = acc[0];
+    red[1][threadIdx.x] = acc[1];
+    msm_store_ext(pts + threadIdx.x * MSM_EXT_WORDS, sum);
+    __syncthreads();
+    for (int step = BLOCK / 2; step > 0; step >>= 1) {
+        if ((int)threadIdx.x < step) {
+            for (int e = 0; e < 2; ++e) red[e][threadIdx.x] = fr_add(red[e][threadIdx.x], red[e][threadIdx.x + step]);
+            msm_store_ext(pts + threadIdx.x * MSM_EXT_WORDS,
+                          msm_add_ext(msm_load_ext(pts + threadIdx.x * MSM_EXT_WORDS), msm_load_ext(pts + (threadIdx.x + step) * MSM_EXT_WORDS)));
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const words8 zu[2] = {red[0][0], red[1][0]};
+        const ext_pt total = msm_add_ext(msm_combine(M.win, M.W, M.c), msm_load_ext(pts));
+        *verdict = bv_verdict(B.V, total, zu, *B.fail != 0u) ? 1u : 0u;
+    }
+}

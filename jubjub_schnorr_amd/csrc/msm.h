@@ -29,17 +29,31 @@ JJS_HD uint32_t msm_buckets(int c) { return 1u << (c - 1); }
 // in 2^s slots by the low bits of the term index, so that the top window's terms spread over all B slots as the other
 // windows' do (a lane per bucket would otherwise take 2^s times the terms of a lane of another window).
 JJS_HD int msm_top_split(int c) { return c * msm_windows(c) - 253; }
-// slot of the non-zero digit d of term t in window j
-JJS_HD uint32_t msm_slot(int j, int32_t d, uint64_t t, int c, int W) {
+// slot of the non-zero digit d of term t in window j, the top window's digits split in 2^s slots each
+JJS_HD uint32_t msm_slot_split(int j, int32_t d, uint64_t t, int W, int s) {
     const uint32_t mag = (uint32_t)(d < 0 ? -d : d) - 1u;
     if (j < W - 1) return mag;
-    const int s = msm_top_split(c);
     return (mag << s) | (uint32_t)(t & ((1u << s) - 1u));
 }
+JJS_HD uint32_t msm_slot(int j, int32_t d, uint64_t t, int c, int W) { return msm_slot_split(j, d, t, W, msm_top_split(c)); }
 // Bits of the batch verdict's weights for window width c: c * ceil(129 / c) - 1 >= 128, so that a weight's top window is
 // as full as the others (a weight of exactly 128 bits would carry 0 or 1 into one more window: half of those terms in
 // ONE bucket).
 JJS_HD int msm_weight_bits(int c) { return c * ((129 + c - 1) / c) - 1; }
+
+// Scalars that are all weights of msm_weight_bits(c) bits (the R terms of keyset_verdict.h) need only the windows the
+// weights reach: ceil(129 / c) of them, the top digit unsigned in [0, 2^(c-1)] like the others' magnitudes (the weight has
+// c * W - 1 bits), so the top window is as full as the rest and takes no split.
+JJS_HD int msm_short_windows(int c) { return (129 + c - 1) / c; }
+// ... their window width for N terms: about eight terms per bucket; every width from 8 to MSM_MAX_WINDOW serves
+JJS_HD int msm_pick_short_window(uint64_t N) {
+    int lg = 0;
+    while (lg < 40 && (1ull << (lg + 1)) <= N) ++lg;
+    const int want = lg - 2;
+    return want > 16 ? 16 : (want < 8 ? 8 : want);
+}
+// ... and their segments per window: 64 slots each
+JJS_HD uint32_t msm_short_segments(int c) { return msm_buckets(c) > 64u ? msm_buckets(c) / 64u : 1u; }
 
 // c bits of s at bit position pos (pos < 256)
 JJS_HD uint32_t msm_bits(const words8& s, int pos, int c) {

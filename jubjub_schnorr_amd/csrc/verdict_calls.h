@@ -70,7 +70,7 @@ static int verdict_launch_msm(int scheme, const void* const* d, size_t n, uint32
     if (g_force_msm_window >= 8 && g_force_msm_window <= MSM_MAX_WINDOW) M.c = g_force_msm_window;
 #endif
     B.z_bits = msm_weight_bits(M.c);
-    M.W = msm_windows(M.c); M.B = msm_buckets(M.c); M.K = msm_segments(M.c); M.L = M.B / M.K;
+    M.W = msm_windows(M.c); M.top_split = msm_top_split(M.c); M.B = msm_buckets(M.c); M.K = msm_segments(M.c); M.L = M.B / M.K;
     const uint32_t blocks = (uint32_t)grid_for(g->grid_prepare, n);
     const size_t nb = (size_t)M.W * M.B;
     const size_t sz[] = {pad256(64 + 4 * ((nb + MSM_SCAN_SPAN - 1) / MSM_SCAN_SPAN + 1)), pad256((size_t)blocks * 64), pad256(M.N * MSM_TERM_WORDS * 4), pad256(M.N * 32), pad256((nb + 1) * 4),

@@ -9,6 +9,7 @@ struct msm_params {
     uint64_t n, N;                    // items, terms (n_kinds * n)
     uint32_t neg_kinds;               // bit k: the terms of kind k are negated points
     int c, W;                         // window width, windows
+    int top_split;                    // the top window's slots per digit, as a power of two (msm_top_split; 0 for short scalars)
     uint32_t B, K, L;                 // buckets per window, segments per window, buckets per segment
     uint32_t* off;                    // W * B + 1: counts, then their exclusive prefix sums
     uint32_t* cursor;                 // W * B: the scatter's positions
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(BLOCK) void msm_sort_kernel(msm_params M) {
         for (int j = 0; j < M.W; ++j) {
             const int32_t d = msm_digit_step(s, j, M.c, M.W, carry);
             if (!d) continue;
-            const uint32_t slot = msm_slot(j, d, t, M.c, M.W);
+            const uint32_t slot = msm_slot_split(j, d, t, M.W, M.top_split);
             if (slot >= M.B) continue;             // (scalars below 2^252 keep every digit in range)
             const uint32_t id = (uint32_t)j * M.B + slot;
             if (!scatter) atomicAdd(&M.off[id], 1u);
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(BLOCK, 2) void msm_segment_kernel(msm_params M) {
     const uint32_t id = blockIdx.x * BLOCK + threadIdx.x;
     if (id >= (uint32_t)M.W * M.K) return;
     const uint32_t j = id / M.K;
-    msm_store_ext(M.segs + (size_t)id * MSM_EXT_WORDS, msm_segment(M.buckets, M.B, j, id % M.K, M.L, j + 1 == (uint32_t)M.W ? msm_top_split(M.c) : 0));
+    msm_store_ext(M.segs + (size_t)id * MSM_EXT_WORDS, msm_segment(M.buckets, M.B, j, id % M.K, M.L, j + 1 == (uint32_t)M.W ? M.top_split : 0));
 }
 // one block per window: its K segments added
 __global__ __launch_bounds__(BLOCK) void msm_window_kernel(msm_params M) {

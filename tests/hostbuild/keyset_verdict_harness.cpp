@@ -1,0 +1,155 @@
+// CPU build of csrc/keyset_verdict.h (the batch verdict against a registered key set, jjs_keyset_verify_all*) for
+// tests/test_keyset_verify_all_host.py: the device's steps run here in loops with the same functions -- the set built as
+// keyset_harness.cpp builds it, the index pass, the keyed item pass (ksv_item), the counting sort by key, the heads and
+// cells of the runs, the key points (ksv_key_point), the bucket method over the R terms with the short weights' windows,
+// bv_verdict.  The comb tables and the double scheme's tag come from host_harness.cpp.
+#include "host_harness.cpp"
+#include "keyset_verdict.h"
+
+namespace {
+
+// sum of N negated terms with short weights by the bucket method: msm_short_windows(c) windows, no split of the top one
+ext_pt short_msm(const uint32_t* terms, const uint8_t* scalars, uint64_t N, int c) {
+    const int W = msm_short_windows(c);
+    const uint32_t B = msm_buckets(c), K = msm_short_segments(c), L = B / K;
+    std::vector<uint32_t> off((size_t)W * B + 1, 0), order;
+    for (int pass = 0; pass < 2; ++pass) {                     // 0: count, 1: scatter
+        std::vector<uint32_t> cursor;
+        if (pass) {
+            uint32_t sum = 0;
+            for (size_t i = 0; i < off.size(); ++i) { const uint32_t v = off[i]; off[i] = sum; sum += v; }
+            order.assign(sum, 0);
+            cursor.assign(off.begin(), off.end());
+        }
+        for (uint64_t t = 0; t < N; ++t) {
+            const words8 s = load_words(fe_src{scalars, 32, 0}, t);
+            uint32_t carry = 0;
+            for (int j = 0; j < W; ++j) {
+                const int32_t d = msm_digit_step(s, j, c, W, carry);
+                if (!d) continue;
+                const uint32_t slot = msm_slot_split(j, d, t, W, 0);
+                if (slot >= B) continue;               // (never: the weights have c W - 1 bits)
+                const uint32_t id = (uint32_t)j * B + slot;
+                if (!pass) ++off[id];
+                else order[cursor[id]++] = (uint32_t)t | ((d < 0) ? 0u : MSM_NEG);
+            }
+        }
+    }
+    std::vector<uint32_t> buckets((size_t)W * B * MSM_EXT_WORDS), win((size_t)W * MSM_EXT_WORDS);
+    for (uint32_t id = 0; id < (uint32_t)W * B; ++id) msm_store_ext(&buckets[(size_t)id * MSM_EXT_WORDS], msm_bucket(off.data(), order.data(), terms, id));
+    for (int j = 0; j < W; ++j) {
+        ext_pt acc = ext_identity();
+        for (uint32_t seg = 0; seg < K; ++seg) acc = msm_add_ext(acc, msm_segment(buckets.data(), B, (uint32_t)j, seg, L, 0));
+        msm_store_ext(&win[(size_t)j * MSM_EXT_WORDS], acc);
+    }
+    return msm_combine(win.data(), W, c);
+}
+
+template <class T>
+T* align16(std::vector<T>& v) { return (T*)(((uintptr_t)v.data() + 15) & ~(uintptr_t)15); }
+
+}  // namespace
+
+extern "C" {
+
+// scheme 0 / 1 / 2; keys0, keys1: n_keys x 64 affine (keys1 NULL for single); affine signature columns; seed: 32 bytes;
+// c: the window width of the bucket method (0: by size); poison: the tables of the keys that are not valid are filled with
+// 0xFF before the call.  Outputs (nullable): total = the affine sum (sum z u) G + sum_k S_k PK_k - sum z_i R_i (64 bytes),
+// key_sums = the S_k of point column 0 then 1 (n_keys x 32 each), key_status, z_bits = the bits of the weights.
+int jjs_ksv_host_verify_all(int scheme, const uint8_t* keys0, const uint8_t* keys1, uint32_t n_keys, const uint32_t* key_idx,
+                            const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* m, size_t n, const uint8_t seed[32],
+                            int c, int poison, int* verdict, uint8_t* total_out, uint8_t* key_sums, uint8_t* key_status, int* z_bits) {
+    if (scheme < 0 || scheme > 2 || n_keys == 0 || n == 0 || !verdict) return -1;
+    ensure_tables();
+    const int w = KEYSET_WINDOW;
+    const uint32_t cols = scheme == 0 ? 1u : 2u;
+    const uint8_t* keys[2] = {keys0, keys1};
+    std::vector<uint32_t> key_item(n_keys), tables[2], bases[2], keyid(n + 1);
+    std::vector<uint8_t> flags[2], gathered[2], bad(n + 1, 0);
+    for (uint32_t k = 0; k < n_keys; ++k) key_item[k] = k;
+    key_column col[2] = {};
+    const size_t key_table_words = (size_t)kt_positions(w) * kt_table_words(w);
+    for (uint32_t ci = 0; ci < cols; ++ci) {
+        key_column& C = col[ci];
+        flags[ci].assign(n_keys, 0);
+        bases[ci].assign((size_t)n_keys * kt_positions(w) * KT_BASE_WORDS + 4, 0);
+        tables[ci].assign((size_t)n_keys * key_table_words + 8, 0);
+        gathered[ci].assign(64 * n + 64, 0);
+        C.src = fe_src{keys[ci], 64, 0};
+        C.key_item = key_item.data(); C.key_flags = flags[ci].data(); C.bases = bases[ci].data();
+        C.tables = align16(tables[ci]);
+        C.keyid = keyid.data();
+        for (uint32_t k = 0; k < n_keys; ++k) {
+            if (kt_chain_key(C, k, w)) {                      // tables for the valid keys only, as on the device
+                for (uint32_t pos = 0; pos < (uint32_t)kt_positions(w); ++pos) kt_table_lane(C, k, pos, w);
+            } else if (poison) {
+                memset(C.tables + (size_t)k * key_table_words, 0xFF, key_table_words * 4);
+            }
+        }
+    }
+    if (key_status)
+        for (uint32_t k = 0; k < n_keys; ++k) key_status[k] = (uint8_t)ks_key_status(flags[0][k], cols > 1 ? flags[1][k] : (uint32_t)KT_KEY_VALID);
+    uint8_t* g0 = align16(gathered[0]);
+    uint8_t* g1 = cols > 1 ? align16(gathered[1]) : nullptr;
+    for (uint64_t i = 0; i < n; ++i) ks_index_item(key_idx, n_keys, i, keyid.data(), bad.data(), cols, keys0, keys1, g0, g1);
+    const out_ptrs o{nullptr, nullptr, nullptr, nullptr};
+    ksv_params B{};
+    B.V = scheme == 0 ? params_single(u, R, g0, m, n, g_comb_g.data(), o)
+        : scheme == 1 ? params_double(u, R, Rp, g0, g1, m, n, (const uint8_t*)g_tag, g_comb_g.data(), g_comb_gn.data(), o)
+                      : params_vargen(u, R, g0, g1, m, n, o);
+    uint32_t window = (uint32_t)w;
+    B.V.key_flag = &window;
+    B.V.pre_malformed = bad.data();
+    memcpy(B.seed, seed, 32);
+    B.n_cols = cols; B.keyid = keyid.data();
+    B.key_flags[0] = flags[0].data(); B.key_flags[1] = cols > 1 ? flags[1].data() : nullptr;
+    const size_t N = (size_t)B.V.n_eq * n;
+    if (c == 0) c = msm_pick_short_window(N);
+    if (c < 8 || c > MSM_MAX_WINDOW) return -1;
+    B.z_bits = msm_weight_bits(c);
+    if (z_bits) *z_bits = B.z_bits;
+    std::vector<uint32_t> terms(N * MSM_TERM_WORDS + 4);
+    std::vector<uint8_t> scalars(N * 32 + 16), a[2], head[2], cell[2];
+    B.terms = align16(terms); B.scalars = align16(scalars);
+    const uint32_t cells = ksv_cells(n);
+    for (uint32_t ci = 0; ci < 2; ++ci) {
+        a[ci].assign(n * 32 + 16, 0); head[ci].assign((size_t)n_keys * 32 + 16, 0); cell[ci].assign((size_t)cells * 32 + 16, 0);
+        B.a[ci] = align16(a[ci]);
+    }
+    bool failed = false;
+    words8 sum[2] = {words_zero(), words_zero()};
+    for (uint64_t i = 0; i < n; ++i) {
+        words8 zu[2];
+        failed = !ksv_item(B, i, zu) || failed;
+        sum[0] = fr_add(sum[0], zu[0]);
+        sum[1] = fr_add(sum[1], zu[1]);
+    }
+    // the counting sort by key: counts, exclusive scan, scatter (the cursors end at the ends of the runs)
+    std::vector<uint32_t> cursor(n_keys, 0), order(n);
+    for (uint64_t i = 0; i < n; ++i) ++cursor[keyid[i]];
+    uint32_t run = 0;
+    for (uint32_t k = 0; k < n_keys; ++k) { const uint32_t cnt = cursor[k]; cursor[k] = run; run += cnt; }
+    for (uint64_t i = 0; i < n; ++i) order[cursor[keyid[i]]++] = (uint32_t)i;
+    const ksv_runs Rn{cursor.data(), 1u, order.data(), keyid.data(), n_keys, n};
+    ext_pt total = short_msm(B.terms, B.scalars, N, c);
+    for (uint32_t ci = 0; ci < cols; ++ci) {
+        uint8_t *h = align16(head[ci]), *cl = align16(cell[ci]);
+        for (uint32_t k = 0; k < n_keys; ++k) store_words(h, k, ksv_head(Rn, B.a[ci], k));
+        for (uint32_t g = 0; g < cells; ++g) store_words(cl, g, ksv_cell(Rn, B.a[ci], g));
+        for (uint32_t k = 0; k < n_keys; ++k) {
+            total = msm_add_ext(total, ksv_key_point(Rn, col[ci], h, cl, k));
+            if (key_sums) store_words(key_sums, (uint64_t)ci * n_keys + k, ksv_key_sum(Rn, h, cl, k));
+        }
+    }
+    *verdict = bv_verdict(B.V, total, sum, failed) ? 1 : 0;
+    if (total_out) {
+        for (uint32_t e = 0; e < B.V.n_eq; ++e)
+            if (B.V.eq[e].comb) total = add_comb_range(total, B.V.eq[e].comb, sum[e], 0, COMB_WINDOWS, true);
+        const fe_n zi = fq_inverse(total.z);
+        store_words(total_out, 0, fq_to_words(fq_mul(total.x, zi)));
+        store_words(total_out, 1, fq_to_words(fq_mul(total.y, zi)));
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,56 @@
+"""ctypes loader for tests/hostbuild/libjjs_keyset_verdict_hosttest.so: csrc/keyset_verdict.h and the product headers
+compiled for the CPU (the recipe of hostlib.py)."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+SRC = os.path.join(HERE, "hostbuild", "keyset_verdict_harness.cpp")
+LIB = os.path.join(HERE, "hostbuild", "libjjs_keyset_verdict_hosttest.so")
+CSRC = os.path.join(ROOT, "jubjub_schnorr_amd", "csrc")
+SCHEMES = {"single": 0, "double": 1, "vargen": 2}
+_lib = None
+
+
+def _stale():
+    if not os.path.exists(LIB):
+        return True
+    t = os.path.getmtime(LIB)
+    deps = [SRC, os.path.join(HERE, "hostbuild", "host_harness.cpp")] + \
+        [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def load():
+    global _lib
+    if _lib is not None:
+        return _lib
+    if _stale():
+        san = ["-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=undefined"] if os.environ.get("JJS_HOST_SANITIZE") else ["-O2"]
+        subprocess.check_call(["g++", *san, "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas",
+                               "-I" + CSRC, "-o", LIB, SRC])
+    _lib = ctypes.CDLL(LIB)
+    return _lib
+
+
+def _p(a):
+    return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+
+
+def verify_all(scheme, keys, idx, b, seed=bytes(32), c=0, poison=False):
+    """keys: list of (n_keys, 64) affine columns; b: a batch dict (its key columns are not read).  Returns a dict: verdict,
+    total (the affine combined sum, 64 bytes), key_sums (point columns x n_keys x 32), key_status, z_bits."""
+    keys = [np.ascontiguousarray(k, dtype=np.uint8) for k in keys]
+    idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    cols = [np.ascontiguousarray(b[k], dtype=np.uint8) if b.get(k) is not None else None for k in ("u", "R", "Rp", "m")]
+    n, nk = len(idx), len(keys[0])
+    verdict, z_bits = ctypes.c_int(-1), ctypes.c_int(0)
+    total, sums, key_status = np.zeros(64, np.uint8), np.zeros((len(keys), nk, 32), np.uint8), np.empty(nk, np.uint8)
+    rc = load().jjs_ksv_host_verify_all(SCHEMES[scheme], _p(keys[0]), _p(keys[1]) if len(keys) > 1 else None, ctypes.c_uint32(nk),
+                                        _p(idx), *[_p(x) for x in cols], ctypes.c_size_t(n), seed, c, int(poison),
+                                        ctypes.byref(verdict), _p(total), _p(sums), _p(key_status), ctypes.byref(z_bits))
+    assert rc == 0
+    return {"verdict": verdict.value, "total": total, "key_sums": sums, "key_status": key_status, "z_bits": z_bits.value}
