@@ -321,6 +321,13 @@ std::vector<std::unique_ptr<keyset_entry>> g_keysets;   // the registry (under L
 uint32_t g_keyset_generation = 0;                       // never reset: a handle from before jjs_shutdown stays stale
 uint32_t g_keyset_host_calls = 0;                       // host-buffer keyset calls between their first and last use of L.mu:
                                                         // jjs_shutdown waits for them before it frees a device (under L.mu)
+struct keyset_host_call_leave {                         // ... the way out of such a call, on every path
+    ~keyset_host_call_leave() {
+        std::lock_guard<std::mutex> lock(L.mu);
+        --g_keyset_host_calls;
+        L.lane_cv.notify_all();
+    }
+};
 // Device bound to the work in progress on THIS host thread: set by check_ready for an entry point and by each
 // per-device worker of run_host for its own block (the workers run concurrently, one device each).
 thread_local device_state* g = nullptr;

@@ -110,38 +110,31 @@ static int keyset_build_copy(keyset_entry& k, keyset_copy& c, int format, const 
     return rc;
 }
 
-// The launches of one call against a set's copy `c` on stream s (g is c's device).  d = key_idx, s0, s1, s2, m (device).
-static int keyset_launch(keyset_entry& k, const keyset_copy& c, int format, const void* const* d, size_t n, void* status, void* tally,
-                         hipStream_t s) {
-    const int scheme = k.scheme;
-    const bool small = n <= KEYSET_SMALL_MAX_ITEMS;
+// the scheme's verification descriptor over affine columns (Rp, PK2: the columns the scheme has)
+static verify_params scheme_params(int scheme, const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* PK, const uint8_t* PK2,
+                                   const uint8_t* m, size_t n, const out_ptrs& o) {
+    if (scheme == JJS_SCHEME_SINGLE) return params_single(u, R, PK, m, n, g->comb_g, o);
+    if (scheme == JJS_SCHEME_DOUBLE) return params_double(u, R, Rp, PK, PK2, m, n, g->tag, g->comb_g, g->comb_gn, o);
+    return params_vargen(u, R, PK, PK2, m, n, o);
+}
+
+// The front of a call against a set's copy `c` on stream s (g is c's device), shared by keyset_launch and
+// keyset_verdict_launch_msm: the call's slot, the items' key indices, the sort's order and cursors carved from sl->keys, the
+// key descriptor over the set's keys in order, the index pass that gathers the keys per item into wire_pts(2) (3), and the
+// verification descriptor over those columns.  Without `sort` the cursors are neither cleared nor used.
+struct keyset_front {
+    key_params K;
+    keyset_index_params X;
+    size_t cursor_words;
+};
+static int keyset_front_end(const keyset_entry& k, const keyset_copy& c, const void* key_idx, size_t n, bool sort, hipStream_t s, keyset_front& F) {
     pick_slot(n, s);
     if (int rc = ensure_wire(n)) return rc;
-    if (int rc = ensure_prep(n)) return rc;
-    if (int rc = ensure_pending(n)) return rc;
-    if (small)
-        if (int rc = ensure_small(2 * n + 64)) return rc;      // the subgroup tests of the R points (keyset_hash_kernel)
-    const size_t cursor_words = (size_t)k.n_keys + 1 > (size_t)CURSOR_DENSE_FROM * CURSOR_STRIDE ? (size_t)k.n_keys + 1
-                                                                                                  : (size_t)CURSOR_DENSE_FROM * CURSOR_STRIDE;
-    if (int rc = ensure_key_index(2 * pad256(n * 4) + pad256(cursor_words * 4))) return rc;
-    // the verification descriptor: R (R') as the format gives them, the keys gathered per item into wire_pts(2) (3)
-    const uint8_t* u = (const uint8_t*)d[1];
-    const uint8_t *R = (const uint8_t*)d[2], *Rp = (const uint8_t*)d[3];
-    const uint32_t n_r = scheme == JJS_SCHEME_DOUBLE ? 2u : 1u;
-    if (format != JJS_FORMAT_AFFINE) { R = wire_pts(0); Rp = wire_pts(1); }
-    out_ptrs o{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace};
-    verify_params P{};
-    if (scheme == JJS_SCHEME_SINGLE) P = params_single(u, R, wire_pts(2), (const uint8_t*)d[4], n, g->comb_g, o);
-    else if (scheme == JJS_SCHEME_DOUBLE) P = params_double(u, R, Rp, wire_pts(2), wire_pts(3), (const uint8_t*)d[4], n, g->tag, g->comb_g, g->comb_gn, o);
-    else P = params_vargen(u, R, wire_pts(2), wire_pts(3), (const uint8_t*)d[4], n, o);
-    const uint32_t sig_stride = scheme == JJS_SCHEME_DOUBLE ? 96u : 64u;
-    if (format == JJS_FORMAT_WIRE) { P.u = fe_src{(const uint8_t*)d[1], sig_stride, 0}; P.decoded_points = 1; }
-    P.pre_malformed = wire_bad();
-    P.key_flag = c.words + 2;
-    P.prep = sl->prep;
-    P.pending_count = reinterpret_cast<unsigned long long*>(sl->pending);
-    P.pending = sl->pending + 2;
-    key_params K{};
+    F.cursor_words = (size_t)k.n_keys + 1 > (size_t)CURSOR_DENSE_FROM * CURSOR_STRIDE ? (size_t)k.n_keys + 1
+                                                                                      : (size_t)CURSOR_DENSE_FROM * CURSOR_STRIDE;
+    if (int rc = ensure_key_index(2 * pad256(n * 4) + pad256(F.cursor_words * 4))) return rc;
+    key_params& K = F.K;
+    K = key_params{};
     K.n_cols = k.n_cols; K.max_keys = k.n_keys; K.max_keys_wide = k.n_keys; K.n = n; K.counters = c.words;
     uint8_t* q = sl->keys;
     uint32_t* keyid = reinterpret_cast<uint32_t*>(q); q += pad256(n * 4);
@@ -151,6 +144,55 @@ static int keyset_launch(keyset_entry& k, const keyset_copy& c, int format, cons
         K.col[i].src = fe_src{c.keys[i], 64, 0};
         K.col[i].keyid = keyid; K.col[i].key_flags = c.flags[i]; K.col[i].tables = c.tables[i];
     }
+    keyset_index_params& X = F.X;
+    X = keyset_index_params{};
+    X.key_idx = (const uint32_t*)key_idx; X.n_keys = k.n_keys; X.n_cols = k.n_cols;
+    X.keys[0] = c.keys[0]; X.keys[1] = c.keys[1]; X.out[0] = wire_pts(2); X.out[1] = wire_pts(3);
+    X.keyid = keyid; X.bad = wire_bad(); X.n = n;
+    X.cursor = sort ? K.key_cursor : nullptr; X.cursor_words = sort ? F.cursor_words : 0;
+    return JJS_OK;
+}
+static verify_params keyset_params(int scheme, const keyset_copy& c, const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* m,
+                                   size_t n, const out_ptrs& o) {
+    verify_params P = scheme_params(scheme, u, R, Rp, wire_pts(2), wire_pts(3), m, n, o);
+    P.pre_malformed = wire_bad();
+    P.key_flag = c.words + 2;
+    return P;
+}
+// the index pass, and with `sort` the counting sort of the items by key
+static void keyset_front_launch(const keyset_front& F, bool sort, hipStream_t s) {
+    const size_t n = F.K.n;
+    hipLaunchKernelGGL(keyset_index_kernel, dim3((unsigned)grid_for(8192, n > F.cursor_words ? n : F.cursor_words)), dim3(BLOCK), 0, s, F.X);
+    if (!sort) return;
+    const unsigned item_blocks = (unsigned)grid_for(8192, n);
+    hipLaunchKernelGGL(key_count_kernel, dim3(item_blocks), dim3(BLOCK), 0, s, F.K);
+    hipLaunchKernelGGL(key_scan_kernel, dim3(1), dim3(1024), 0, s, F.K);
+    hipLaunchKernelGGL(key_scatter_kernel, dim3(item_blocks), dim3(BLOCK), 0, s, F.K);
+}
+
+// The launches of one call against a set's copy `c` on stream s (g is c's device).  d = key_idx, s0, s1, s2, m (device).
+static int keyset_launch(keyset_entry& k, const keyset_copy& c, int format, const void* const* d, size_t n, void* status, void* tally,
+                         hipStream_t s) {
+    const int scheme = k.scheme;
+    const bool small = n <= KEYSET_SMALL_MAX_ITEMS;
+    keyset_front F;
+    if (int rc = keyset_front_end(k, c, d[0], n, !small, s, F)) return rc;
+    const key_params& K = F.K;
+    if (int rc = ensure_prep(n)) return rc;
+    if (int rc = ensure_pending(n)) return rc;
+    if (small)
+        if (int rc = ensure_small(2 * n + 64)) return rc;      // the subgroup tests of the R points (keyset_hash_kernel)
+    // the verification descriptor: R (R') as the format gives them, the keys gathered per item into wire_pts(2) (3)
+    const uint8_t *R = (const uint8_t*)d[2], *Rp = (const uint8_t*)d[3];
+    const uint32_t n_r = scheme == JJS_SCHEME_DOUBLE ? 2u : 1u;
+    if (format != JJS_FORMAT_AFFINE) { R = wire_pts(0); Rp = wire_pts(1); }
+    verify_params P = keyset_params(scheme, c, (const uint8_t*)d[1], R, Rp, (const uint8_t*)d[4], n,
+                                    out_ptrs{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace});
+    const uint32_t sig_stride = scheme == JJS_SCHEME_DOUBLE ? 96u : 64u;
+    if (format == JJS_FORMAT_WIRE) { P.u = fe_src{(const uint8_t*)d[1], sig_stride, 0}; P.decoded_points = 1; }
+    P.prep = sl->prep;
+    P.pending_count = reinterpret_cast<unsigned long long*>(sl->pending);
+    P.pending = sl->pending + 2;
 
     if (int rc = begin_shared(s)) return rc;
     clear_params Z{};
@@ -178,12 +220,7 @@ static int keyset_launch(keyset_entry& k, const keyset_copy& c, int format, cons
             hipLaunchKernelGGL(decode_kernel, dim3((unsigned)grid_for(8192, n)), dim3(BLOCK), 0, s, D);
         }
     }
-    keyset_index_params X{};
-    X.key_idx = (const uint32_t*)d[0]; X.n_keys = k.n_keys; X.n_cols = k.n_cols;
-    X.keys[0] = c.keys[0]; X.keys[1] = c.keys[1]; X.out[0] = wire_pts(2); X.out[1] = wire_pts(3);
-    X.keyid = keyid; X.bad = wire_bad(); X.n = n;
-    X.cursor = small ? nullptr : K.key_cursor; X.cursor_words = small ? 0 : cursor_words;
-    hipLaunchKernelGGL(keyset_index_kernel, dim3((unsigned)grid_for(8192, n > cursor_words ? n : cursor_words)), dim3(BLOCK), 0, s, X);
+    keyset_front_launch(F, !small, s);
     if (small) {
         ++k.small_calls;
         const uint32_t hash_blocks = (uint32_t)((n * SB_HASH_LANES + BLOCK - 1) / BLOCK);
@@ -196,10 +233,6 @@ static int keyset_launch(keyset_entry& k, const keyset_copy& c, int format, cons
         return end_shared(s);                  // nothing is left to the resolve pass
     } else {
         ++k.large_calls;
-        const unsigned item_blocks = (unsigned)grid_for(8192, n);
-        hipLaunchKernelGGL(key_count_kernel, dim3(item_blocks), dim3(BLOCK), 0, s, K);
-        hipLaunchKernelGGL(key_scan_kernel, dim3(1), dim3(1024), 0, s, K);
-        hipLaunchKernelGGL(key_scatter_kernel, dim3(item_blocks), dim3(BLOCK), 0, s, K);
         hipLaunchKernelGGL(prepare_kernel, dim3(grid_for(g->grid_prepare, n)), dim3(BLOCK), 0, s, P, (int)PREP_ALL, (uint64_t)0, (uint64_t)n);
         hipLaunchKernelGGL(key_verify_kernel, dim3(grid_for(g->grid_key_verify, n)), dim3(BLOCK), 0, s, P, K);
     }
@@ -229,6 +262,55 @@ static int keyset_check_cols(int scheme, int format, const void* key_idx, const 
     return JJS_OK;
 }
 
+// ---- blocking host calls on a device's key-set stream ------------------------------------------------------------------------
+// Such a call (jjs_keyset_create, jjs_keyset_verify, the verdict algorithm of jjs_verify_all_* and jjs_keyset_verify_all)
+// counts itself among g_keyset_host_calls in its first section under L.mu, so that jjs_shutdown does not free its device
+// before it has left, and leaves through keyset_host_call_leave (engine_state.h) on every way out.
+extern "C++" {        // (templates below)
+// The call's columns and outputs in dev's staging area (under dev->host_mu): column i of widths[i] bytes per item (0: not
+// used) copied from src[i] on the key-set stream s, then output areas of out_bytes[j] bytes, each part padded to 256 bytes.
+struct keyset_stage {
+    const void* d[6];
+    uint8_t* out[2];
+    hipStream_t s;
+};
+static int keyset_stage_in(device_state* dev, const size_t* widths, const void* const* src, size_t cols, size_t n, const size_t* out_bytes,
+                           size_t outs, keyset_stage& S) {
+    size_t off[8], total = 0;
+    for (size_t i = 0; i < cols; ++i) { off[i] = total; total += pad256(widths[i] * n); }
+    for (size_t j = 0; j < outs; ++j) { off[cols + j] = total; total += pad256(out_bytes[j]); }
+    if (total > dev->ks_stage_bytes) {
+        const size_t cap = grown(total);
+        if (int rc = regrow(dev->ks_stage, dev->ks_stage_bytes, dev->ks_stage_bytes, cap, cap)) return rc;
+    }
+    HIP_TRY(hipSetDevice(dev->device));
+    S.s = dev->ks_stream;
+    for (size_t i = 0; i < cols; ++i) {
+        if (!widths[i]) continue;
+        S.d[i] = dev->ks_stage + off[i];
+        HIP_TRY(hipMemcpyAsync(dev->ks_stage + off[i], src[i], widths[i] * n, hipMemcpyHostToDevice, S.s));
+    }
+    for (size_t j = 0; j < outs; ++j) S.out[j] = dev->ks_stage + off[cols + j];
+    return JJS_OK;
+}
+// The call's second section under L.mu (it holds dev->host_mu and has set g = dev): the engine still drives the same
+// devices and, for a call against a set (ks non-null), the set and its copy on dev are still there; then launch(k, c).
+template <class Launch>
+static int keyset_launch_locked(device_state* dev, const jjs_keyset* ks, Launch launch) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
+    keyset_entry* k = nullptr;
+    const keyset_copy* c = nullptr;
+    if (ks) {
+        k = find_keyset(*ks);
+        if (!k) return fail(JJS_ERR_ARG, "the key set was destroyed during the call");
+        c = keyset_copy_for(*k, dev);
+        if (!c) return fail(JJS_ERR_ARG, "the key set has no copy on this device");
+    }
+    return launch(k, c);
+}
+}  // extern "C++"
+
 extern "C" {
 
 // The set is built outside the engine's mutex, on a stream of its own per device (other threads' calls go on meanwhile), and
@@ -246,13 +328,7 @@ int jjs_keyset_create(int scheme, int format, const uint8_t* keys, const uint8_t
         devs = L.devs;
         ++g_keyset_host_calls;
     }
-    struct leave {
-        ~leave() {
-            std::lock_guard<std::mutex> lock(L.mu);
-            --g_keyset_host_calls;
-            L.lane_cv.notify_all();
-        }
-    } leave_on_every_way_out;
+    keyset_host_call_leave leave_on_every_way_out;
     const uint32_t cols = keyset_cols(scheme);
     std::unique_ptr<keyset_entry> k(new keyset_entry());
     k->scheme = scheme; k->n_keys = (uint32_t)n_keys; k->n_cols = cols;
@@ -370,49 +446,24 @@ int jjs_keyset_verify(jjs_keyset ks, int format, const uint32_t* key_idx, const 
         dev = g;
         ++g_keyset_host_calls;           // jjs_shutdown does not free `dev` before this call has left (see below)
     }
-    struct leave {
-        ~leave() {
-            std::lock_guard<std::mutex> lock(L.mu);
-            --g_keyset_host_calls;
-            L.lane_cv.notify_all();
-        }
-    } leave_on_every_way_out;
+    keyset_host_call_leave leave_on_every_way_out;
     std::lock_guard<std::mutex> big(dev->host_mu);
     g = dev;
     return no_throw([&]() -> int {
         size_t w[3];
         keyset_sig_widths(scheme, format, w);
-        const size_t widths[5] = {4, w[0], w[1], w[2], 32};
+        const size_t widths[5] = {4, w[0], w[1], w[2], 32}, out_bytes[2] = {n, 256};      // outputs: statuses, tally
         const void* src[5] = {key_idx, s0, s1, s2, m};
-        size_t off[7], total = 0;
-        for (int i = 0; i < 5; ++i) { off[i] = total; total += pad256(widths[i] * n); }
-        off[5] = total; total += pad256(n);                       // statuses
-        off[6] = total; total += 256;                             // tally
-        if (total > dev->ks_stage_bytes) {
-            const size_t cap = grown(total);
-            if (int rc = regrow(dev->ks_stage, dev->ks_stage_bytes, dev->ks_stage_bytes, cap, cap)) return rc;
-        }
-        HIP_TRY(hipSetDevice(dev->device));
-        hipStream_t s = dev->ks_stream;
-        const void* d[5] = {};
-        for (int i = 0; i < 5; ++i) {
-            if (!widths[i]) continue;
-            d[i] = dev->ks_stage + off[i];
-            HIP_TRY(hipMemcpyAsync(dev->ks_stage + off[i], src[i], widths[i] * n, hipMemcpyHostToDevice, s));
-        }
-        {
-            std::lock_guard<std::mutex> lock(L.mu);
-            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
-            keyset_entry* k = find_keyset(ks);
-            if (!k) return fail(JJS_ERR_ARG, "the key set was destroyed during the call");
-            const keyset_copy* c = keyset_copy_for(*k, dev);
-            if (!c) return fail(JJS_ERR_ARG, "the key set has no copy on this device");
-            if (int rc = keyset_launch(*k, *c, format, d, n, dev->ks_stage + off[5], dev->ks_stage + off[6], s)) return rc;
-        }
-        if (status) HIP_TRY(hipMemcpyAsync(status, dev->ks_stage + off[5], n, hipMemcpyDeviceToHost, s));
+        keyset_stage S{};
+        if (int rc = keyset_stage_in(dev, widths, src, 5, n, out_bytes, 2, S)) return rc;
+        if (int rc = keyset_launch_locked(dev, &ks, [&](keyset_entry* k, const keyset_copy* c) {
+                return keyset_launch(*k, *c, format, S.d, n, S.out[0], S.out[1], S.s);
+            }))
+            return rc;
+        if (status) HIP_TRY(hipMemcpyAsync(status, S.out[0], n, hipMemcpyDeviceToHost, S.s));
         unsigned long long t[4] = {};
-        HIP_TRY(hipMemcpyAsync(t, dev->ks_stage + off[6], sizeof(t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpyAsync(t, S.out[1], sizeof(t), hipMemcpyDeviceToHost, S.s));
+        HIP_TRY(hipStreamSynchronize(S.s));
         if (tally) for (int i = 0; i < 4; ++i) tally[i] = t[i];
         return JJS_OK;
     });

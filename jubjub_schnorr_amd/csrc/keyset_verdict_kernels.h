@@ -15,36 +15,9 @@ struct ksv_key_params {
     uint32_t* points;                 // one extended point per block of ksv_key_kernel
 };
 
-// The keyed per-item pass: one lane per item (grid-stride), the sums of z u (z' u) per block, a failed check clears the
-// verdict (one atomic per wave, from the ballot).
+// the keyed per-item pass
 __global__ __launch_bounds__(BLOCK, 2) void ksv_item_kernel(ksv_params B) {
-    __shared__ words8 red[2][BLOCK];
-    words8 acc[2] = {words_zero(), words_zero()};
-    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
-    for (uint64_t base = 0; base < B.V.n; base += total) {
-        const uint64_t item = base + (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-        const bool active = item < B.V.n;
-        bool ok = true;
-        if (active) {
-            words8 zu[2];
-            ok = ksv_item(B, item, zu);
-            acc[0] = fr_add(acc[0], zu[0]);
-            acc[1] = fr_add(acc[1], zu[1]);
-        }
-        if (__ballot(!ok) && (threadIdx.x & 63) == 0) atomicOr(B.fail, 1u);
-    }
-    red[0][threadIdx.x] = acc[0];
-    red[1][threadIdx.x] = acc[1];
-    __syncthreads();
-    for (int step = BLOCK / 2; step > 0; step >>= 1) {
-        if ((int)threadIdx.x < step)
-            for (int e = 0; e < 2; ++e) red[e][threadIdx.x] = fr_add(red[e][threadIdx.x], red[e][threadIdx.x + step]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        store_words(B.partial, 2 * blockIdx.x, red[0][0]);
-        store_words(B.partial, 2 * blockIdx.x + 1, red[1][0]);
-    }
+    verdict_item_pass(B, [](const ksv_params& b, uint64_t item, words8* zu) { return ksv_item(b, item, zu); });
 }
 
 // the pieces of the runs: per point column, one lane per key (its head) and one per line (its cell)
@@ -73,14 +46,7 @@ __global__ __launch_bounds__(BLOCK, 2) void ksv_key_kernel(ksv_key_params S) {
         acc = ksv_key_point(S.R, C, second ? S.head[1] : S.head[0], second ? S.cell[1] : S.cell[0],
                             (uint32_t)(second ? id - S.R.n_keys : id));
     }
-    msm_store_ext(red + threadIdx.x * MSM_EXT_WORDS, acc);
-    __syncthreads();
-    for (int step = BLOCK / 2; step > 0; step >>= 1) {
-        if ((int)threadIdx.x < step)
-            msm_store_ext(red + threadIdx.x * MSM_EXT_WORDS,
-                          msm_add_ext(msm_load_ext(red + threadIdx.x * MSM_EXT_WORDS), msm_load_ext(red + (threadIdx.x + step) * MSM_EXT_WORDS)));
-        __syncthreads();
-    }
+    block_sum_ext(red, acc);
     if (threadIdx.x < MSM_EXT_WORDS) S.points[(size_t)blockIdx.x * MSM_EXT_WORDS + threadIdx.x] = red[threadIdx.x];
 }
 

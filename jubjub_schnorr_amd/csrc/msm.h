@@ -174,4 +174,14 @@ JJS_HD uint32_t msm_segments(int c) {
     return B > L ? B / L : 1u;
 }
 
+// The shape of an MSM with c-bit windows: W windows (the top one's digits split in 2^top_split slots each) of B buckets, cut
+// into K segments of L.  msm_shape_full: scalars below 2^252; msm_shape_short: scalars that are all weights of
+// msm_weight_bits(c) bits.
+struct msm_shape {
+    int c, W, top_split;
+    uint32_t B, K, L;
+};
+JJS_HD msm_shape msm_shape_full(int c) { return {c, msm_windows(c), msm_top_split(c), msm_buckets(c), msm_segments(c), msm_buckets(c) / msm_segments(c)}; }
+JJS_HD msm_shape msm_shape_short(int c) { return {c, msm_short_windows(c), 0, msm_buckets(c), msm_short_segments(c), msm_buckets(c) / msm_short_segments(c)}; }
+
 }  // namespace jjs

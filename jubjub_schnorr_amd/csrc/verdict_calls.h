@@ -47,13 +47,65 @@ static int ensure_verdict(size_t bytes) {
     return regrow(sl->verdict, sl->verdict_bytes, sl->verdict_bytes, cap, cap);
 }
 static verify_params verdict_params(int scheme, const void* const* d, size_t n) {
+    const uint8_t* const* p = reinterpret_cast<const uint8_t* const*>(d);
     const out_ptrs o{nullptr, nullptr, nullptr, nullptr};
-    if (scheme == JJS_SCHEME_SINGLE)
-        return params_single((const uint8_t*)d[0], (const uint8_t*)d[1], (const uint8_t*)d[2], (const uint8_t*)d[3], n, g->comb_g, o);
-    if (scheme == JJS_SCHEME_DOUBLE)
-        return params_double((const uint8_t*)d[0], (const uint8_t*)d[1], (const uint8_t*)d[2], (const uint8_t*)d[3], (const uint8_t*)d[4],
-                             (const uint8_t*)d[5], n, g->tag, g->comb_g, g->comb_gn, o);
-    return params_vargen((const uint8_t*)d[0], (const uint8_t*)d[1], (const uint8_t*)d[2], (const uint8_t*)d[3], (const uint8_t*)d[4], n, o);
+    if (scheme == JJS_SCHEME_SINGLE) return scheme_params(scheme, p[0], p[1], nullptr, p[2], nullptr, p[3], n, o);
+    if (scheme == JJS_SCHEME_DOUBLE) return scheme_params(scheme, p[0], p[1], p[2], p[3], p[4], p[5], n, o);
+    return scheme_params(scheme, p[0], p[1], nullptr, p[2], p[3], p[4], n, o);
+}
+
+// ---- the MSM of a verdict call (msm.h; its kernels: verdict_kernels.h) --------------------------------------------------------
+// the window width: by size, or jjs_debug_force_path's
+static int msm_window(int by_size) {
+#if defined(JJS_PROFILING)
+    if (g_force_msm_window >= 8 && g_force_msm_window <= MSM_MAX_WINDOW) return g_force_msm_window;
+#endif
+    return by_size;
+}
+extern "C++" {
+// The slot's verdict scratch of a call whose item pass runs `blocks` blocks (B: bv_params or ksv_params; M: its n, N and
+// shape set), sized and carved: the fail word with the scan's span sums behind it (<= 4096 + 1 words), the item pass's
+// partial sums, the terms, the scalars, M.off .. M.win, then the caller's n_extra parts of extra[i] bytes (-> q_extra[i]),
+// each part padded to 256 bytes.
+constexpr int MSM_PARTS = 10;
+template <class P>
+static int verdict_scratch(P& B, msm_params& M, uint32_t blocks, const size_t* extra, int n_extra, uint8_t** q_extra, uint32_t*& span_sum) {
+    const size_t nb = (size_t)M.W * M.B;
+    const size_t sz[MSM_PARTS] = {64 + 4 * ((nb + MSM_SCAN_SPAN - 1) / MSM_SCAN_SPAN + 1), (size_t)blocks * 64, M.N * MSM_TERM_WORDS * 4, M.N * 32,
+                                  (nb + 1) * 4, nb * 4, M.N * M.W * 4, nb * MSM_EXT_WORDS * 4, (size_t)M.W * M.K * MSM_EXT_WORDS * 4,
+                                  (size_t)M.W * MSM_EXT_WORDS * 4};
+    size_t total = 0;
+    for (size_t x : sz) total += pad256(x);
+    for (int i = 0; i < n_extra; ++i) total += pad256(extra[i]);
+    if (int rc = ensure_verdict(total)) return rc;
+    uint8_t* p = sl->verdict;
+    uint8_t* q[MSM_PARTS];
+    for (int i = 0; i < MSM_PARTS; ++i) { q[i] = p; p += pad256(sz[i]); }
+    for (int i = 0; i < n_extra; ++i) { q_extra[i] = p; p += pad256(extra[i]); }
+    B.fail = reinterpret_cast<uint32_t*>(q[0]);
+    span_sum = B.fail + 16;
+    B.partial = q[1];
+    B.terms = reinterpret_cast<uint32_t*>(q[2]);
+    B.scalars = q[3];
+    M.terms = B.terms; M.scalars = B.scalars;
+    M.off = reinterpret_cast<uint32_t*>(q[4]); M.cursor = reinterpret_cast<uint32_t*>(q[5]); M.order = reinterpret_cast<uint32_t*>(q[6]);
+    M.buckets = reinterpret_cast<uint32_t*>(q[7]); M.segs = reinterpret_cast<uint32_t*>(q[8]); M.win = reinterpret_cast<uint32_t*>(q[9]);
+    return JJS_OK;
+}
+}  // extern "C++"
+// the MSM's launches on stream s, after the item pass has written the terms and scalars and M.off is clear
+static void msm_launch(const msm_params& M, uint32_t* span_sum, hipStream_t s) {
+    const size_t nb = (size_t)M.W * M.B;
+    const unsigned term_blocks = (unsigned)grid_for(8192, M.N);
+    hipLaunchKernelGGL(msm_sort_kernel<false>, dim3(term_blocks), dim3(BLOCK), 0, s, M);
+    const unsigned spans = (unsigned)((nb + MSM_SCAN_SPAN - 1) / MSM_SCAN_SPAN);
+    hipLaunchKernelGGL(msm_scan_kernel<0>, dim3(spans), dim3(1024), 0, s, M, span_sum);
+    hipLaunchKernelGGL(msm_scan_kernel<1>, dim3(1), dim3(1024), 0, s, M, span_sum);
+    hipLaunchKernelGGL(msm_scan_kernel<2>, dim3(spans), dim3(1024), 0, s, M, span_sum);
+    hipLaunchKernelGGL(msm_sort_kernel<true>, dim3(term_blocks), dim3(BLOCK), 0, s, M);
+    hipLaunchKernelGGL(msm_bucket_kernel, dim3((unsigned)((nb + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, M);
+    hipLaunchKernelGGL(msm_segment_kernel, dim3((unsigned)(((size_t)M.W * M.K + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, M);
+    hipLaunchKernelGGL(msm_window_kernel, dim3((unsigned)M.W), dim3(BLOCK), 0, s, M);
 }
 
 // The verdict algorithm on stream s (under L.mu; g is the device): d = the affine columns in the entry point's order.
@@ -65,48 +117,20 @@ static int verdict_launch_msm(int scheme, const void* const* d, size_t n, uint32
     msm_params M{};
     M.n = n; M.N = (uint64_t)B.n_kinds * n;
     for (uint32_t k = 0; k < B.n_kinds; ++k) M.neg_kinds |= bv_kind_negated(B.V, k) ? 1u << k : 0u;
-    M.c = msm_pick_window(M.N);
-#if defined(JJS_PROFILING)
-    if (g_force_msm_window >= 8 && g_force_msm_window <= MSM_MAX_WINDOW) M.c = g_force_msm_window;
-#endif
+    static_cast<msm_shape&>(M) = msm_shape_full(msm_window(msm_pick_window(M.N)));
     B.z_bits = msm_weight_bits(M.c);
-    M.W = msm_windows(M.c); M.top_split = msm_top_split(M.c); M.B = msm_buckets(M.c); M.K = msm_segments(M.c); M.L = M.B / M.K;
     const uint32_t blocks = (uint32_t)grid_for(g->grid_prepare, n);
-    const size_t nb = (size_t)M.W * M.B;
-    const size_t sz[] = {pad256(64 + 4 * ((nb + MSM_SCAN_SPAN - 1) / MSM_SCAN_SPAN + 1)), pad256((size_t)blocks * 64), pad256(M.N * MSM_TERM_WORDS * 4), pad256(M.N * 32), pad256((nb + 1) * 4),
-                         pad256(nb * 4), pad256(M.N * M.W * 4), pad256(nb * MSM_EXT_WORDS * 4), pad256((size_t)M.W * M.K * MSM_EXT_WORDS * 4),
-                         pad256((size_t)M.W * MSM_EXT_WORDS * 4)};
-    size_t total = 0;
-    for (size_t x : sz) total += x;
     pick_slot(n, s);
-    if (int rc = ensure_verdict(total)) return rc;
-    uint8_t* p = sl->verdict;
-    uint8_t* q[10];
-    for (int i = 0; i < 10; ++i) { q[i] = p; p += sz[i]; }
-    B.fail = reinterpret_cast<uint32_t*>(q[0]);
-    B.partial = q[1];
-    B.terms = reinterpret_cast<uint32_t*>(q[2]);
-    B.scalars = q[3];
-    M.terms = B.terms; M.scalars = B.scalars;
-    M.off = reinterpret_cast<uint32_t*>(q[4]); M.cursor = reinterpret_cast<uint32_t*>(q[5]); M.order = reinterpret_cast<uint32_t*>(q[6]);
-    M.buckets = reinterpret_cast<uint32_t*>(q[7]); M.segs = reinterpret_cast<uint32_t*>(q[8]); M.win = reinterpret_cast<uint32_t*>(q[9]);
+    uint32_t* span_sum = nullptr;
+    if (int rc = verdict_scratch(B, M, blocks, nullptr, 0, nullptr, span_sum)) return rc;
     if (int rc = begin_shared(s)) return rc;
+    const size_t nb = (size_t)M.W * M.B;
     clear_params Z{};
     Z.p[0] = B.fail; Z.bytes[0] = 4;
     Z.p[1] = M.off; Z.bytes[1] = (nb + 1) * 4;
     hipLaunchKernelGGL(clear_kernel, dim3((unsigned)grid_for(256, nb / 16 + 1)), dim3(BLOCK), 0, s, Z);
     hipLaunchKernelGGL(bv_item_kernel, dim3(blocks), dim3(BLOCK), 0, s, B);
-    const unsigned term_blocks = (unsigned)grid_for(8192, M.N);
-    hipLaunchKernelGGL(msm_sort_kernel<false>, dim3(term_blocks), dim3(BLOCK), 0, s, M);
-    const unsigned spans = (unsigned)((nb + MSM_SCAN_SPAN - 1) / MSM_SCAN_SPAN);
-    uint32_t* span_sum = reinterpret_cast<uint32_t*>(q[0]) + 16;        // <= 4096 + 1 words behind the fail word
-    hipLaunchKernelGGL(msm_scan_kernel<0>, dim3(spans), dim3(1024), 0, s, M, span_sum);
-    hipLaunchKernelGGL(msm_scan_kernel<1>, dim3(1), dim3(1024), 0, s, M, span_sum);
-    hipLaunchKernelGGL(msm_scan_kernel<2>, dim3(spans), dim3(1024), 0, s, M, span_sum);
-    hipLaunchKernelGGL(msm_sort_kernel<true>, dim3(term_blocks), dim3(BLOCK), 0, s, M);
-    hipLaunchKernelGGL(msm_bucket_kernel, dim3((unsigned)((nb + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, M);
-    hipLaunchKernelGGL(msm_segment_kernel, dim3((unsigned)(((size_t)M.W * M.K + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, M);
-    hipLaunchKernelGGL(msm_window_kernel, dim3((unsigned)M.W), dim3(BLOCK), 0, s, M);
+    msm_launch(M, span_sum, s);
     hipLaunchKernelGGL(bv_final_kernel, dim3(1), dim3(BLOCK), 0, s, B, M, blocks, verdict);
     HIP_TRY(hipGetLastError());
     return end_shared(s);
@@ -125,16 +149,19 @@ static int verdict_launch_items(int scheme, const void* const* d, size_t n, uint
 }
 static size_t verdict_cols(int scheme) { return scheme == JJS_SCHEME_DOUBLE ? 6 : (scheme == JJS_SCHEME_SINGLE ? 4 : 5); }
 
+// the verdict word of a resident call, checked; an empty batch is answered here (1)
+static int verdict_word_dev(void* verdict, size_t n, hipStream_t s) {
+    if (!verdict || (reinterpret_cast<uintptr_t>(verdict) & 3u)) return fail(JJS_ERR_ARG, "null or misaligned verdict word");
+    if (n == 0) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)verdict, 1, 1, s));
+    return JJS_OK;
+}
 // a resident verdict call: device columns d[], the verdict word on the device, asynchronous on `stream`
 static int verdict_dev(int scheme, const void* const* d, size_t n, void* verdict, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (!verdict || (reinterpret_cast<uintptr_t>(verdict) & 3u)) return fail(JJS_ERR_ARG, "null or misaligned verdict word");
-    if (n == 0) {
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)verdict, 1, 1, s));
-        return JJS_OK;
-    }
+    if (int rc = verdict_word_dev(verdict, n, s)) return rc;
+    if (n == 0) return JJS_OK;
     for (size_t k = 0; k < verdict_cols(scheme); ++k)
         if (!d[k] || !aligned16(d[k])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
     return no_throw([&] {
@@ -143,9 +170,42 @@ static int verdict_dev(int scheme, const void* const* d, size_t n, void* verdict
     });
 }
 
-// a host-buffer verdict call: blocking.  The per-item route is the existing host call (its statuses are the caller's);
-// the verdict algorithm uploads the columns whole to the key-set staging area (one such call at a time per device,
-// host_mu), and on a verdict of 0 the statuses come from the existing host call.
+// The verdict algorithm's route of a blocking host call that has counted itself among g_keyset_host_calls: the columns go
+// whole to dev's key-set staging area (one such call at a time per device, host_mu), launch(k, c, d, verdict word, stream)
+// runs under L.mu, the verdict comes back.  Verdict 1: every status is 0; verdict 0: the statuses come from per_item().
+extern "C++" {
+template <class Launch, class PerItem>
+static int verdict_host_msm(device_state* dev, const jjs_keyset* ks, const size_t* widths, const void* const* src, size_t cols, size_t n,
+                            Launch launch, PerItem per_item, uint8_t* status, int* verdict) {
+    int v = 0;
+    {
+        keyset_host_call_leave leave_on_every_way_out;
+        std::lock_guard<std::mutex> big(dev->host_mu);
+        g = dev;
+        int rc = no_throw([&]() -> int {
+            const size_t out_bytes[1] = {256};                        // the verdict word
+            keyset_stage S{};
+            if (int r = keyset_stage_in(dev, widths, src, cols, n, out_bytes, 1, S)) return r;
+            uint32_t* vw = reinterpret_cast<uint32_t*>(S.out[0]);
+            if (int r = keyset_launch_locked(dev, ks, [&](keyset_entry* k, const keyset_copy* c) { return launch(k, c, S.d, vw, S.s); })) return r;
+            uint32_t hv = 0;
+            HIP_TRY(hipMemcpyAsync(&hv, vw, 4, hipMemcpyDeviceToHost, S.s));
+            HIP_TRY(hipStreamSynchronize(S.s));
+            v = hv ? 1 : 0;
+            return JJS_OK;
+        });
+        if (rc) return rc;
+    }
+    *verdict = v;
+    if (status) {
+        if (v) memset(status, 0, n);
+        else return per_item();
+    }
+    return JJS_OK;
+}
+}  // extern "C++"
+
+// a host-buffer verdict call: blocking.  The per-item route is the existing host call (its statuses are the caller's).
 static int verdict_host(int scheme, const uint8_t* const* ptrs, size_t n, uint8_t* status, int* verdict) {
     if (!verdict) return fail(JJS_ERR_ARG, "null verdict");
     const size_t ncol = verdict_cols(scheme);
@@ -162,57 +222,19 @@ static int verdict_host(int scheme, const uint8_t* const* ptrs, size_t n, uint8_
         if (msm) ++g_keyset_host_calls;       // jjs_shutdown does not free `dev` before this call has left
     }
     uint64_t tally[4] = {};
+    auto per_item = [&] { return host_call(scheme, JJS_FORMAT_AFFINE, ptrs, n, status, tally); };
     if (!msm) {
-        if (int rc = host_call(scheme, JJS_FORMAT_AFFINE, ptrs, n, status, tally)) return rc;
+        if (int rc = per_item()) return rc;
         *verdict = tally[0] == n ? 1 : 0;
         return JJS_OK;
     }
-    int v = 0;
-    {
-        struct leave {
-            ~leave() {
-                std::lock_guard<std::mutex> lock(L.mu);
-                --g_keyset_host_calls;
-                L.lane_cv.notify_all();
-            }
-        } leave_on_every_way_out;
-        std::lock_guard<std::mutex> big(dev->host_mu);
-        g = dev;
-        int rc = no_throw([&]() -> int {
-            size_t off[7], total = 0;
-            for (size_t i = 0; i < ncol; ++i) { off[i] = total; total += pad256(SHAPES[scheme][JJS_FORMAT_AFFINE].col[i].width * n); }
-            off[ncol] = total; total += 256;                          // the verdict word
-            if (total > dev->ks_stage_bytes) {
-                const size_t cap = grown(total);
-                if (int r = regrow(dev->ks_stage, dev->ks_stage_bytes, dev->ks_stage_bytes, cap, cap)) return r;
-            }
-            HIP_TRY(hipSetDevice(dev->device));
-            hipStream_t s = dev->ks_stream;
-            const void* d[6] = {};
-            for (size_t i = 0; i < ncol; ++i) {
-                d[i] = dev->ks_stage + off[i];
-                HIP_TRY(hipMemcpyAsync(dev->ks_stage + off[i], ptrs[i], SHAPES[scheme][JJS_FORMAT_AFFINE].col[i].width * n, hipMemcpyHostToDevice, s));
-            }
-            uint32_t* vw = reinterpret_cast<uint32_t*>(dev->ks_stage + off[ncol]);
-            {
-                std::lock_guard<std::mutex> lock(L.mu);
-                if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
-                if (int r = verdict_launch_msm(scheme, d, n, vw, s)) return r;
-            }
-            uint32_t hv = 0;
-            HIP_TRY(hipMemcpyAsync(&hv, vw, 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            v = hv ? 1 : 0;
-            return JJS_OK;
-        });
-        if (rc) return rc;
-    }
-    *verdict = v;
-    if (status) {
-        if (v) memset(status, 0, n);
-        else if (int rc = host_call(scheme, JJS_FORMAT_AFFINE, ptrs, n, status, tally)) return rc;
-    }
-    return JJS_OK;
+    size_t widths[6];
+    for (size_t i = 0; i < ncol; ++i) widths[i] = SHAPES[scheme][JJS_FORMAT_AFFINE].col[i].width;
+    return verdict_host_msm(dev, nullptr, widths, reinterpret_cast<const void* const*>(ptrs), ncol, n,
+                            [&](keyset_entry*, const keyset_copy*, const void* const* d, uint32_t* vw, hipStream_t s) {
+                                return verdict_launch_msm(scheme, d, n, vw, s);
+                            },
+                            per_item, status, verdict);
 }
 
 extern "C" {

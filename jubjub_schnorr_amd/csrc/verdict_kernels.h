@@ -3,14 +3,11 @@
 #pragma once
 
 // the MSM's launches: terms and scalars from bv_item_kernel, then the sort, buckets, segments and windows of msm.h
-struct msm_params {
+struct msm_params : msm_shape {       // c, W, top_split, B, K, L
     const uint32_t* terms;
     const uint8_t* scalars;
     uint64_t n, N;                    // items, terms (n_kinds * n)
     uint32_t neg_kinds;               // bit k: the terms of kind k are negated points
-    int c, W;                         // window width, windows
-    int top_split;                    // the top window's slots per digit, as a power of two (msm_top_split; 0 for short scalars)
-    uint32_t B, K, L;                 // buckets per window, segments per window, buckets per segment
     uint32_t* off;                    // W * B + 1: counts, then their exclusive prefix sums
     uint32_t* cursor;                 // W * B: the scatter's positions
     uint32_t* order;                  // the sorted entries: term | MSM_NEG
@@ -19,9 +16,22 @@ struct msm_params {
     uint32_t* win;                    // W extended points
 };
 
-// The per-item pass: one lane per item (grid-stride), the sums of z u (z' u) per block, a failed check clears the verdict
-// (one atomic per wave, from the ballot).
-__global__ __launch_bounds__(BLOCK, 2) void bv_item_kernel(bv_params B) {
+// red[0 .. MSM_EXT_WORDS) = the sum over the block's lanes of acc, by a tree (red: BLOCK * MSM_EXT_WORDS words)
+__device__ inline void block_sum_ext(uint32_t* red, const ext_pt& acc) {
+    msm_store_ext(red + threadIdx.x * MSM_EXT_WORDS, acc);
+    __syncthreads();
+    for (int step = BLOCK / 2; step > 0; step >>= 1) {
+        if ((int)threadIdx.x < step)
+            msm_store_ext(red + threadIdx.x * MSM_EXT_WORDS,
+                          msm_add_ext(msm_load_ext(red + threadIdx.x * MSM_EXT_WORDS), msm_load_ext(red + (threadIdx.x + step) * MSM_EXT_WORDS)));
+        __syncthreads();
+    }
+}
+
+// The per-item pass (item = bv_item or ksv_item on its params): one lane per item (grid-stride), the sums of z u (z' u) per
+// block, a failed check clears the verdict (one atomic per wave, from the ballot).
+template <class P, class Item>
+__device__ inline void verdict_item_pass(const P& B, Item item_fn) {
     __shared__ words8 red[2][BLOCK];
     words8 acc[2] = {words_zero(), words_zero()};
     const uint64_t total = (uint64_t)gridDim.x * BLOCK;
@@ -31,7 +41,7 @@ __global__ __launch_bounds__(BLOCK, 2) void bv_item_kernel(bv_params B) {
         bool ok = true;
         if (active) {
             words8 zu[2];
-            ok = bv_item(B, item, zu);
+            ok = item_fn(B, item, zu);
             acc[0] = fr_add(acc[0], zu[0]);
             acc[1] = fr_add(acc[1], zu[1]);
         }
@@ -49,6 +59,9 @@ __global__ __launch_bounds__(BLOCK, 2) void bv_item_kernel(bv_params B) {
         store_words(B.partial, 2 * blockIdx.x, red[0][0]);
         store_words(B.partial, 2 * blockIdx.x + 1, red[1][0]);
     }
+}
+__global__ __launch_bounds__(BLOCK, 2) void bv_item_kernel(bv_params B) {
+    verdict_item_pass(B, [](const bv_params& b, uint64_t item, words8* zu) { return bv_item(b, item, zu); });
 }
 
 // counting sort of (window, |digit|): count (scatter = false), then place (scatter = true); one lane per term
@@ -129,14 +142,7 @@ __global__ __launch_bounds__(BLOCK) void msm_window_kernel(msm_params M) {
     const uint32_t j = blockIdx.x;
     ext_pt acc = ext_identity();
     for (uint32_t k = threadIdx.x; k < M.K; k += BLOCK) acc = msm_add_ext(acc, msm_load_ext(M.segs + ((size_t)j * M.K + k) * MSM_EXT_WORDS));
-    msm_store_ext(red + threadIdx.x * MSM_EXT_WORDS, acc);
-    __syncthreads();
-    for (int step = BLOCK / 2; step > 0; step >>= 1) {
-        if ((int)threadIdx.x < step)
-            msm_store_ext(red + threadIdx.x * MSM_EXT_WORDS,
-                          msm_add_ext(msm_load_ext(red + threadIdx.x * MSM_EXT_WORDS), msm_load_ext(red + (threadIdx.x + step) * MSM_EXT_WORDS)));
-        __syncthreads();
-    }
+    block_sum_ext(red, acc);
     if (threadIdx.x < MSM_EXT_WORDS) M.win[(size_t)j * MSM_EXT_WORDS + threadIdx.x] = red[threadIdx.x];
 }
 // one block: the per-block sums of z u added, the windows combined, the fixed-base part, the verdict word

@@ -1,54 +1,11 @@
 // CPU build of csrc/keyset_verdict.h (the batch verdict against a registered key set, jjs_keyset_verify_all*) for
 // tests/test_keyset_verify_all_host.py: the device's steps run here in loops with the same functions -- the set built as
 // keyset_harness.cpp builds it, the index pass, the keyed item pass (ksv_item), the counting sort by key, the heads and
-// cells of the runs, the key points (ksv_key_point), the bucket method over the R terms with the short weights' windows,
-// bv_verdict.  The comb tables and the double scheme's tag come from host_harness.cpp.
+// cells of the runs, the key points (ksv_key_point), the bucket method (host_msm.h) over the R terms with the short
+// weights' windows, bv_verdict.  The comb tables and the double scheme's tag come from host_harness.cpp.
 #include "host_harness.cpp"
 #include "keyset_verdict.h"
-
-namespace {
-
-// sum of N negated terms with short weights by the bucket method: msm_short_windows(c) windows, no split of the top one
-ext_pt short_msm(const uint32_t* terms, const uint8_t* scalars, uint64_t N, int c) {
-    const int W = msm_short_windows(c);
-    const uint32_t B = msm_buckets(c), K = msm_short_segments(c), L = B / K;
-    std::vector<uint32_t> off((size_t)W * B + 1, 0), order;
-    for (int pass = 0; pass < 2; ++pass) {                     // 0: count, 1: scatter
-        std::vector<uint32_t> cursor;
-        if (pass) {
-            uint32_t sum = 0;
-            for (size_t i = 0; i < off.size(); ++i) { const uint32_t v = off[i]; off[i] = sum; sum += v; }
-            order.assign(sum, 0);
-            cursor.assign(off.begin(), off.end());
-        }
-        for (uint64_t t = 0; t < N; ++t) {
-            const words8 s = load_words(fe_src{scalars, 32, 0}, t);
-            uint32_t carry = 0;
-            for (int j = 0; j < W; ++j) {
-                const int32_t d = msm_digit_step(s, j, c, W, carry);
-                if (!d) continue;
-                const uint32_t slot = msm_slot_split(j, d, t, W, 0);
-                if (slot >= B) continue;               // (never: the weights have c W - 1 bits)
-                const uint32_t id = (uint32_t)j * B + slot;
-                if (!pass) ++off[id];
-                else order[cursor[id]++] = (uint32_t)t | ((d < 0) ? 0u : MSM_NEG);
-            }
-        }
-    }
-    std::vector<uint32_t> buckets((size_t)W * B * MSM_EXT_WORDS), win((size_t)W * MSM_EXT_WORDS);
-    for (uint32_t id = 0; id < (uint32_t)W * B; ++id) msm_store_ext(&buckets[(size_t)id * MSM_EXT_WORDS], msm_bucket(off.data(), order.data(), terms, id));
-    for (int j = 0; j < W; ++j) {
-        ext_pt acc = ext_identity();
-        for (uint32_t seg = 0; seg < K; ++seg) acc = msm_add_ext(acc, msm_segment(buckets.data(), B, (uint32_t)j, seg, L, 0));
-        msm_store_ext(&win[(size_t)j * MSM_EXT_WORDS], acc);
-    }
-    return msm_combine(win.data(), W, c);
-}
-
-template <class T>
-T* align16(std::vector<T>& v) { return (T*)(((uintptr_t)v.data() + 15) & ~(uintptr_t)15); }
-
-}  // namespace
+#include "host_msm.h"
 
 extern "C" {
 
@@ -131,7 +88,7 @@ int jjs_ksv_host_verify_all(int scheme, const uint8_t* keys0, const uint8_t* key
     for (uint32_t k = 0; k < n_keys; ++k) { const uint32_t cnt = cursor[k]; cursor[k] = run; run += cnt; }
     for (uint64_t i = 0; i < n; ++i) order[cursor[keyid[i]]++] = (uint32_t)i;
     const ksv_runs Rn{cursor.data(), 1u, order.data(), keyid.data(), n_keys, n};
-    ext_pt total = short_msm(B.terms, B.scalars, N, c);
+    ext_pt total = host_msm(B.terms, B.scalars, N, msm_shape_short(c), [](uint64_t) { return true; });     // every term is a -R
     for (uint32_t ci = 0; ci < cols; ++ci) {
         uint8_t *h = align16(head[ci]), *cl = align16(cell[ci]);
         for (uint32_t k = 0; k < n_keys; ++k) store_words(h, k, ksv_head(Rn, B.a[ci], k));
@@ -145,9 +102,7 @@ int jjs_ksv_host_verify_all(int scheme, const uint8_t* keys0, const uint8_t* key
     if (total_out) {
         for (uint32_t e = 0; e < B.V.n_eq; ++e)
             if (B.V.eq[e].comb) total = add_comb_range(total, B.V.eq[e].comb, sum[e], 0, COMB_WINDOWS, true);
-        const fe_n zi = fq_inverse(total.z);
-        store_words(total_out, 0, fq_to_words(fq_mul(total.x, zi)));
-        store_words(total_out, 1, fq_to_words(fq_mul(total.y, zi)));
+        to_affine_bytes(total, total_out);
     }
     return 0;
 }

@@ -1,54 +1,9 @@
 // CPU build of csrc/batch_verdict.h and csrc/msm.h (the batch verdict of jjs_verify_all_*) for tests/test_verify_all_host.py:
-// the device's steps run here in loops -- the per-item pass (bv_item), the counting sort of the MSM terms, one bucket, one
-// segment and one window at a time, Horner's rule -- with the same functions.  The comb tables and the double scheme's tag
-// come from host_harness.cpp.
+// the device's steps run here in loops -- the per-item pass (bv_item), then the bucket method (host_msm.h) -- with the same
+// functions.  The comb tables and the double scheme's tag come from host_harness.cpp.
 #include "host_harness.cpp"
 #include "batch_verdict.h"
-
-namespace {
-
-// sum of the terms (terms: N cached addends; scalars N x 32; neg: N flags) by the bucket method with c-bit windows
-ext_pt host_msm(const uint32_t* terms, const uint8_t* scalars, const uint8_t* neg, uint64_t N, int c) {
-    const int W = msm_windows(c);
-    const uint32_t B = msm_buckets(c), K = msm_segments(c), L = B / K;
-    std::vector<uint32_t> off((size_t)W * B + 1, 0), order;
-    for (int pass = 0; pass < 2; ++pass) {                     // 0: count, 1: scatter
-        std::vector<uint32_t> cursor;
-        if (pass) {
-            uint32_t sum = 0;
-            for (size_t i = 0; i < off.size(); ++i) { const uint32_t v = off[i]; off[i] = sum; sum += v; }
-            order.assign(sum, 0);
-            cursor.assign(off.begin(), off.end());
-        }
-        for (uint64_t t = 0; t < N; ++t) {
-            const words8 s = load_words(fe_src{scalars, 32, 0}, t);
-            uint32_t carry = 0;
-            for (int j = 0; j < W; ++j) {
-                const int32_t d = msm_digit_step(s, j, c, W, carry);
-                if (!d) continue;
-                const uint32_t id = (uint32_t)j * B + msm_slot(j, d, t, c, W);
-                if (!pass) ++off[id];
-                else order[cursor[id]++] = (uint32_t)t | (((d < 0) != (neg[t] != 0)) ? MSM_NEG : 0u);
-            }
-        }
-    }
-    std::vector<uint32_t> buckets((size_t)W * B * MSM_EXT_WORDS), win((size_t)W * MSM_EXT_WORDS);
-    for (uint32_t id = 0; id < (uint32_t)W * B; ++id) msm_store_ext(&buckets[(size_t)id * MSM_EXT_WORDS], msm_bucket(off.data(), order.data(), terms, id));
-    for (int j = 0; j < W; ++j) {
-        ext_pt acc = ext_identity();
-        for (uint32_t seg = 0; seg < K; ++seg) acc = msm_add_ext(acc, msm_segment(buckets.data(), B, (uint32_t)j, seg, L, j == W - 1 ? msm_top_split(c) : 0));
-        msm_store_ext(&win[(size_t)j * MSM_EXT_WORDS], acc);
-    }
-    return msm_combine(win.data(), W, c);
-}
-
-void to_affine_bytes(const ext_pt& p, uint8_t* out) {
-    const fe_n zi = fq_inverse(p.z);
-    store_words(out, 0, fq_to_words(fq_mul(p.x, zi)));
-    store_words(out, 1, fq_to_words(fq_mul(p.y, zi)));
-}
-
-}  // namespace
+#include "host_msm.h"
 
 extern "C" {
 
@@ -67,10 +22,10 @@ int jjs_vh_msm(const uint8_t* points, const uint8_t* scalars, const uint8_t* neg
     if (c == 0) c = msm_pick_window(N);
     if (c < 2 || c > MSM_MAX_WINDOW) return -1;
     std::vector<uint32_t> terms(N * MSM_TERM_WORDS + 4);
-    uint32_t* t = (uint32_t*)(((uintptr_t)terms.data() + 15) & ~(uintptr_t)15);
+    uint32_t* t = align16(terms);
     const fe_src src{points, 64, 0};
     for (size_t i = 0; i < N; ++i) msm_store_term(t + i * MSM_TERM_WORDS, load_fq(src, i), load_fq(src, i, 32));
-    to_affine_bytes(host_msm(t, scalars, neg, N, c), out);
+    to_affine_bytes(host_msm(t, scalars, N, msm_shape_full(c), [&](uint64_t i) { return neg[i] != 0; }), out);
     return 0;
 }
 
@@ -91,9 +46,8 @@ int jjs_vh_verify_all(int scheme, const uint8_t* u, const uint8_t* R, const uint
     if (c == 0) c = msm_pick_window(N);
     B.z_bits = msm_weight_bits(c);
     std::vector<uint32_t> terms(N * MSM_TERM_WORDS + 4);
-    std::vector<uint8_t> scalars(N * 32 + 16), neg(N);
-    B.terms = (uint32_t*)(((uintptr_t)terms.data() + 15) & ~(uintptr_t)15);
-    B.scalars = (uint8_t*)(((uintptr_t)scalars.data() + 15) & ~(uintptr_t)15);
+    std::vector<uint8_t> scalars(N * 32 + 16);
+    B.terms = align16(terms); B.scalars = align16(scalars);
     bool failed = false;
     words8 sum[2] = {words_zero(), words_zero()};
     for (uint64_t i = 0; i < n; ++i) {
@@ -102,8 +56,7 @@ int jjs_vh_verify_all(int scheme, const uint8_t* u, const uint8_t* R, const uint
         sum[0] = fr_add(sum[0], zu[0]);
         sum[1] = fr_add(sum[1], zu[1]);
     }
-    for (size_t t = 0; t < N; ++t) neg[t] = bv_kind_negated(B.V, (uint32_t)(t / n)) ? 1 : 0;
-    const ext_pt total = host_msm(B.terms, B.scalars, neg.data(), N, c);
+    const ext_pt total = host_msm(B.terms, B.scalars, N, msm_shape_full(c), [&](uint64_t t) { return bv_kind_negated(B.V, (uint32_t)(t / n)); });
     *verdict = bv_verdict(B.V, total, sum, failed) ? 1 : 0;
     return 0;
 }

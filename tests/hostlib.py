@@ -13,24 +13,23 @@ CSRC = os.path.join(ROOT, "jubjub_schnorr_amd", "csrc")
 _lib = None
 
 
-def _stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
-    return any(os.path.getmtime(d) > t for d in deps)
+def build_hostlib(src, lib):
+    """Compile a harness under tests/hostbuild into `lib` unless it is newer than its sources, and load it."""
+    hostbuild = os.path.dirname(SRC)
+    deps = [src, SRC, os.path.join(hostbuild, "host_msm.h")] + \
+        [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
+    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
+        # JJS_HOST_SANITIZE=1 python -m pytest tests/test_hostbuild.py  -> the same tests under UBSan
+        san = ["-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=undefined"] if os.environ.get("JJS_HOST_SANITIZE") else ["-O2"]
+        subprocess.check_call(["g++", *san, "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas",
+                               "-I" + CSRC, "-o", lib, src])
+    return ctypes.CDLL(lib)
 
 
 def load():
     global _lib
-    if _lib is not None:
-        return _lib
-    if _stale():
-        # JJS_HOST_SANITIZE=1 python -m pytest tests/test_hostbuild.py  -> the same tests under UBSan
-        san = ["-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=undefined"] if os.environ.get("JJS_HOST_SANITIZE") else ["-O2"]
-        subprocess.check_call(["g++", *san, "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas",
-                               "-I" + CSRC, "-o", LIB, SRC])
-    _lib = ctypes.CDLL(LIB)
+    if _lib is None:
+        _lib = build_hostlib(SRC, LIB)
     return _lib
 
 

@@ -2,37 +2,22 @@
 (the recipe of hostlib.py)."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+from hostlib import build_hostlib
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "hostbuild", "verdict_harness.cpp")
 LIB = os.path.join(HERE, "hostbuild", "libjjs_verdict_hosttest.so")
-CSRC = os.path.join(ROOT, "jubjub_schnorr_amd", "csrc")
 SCHEMES = {"single": 0, "double": 1, "vargen": 2}
 _lib = None
 
 
-def _stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [SRC, os.path.join(HERE, "hostbuild", "host_harness.cpp")] + \
-        [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
 def load():
     global _lib
-    if _lib is not None:
-        return _lib
-    if _stale():
-        san = ["-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=undefined"] if os.environ.get("JJS_HOST_SANITIZE") else ["-O2"]
-        subprocess.check_call(["g++", *san, "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas",
-                               "-I" + CSRC, "-o", LIB, SRC])
-    _lib = ctypes.CDLL(LIB)
+    if _lib is None:
+        _lib = build_hostlib(SRC, LIB)
     return _lib
 
 
