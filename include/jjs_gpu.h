@@ -401,6 +401,10 @@ int jjs_debug_comb_table(int which, void* host_out);
 /* Loads RCCL, forms a one-rank clique on the current device and all-reduces a known 4 x u64 vector on the
  * engine stream: the call sequence of the multi-device tally reduction, runnable with a single GPU. */
 int jjs_debug_rccl_selftest(void);
+/* The lanes of the multisignature kernel that are resident at once on the current device (its grid limit times its block
+ * size, from the occupancy query at jjs_init): a call with more shares than this takes a second trip through the kernel's
+ * grid-stride loop.  Negative: an error code. */
+int jjs_debug_msig_resident_lanes(void);
 
 #ifdef __cplusplus
 }

@@ -1157,5 +1157,6 @@ int jjs_debug_comb_table(int which, void* host_out) {
     HIP_TRY(hipMemcpy(host_out, which ? g->comb_gn : g->comb_g, COMB_TABLE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return JJS_OK;
 }
+int jjs_debug_msig_resident_lanes(void) { std::lock_guard<std::mutex> lock(L.mu); if (int rc = check_ready()) return rc; return g->grid_msig * BLOCK; }
 
 }  // extern "C"
