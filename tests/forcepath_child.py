@@ -46,6 +46,30 @@ def main() -> None:
             st, tally = eng.verify(scheme, *[dev(b[k]) for k in ARG_ORDER[scheme]])
             assert (st.cpu().numpy() == want).all(), (scheme, path)
             assert tally.cpu().numpy().tolist() == [int((want == k).sum()) for k in range(4)], (scheme, path)
+    # valid signatures whose points coincide (PK = +-G, PK = +-R, Gen = G, PK = Gen; tests/scalar_mul_cases.py) on the
+    # throughput path and, repeated until the keys take their tables, through the key tables of both widths
+    from scalar_mul_cases import degenerate_batch
+    for scheme in ("single", "double", "vargen"):
+        b = degenerate_batch(scheme)
+        want, want_c = oracle_verify(scheme, b, want_c=True)
+        assert set(want.tolist()) == {0, 2}
+        assert lib.jjs_debug_force_path(3) == 0
+        args = [dev(b[k]) for k in ARG_ORDER[scheme]]
+        before = eng.path_stats()
+        st, tally = eng.verify(scheme, *args)
+        assert st.cpu().numpy().tolist() == want.tolist(), scheme
+        assert (eng.challenge(scheme, *args[1:]).cpu().numpy() == want_c).all(), scheme
+        assert eng.path_stats()["throughput"] == before["throughput"] + 1
+        reps = -(-70000 // len(want))          # the key tables engage from 65 536 items
+        big = {k: np.tile(v, (reps, 1)) for k, v in b.items()}
+        want_big = np.tile(want, reps)
+        for path, name in ((0, "key_tables_wide"), (0x500, "key_tables_narrow")):
+            assert lib.jjs_debug_force_path(path) == 0
+            before = eng.path_stats()
+            st, tally = eng.verify(scheme, *[dev(big[k]) for k in ARG_ORDER[scheme]])
+            assert (st.cpu().numpy() == want_big).all(), (scheme, path)
+            assert tally.cpu().numpy().tolist() == [int((want_big == k).sum()) for k in range(4)], (scheme, path)
+            assert eng.path_stats()[name] == before[name] + 1, (scheme, path, before, eng.path_stats())
     lib.jjs_debug_force_path(0)
     # a device that cannot hold the key-table pool: the same batches take the throughput path, statuses unchanged, and the
     # path statistics say so (resident and host-buffer entry points)

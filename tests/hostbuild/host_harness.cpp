@@ -14,6 +14,7 @@
 #include "multisig_core.h"
 #include "jjs_sponge_tags_long.inc"
 #include "safe_tag.h"
+#include "../../jubjub_schnorr_amd/tools/scalar_stages.h"
 
 using namespace jjs;
 
@@ -154,8 +155,52 @@ static void run_keyed(verify_params P) {
     }
 }
 
+// tools/scalar_stages.h on this thread: the items of a record one after the other, LANES = 1 stages only
+struct host_records {
+    const uint32_t* in;
+    size_t in_words, pos = 0;
+    int records = 0;
+    std::vector<uint32_t> out;
+    sc::ctx C;
+    template <typename S>
+    int step(uint32_t n) {
+        static_assert(S::LANES == 1 && S::IN % 4 == 0, "one thread, 16-byte loads");
+        if (!sc::record_fits<S>(in_words, pos, n)) return 1;
+        std::vector<uint32_t> item(S::IN + 4), scratch(S::SCRATCH + 4), res((size_t)S::OUT + 4);
+        uint32_t* it = (uint32_t*)(((uintptr_t)item.data() + 15) & ~(uintptr_t)15);
+        uint32_t* sp = (uint32_t*)(((uintptr_t)scratch.data() + 15) & ~(uintptr_t)15);
+        uint32_t* rp = (uint32_t*)(((uintptr_t)res.data() + 15) & ~(uintptr_t)15);
+        for (uint32_t i = 0; i < n; ++i) {
+            memcpy(it, in + pos + (size_t)S::IN * i, 4 * S::IN);
+            memset(rp, 0xff, 4 * (size_t)S::OUT);
+            S::run(C, it, rp, sp, 0);
+            out.insert(out.end(), rp, rp + S::OUT);
+        }
+        pos += (size_t)S::IN * n;
+        return 0;
+    }
+};
+
 extern "C" {
 
+// the records of tools/scalar_stages.h (the product's scalar multiplications with caller-chosen scalars); returns 0 and the
+// number of output words, or the failing record's code
+int jjs_host_scalar_records(const uint32_t* in, size_t in_words, uint32_t* out, size_t out_cap, size_t* out_words) {
+    ensure_tables();
+    host_records x{in, in_words};
+    x.C = sc::ctx{{g_comb_g.data(), g_comb_gn.data()}};
+    const int rc = sc::run_records(x);
+    if (rc) return rc;
+    if (x.out.size() > out_cap) return 4;
+    memcpy(out, x.out.data(), 4 * x.out.size());
+    *out_words = x.out.size();
+    return 0;
+}
+// the whole comb table of G (0) or G' (1): COMB_WINDOWS x COMB_ENTRIES x COMB_ENTRY_WORDS words
+const uint32_t* jjs_host_comb_table(int which) {
+    ensure_tables();
+    return which ? g_comb_gn.data() : g_comb_g.data();
+}
 int jjs_host_set_split_prepare(int on) {
     g_split_prepare = on ? 1 : 0;
     return 0;

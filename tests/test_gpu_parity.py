@@ -106,6 +106,12 @@ def test_comb_tables(eng):
             e = tab[i, b]
             val = [sum(int(x) << (29 * j) for j, x in enumerate(e[9 * c:9 * c + 9])) * RPI % o.Q for c in range(3)]
             assert val == [(p[1] + p[0]) % o.Q, (p[1] - p[0]) % o.Q, 2 * o.D * p[0] * p[1] % o.Q]
+    # all 16 x 65 536 entries of both tables as the device built them, with the bounds add_comb_range assumes and the
+    # padding word (reference: the C oracle's point addition, held against the Python oracle on a sample of every row)
+    from scalar_mul_cases import check_comb_table
+    rng = np.random.default_rng(16)
+    for which, base in ((0, o.G), (1, o.G_NUMS)):
+        check_comb_table(np.asarray(eng.debug_comb_table(which)), base, rng)
 
 
 @pytest.mark.parametrize("scheme", ["single", "double", "vargen"])

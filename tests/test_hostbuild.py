@@ -82,6 +82,11 @@ def test_comb_tables_are_multiples_of_generators():
             assert t2d == 2 * o.D * p[0] * p[1] % o.Q
             # the per-entry builder the device runs gives the same entry as the row filler of the CPU harness
             assert hl.comb_entry_matches_device_builder(which, i, b)
+    # every entry of every row the harness builds, with the bounds add_comb_range assumes and the padding word
+    from scalar_mul_cases import check_comb_table
+    rng = np.random.default_rng(16)
+    for which, base in ((0, o.G), (1, o.G_NUMS)):
+        check_comb_table(hl.comb_table(which), base, rng)
 
 
 @pytest.mark.parametrize("scheme", ["single", "double", "vargen"])
