@@ -153,33 +153,106 @@ __global__ __launch_bounds__(BLOCK) void key_spread_kernel(key_params K) {
             if (r != (uint32_t)item) C.keyid[item] = C.keyid[r];      // r's own id was written by the previous launch
         }
 }
-// The chain of bases and `is_valid` of every key.  One lane per key does both (kt_chain_key); where the batch waits for the
-// chains (K.quad_chains, set by job_keys) four lanes per key share the doublings (kt_chain_key_quad) and a fifth runs
-// `is_valid`: the grid covers 5 x n_cols x max_keys lanes then.
+// The memo of the slot's last key-table call (key_tables.h step 5), behind the decision.  match: every distinct key looks
+// itself up; a hit takes over its pool index and flags, a miss joins the column's todo list.  A batch that turned the
+// tables down empties the memo instead (the width 0 matches no call), and so does a call that does not use it (KT_MEMO_OFF:
+// its keys are built at the pool index of their id, as they were before there was a memo).
+__global__ __launch_bounds__(BLOCK) void key_match_kernel(key_params K) {
+    const uint32_t w = K.counters[2];
+    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x, c = t / K.max_keys, id = t % K.max_keys;
+    if (!w || K.memo_mode == KT_MEMO_OFF) {
+        if (t < K.n_cols) kt_memo(K, (int32_t)t).hdr[0] = 0u;               // nobody in this launch reads it
+        if (!w || c >= K.n_cols || id >= K.counters[c]) return;
+        const key_column C = kt_col(K, (int32_t)c);
+        const key_memo M = kt_memo(K, (int32_t)c);
+        C.pool_of[id] = id;
+        M.todo[atomicAdd(&K.counters[8 + c], 1u)] = id;
+        return;
+    }
+    if (c >= K.n_cols || id >= K.counters[c]) return;
+    const key_column C = kt_col(K, (int32_t)c);
+    const key_memo M = kt_memo(K, (int32_t)c);
+    const bool live = K.memo_mode == KT_MEMO_LIVE && M.hdr[0] == w;
+    if (kt_memo_match(C, M, id, live, K.memo_seed, K.memo_call)) atomicAdd(&K.counters[12 + c], 1u);
+    else M.todo[atomicAdd(&K.counters[8 + c], 1u)] = id;
+}
+// place: the first lanes stand for the pool indices of the window width at hand, and those that no hit has claimed take
+// the misses of the todo list in turn (there are enough: the distinct keys fit the pool, and hits hold distinct indices);
+// the lanes behind them stand for the key ids, and the hits enter the hash table as entries of this call beside the misses.
+// The memo is then exactly the keys of this call.
+__global__ __launch_bounds__(BLOCK) void key_place_kernel(key_params K) {
+    const uint32_t w = K.counters[2];
+    if (!w || K.memo_mode == KT_MEMO_OFF) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x, scan = K.n_cols * K.pool_cap;
+    const uint32_t cap = w == (uint32_t)KT_WINDOW_WIDE ? (K.max_keys_wide < K.pool_cap ? K.max_keys_wide : K.pool_cap) : K.pool_cap;
+    const uint32_t pc = t / K.pool_cap, p = t % K.pool_cap;
+    for (uint32_t c = 0; c < K.n_cols; ++c) {                       // wave-uniform: the ballot
+        const key_column C = kt_col(K, (int32_t)c);
+        const key_memo M = kt_memo(K, (int32_t)c);
+        const bool mine = t < scan && pc == c && p < cap && p < M.cap && kt_memo_free(M, p, K.memo_call);
+        const unsigned long long m = __ballot(mine);
+        if (!m) continue;
+        uint32_t start = 0;
+        const int first = __ffsll((long long)m) - 1;
+        if (lane == (uint32_t)first) start = atomicAdd(&K.counters[10 + c], (uint32_t)__popcll(m));
+        start = (uint32_t)__shfl((int)start, first);
+        const uint32_t r = start + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (mine && r < K.counters[8 + c]) kt_memo_claim(C, M, M.todo[r], p, K.memo_seed, K.memo_call);
+    }
+    if (t >= scan) {
+        const uint32_t q = t - scan, c = q / K.max_keys, id = q % K.max_keys;
+        if (c < K.n_cols && id < K.counters[c]) {
+            const key_column C = kt_col(K, (int32_t)c);
+            const key_memo M = kt_memo(K, (int32_t)c);
+            const uint32_t at = M.hit[id];
+            if (at != KT_MEMO_NONE) kt_memo_insert(C, M, id, at, K.memo_seed, K.memo_call);
+        }
+        if (q < K.n_cols) {                                         // what the next call's match step reads; nobody here does
+            const key_memo M = kt_memo(K, (int32_t)q);
+            M.hdr[0] = w; M.hdr[1] = K.memo_call;
+        }
+    }
+}
+// The chain of bases and `is_valid` of every key that is not in the memo: the column's todo list (without a memo -- the
+// build of a registered key set -- every key, in the order of the ids).  One lane per key does both (kt_chain_key); where
+// the batch waits for the chains (K.quad_chains, set by job_keys) four lanes per key share the doublings (kt_chain_key_quad)
+// and a fifth runs `is_valid`: the grid covers 5 x n_cols x max_keys lanes then.  A call whose keys all hit leaves at once.
+__device__ __forceinline__ uint32_t kt_todo_count(const key_params& K, const key_memo& M, uint32_t c) { return M.todo ? K.counters[8 + c] : K.counters[c]; }
 __global__ __launch_bounds__(BLOCK, 2) void key_chain_kernel(key_params K) {
     const int w = (int)K.counters[2];
     if (!w) return;
     const uint32_t t = blockIdx.x * BLOCK + threadIdx.x, keys = K.n_cols * K.max_keys;
     // a key found valid joins the list of the keys that get tables (key_table_kernel)
     if (!K.quad_chains) {
-        const uint32_t c = t / K.max_keys, id = t % K.max_keys;
-        if (c < K.n_cols && id < K.counters[c]) {
+        const uint32_t c = t / K.max_keys, j = t % K.max_keys;
+        if (c >= K.n_cols) return;
+        const key_memo M = kt_memo(K, (int32_t)c);
+        if (j < kt_todo_count(K, M, c)) {
             const key_column C = kt_col(K, (int32_t)c);
-            if (kt_chain_key(C, id, w)) C.valid_ids[atomicAdd(&K.counters[5 + c], 1u)] = id;
+            const uint32_t id = M.todo ? M.todo[j] : j;
+            const bool valid = kt_chain_key(C, id, w);
+            kt_memo_flags(C, M, id);
+            if (valid) C.valid_ids[atomicAdd(&K.counters[5 + c], 1u)] = id;
         }
     } else if (t < 4 * keys) {
-        const uint32_t q = t >> 2, c = q / K.max_keys, id = q % K.max_keys;          // the same for the four lanes of a quad
-        if (id < K.counters[c]) kt_chain_key_quad(kt_col(K, (int32_t)c), id, w, t & 3u);
+        const uint32_t q = t >> 2, c = q / K.max_keys, j = q % K.max_keys;          // the same for the four lanes of a quad
+        const key_memo M = kt_memo(K, (int32_t)c);
+        if (j < kt_todo_count(K, M, c)) kt_chain_key_quad(kt_col(K, (int32_t)c), M.todo ? M.todo[j] : j, w, t & 3u);
     } else if (t < 5 * keys) {
-        const uint32_t q = t - 4 * keys, c = q / K.max_keys, id = q % K.max_keys;
-        if (id < K.counters[c]) {
+        const uint32_t q = t - 4 * keys, c = q / K.max_keys, j = q % K.max_keys;
+        const key_memo M = kt_memo(K, (int32_t)c);
+        if (j < kt_todo_count(K, M, c)) {
             const key_column C = kt_col(K, (int32_t)c);
-            if (kt_key_flags(C, id)) C.valid_ids[atomicAdd(&K.counters[5 + c], 1u)] = id;
+            const uint32_t id = M.todo ? M.todo[j] : j;
+            const bool valid = kt_key_flags(C, id);
+            kt_memo_flags(C, M, id);
+            if (valid) C.valid_ids[atomicAdd(&K.counters[5 + c], 1u)] = id;
         }
     }
 }
 // the grid covers max_keys x KT_MAX_POSITIONS lanes per column; a batch with wide windows has fewer of both, and only the
-// keys whose point is valid get tables (kt_finish_item)
+// keys that were built (key_chain_kernel) and whose point is valid get tables (kt_finish_item)
 __global__ __launch_bounds__(BLOCK, 2) void key_table_kernel(key_params K) {
     const int w = (int)K.counters[2];
     if (!w) return;

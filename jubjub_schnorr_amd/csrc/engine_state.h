@@ -77,7 +77,7 @@ public:
 // What the last key-table attempt of a slot found (key_params::counters), copied to pinned host memory behind the call:
 // the host reads it before the slot's next attempt (note_key_feedback) -- no call ever waits for it.
 struct key_feedback {
-    uint32_t counters[8];
+    uint32_t counters[16];
 };
 struct call_slot {
     uint32_t* workspace = nullptr;    // WS_WORDS_PER_LANE words per lane of the verify grid
@@ -101,6 +101,19 @@ struct call_slot {
     size_t key_pool_bytes = 0;
     size_t key_pool_want = 0;         // what the last call that found the pool too small would have needed
     size_t key_pool_refused = 0;      // a size hipMalloc turned down (not asked for again)
+    // The memo of the slot's last key-table call (key_tables.h step 5): device memory beside the pool, replaced and freed with it.
+    // Only the slot's own kernels touch it, in the order of the slot's calls (last_use), which is also the order in which they
+    // write the pool: a queued call reads the tables its own match step found claimed, and no later call of the slot -- the only
+    // other writer of this pool -- starts before that call has ended.  Another slot has another pool and another memo.
+    uint8_t* key_memo = nullptr;
+    size_t key_memo_bytes = 0;
+    uint32_t memo_cap = 0;            // pool indices per column its arrays hold
+    uint64_t memo_seed = 0;           // of its hash: drawn once, with the slot's first key-table call
+    bool memo_seeded = false;
+    uint32_t memo_call = 0;           // number of the slot's last key-table call (the stamp of what that call claimed)
+    uint32_t memo_cols = 0;           // key columns of that call: another number is another pool layout
+    bool memo_flush = true;           // the next call must not trust the memo: the pool is new, or a call was abandoned half-way
+    bool memo_dirty = false;          // ... and the memory is fresh from hipMalloc: the next call clears it on its key stream
     key_feedback* seen = nullptr;     // pinned host memory
     bool seen_pending = false;        // `seen` is being written by a call that may still run (its end: last_use)
     bool keys_repeated = true;        // the slot's last key-table attempt that has ended built tables (launch_staged)
@@ -247,6 +260,7 @@ struct device_state {
     int key_priority = 0;                // stream priority of the slots' key streams
     int table_priority = 0;              // ... and of their table streams (the lowest)
     std::atomic<uint64_t> stats[JJS_PATH_STATS] = {};   // jjs_path_stats: which path the calls on this device took
+    std::atomic<uint64_t> memo_stats[2] = {};           // keys the key-table calls found in their slot's memo / built (note_key_feedback)
     std::mutex host_mu;                  // large host-buffer calls: one at a time per device (they share the staging below)
     std::mutex retired_mu;               // guards `retired`
     hipStream_t copy_stream = nullptr;   // host-buffer calls: uploads and status downloads, beside `stream`

@@ -202,7 +202,7 @@ void free_device(device_state& d) {
     for (call_slot& c : d.slots) {
         if (c.key_stream) { (void)hipStreamSynchronize(c.key_stream); (void)hipStreamDestroy(c.key_stream); }
         if (c.table_stream) { (void)hipStreamSynchronize(c.table_stream); (void)hipStreamDestroy(c.table_stream); }
-        void* sb[] = {c.workspace, c.pending, c.prep, c.wire, c.small, c.keys, c.key_pool, c.verdict};
+        void* sb[] = {c.workspace, c.pending, c.prep, c.wire, c.small, c.keys, c.key_pool, c.key_memo, c.verdict};
         for (void* b : sb)
             if (b) (void)hipFree(b);
         if (c.seen) (void)hipHostFree(c.seen);
@@ -800,6 +800,8 @@ int jjs_trim(void) {
             HIP_TRY(hipFree(c.key_pool));
             if (c.key_pool_bytes > c.key_pool_want) c.key_pool_want = c.key_pool_bytes;
             c.key_pool = nullptr; c.key_pool_bytes = 0;
+            if (c.key_memo) HIP_TRY(hipFree(c.key_memo));      // the memo goes with the tables it describes
+            c.key_memo = nullptr; c.key_memo_bytes = 0; c.memo_cap = 0; c.memo_flush = true;
         }
     }
     return JJS_OK;
@@ -810,7 +812,7 @@ int jjs_memory_stats(uint64_t out[JJS_MEMORY_STATS]) {
     if (!out) return fail(JJS_ERR_ARG, "null pointer");
     uint64_t pool = 0, slots = 0, lanes = 0;
     for (const call_slot& c : g->slots) {
-        pool += c.key_pool_bytes;
+        pool += c.key_pool_bytes + c.key_memo_bytes;
         slots += c.pending_items * 8 + c.prep_items * 65 + c.wire_items * (4 * 64 + 16 + 2 * 48) + c.small_bytes + c.keys_bytes + c.verdict_bytes;
     }
     for (const host_lane& l : g->lanes) lanes += l.dev_bytes + l.pinned_bytes;
@@ -1117,6 +1119,18 @@ int jjs_debug_pin_hash_seed(int on) {
 int jjs_debug_fail_key_arena(int on) {
     std::lock_guard<std::mutex> lock(L.mu);
     g_fail_key_arena = on != 0;
+    return JJS_OK;
+}
+// include/jjs_gpu_key_memo.h
+int jjs_debug_key_memo_stats(uint64_t out[2]) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    if (!out) return fail(JJS_ERR_ARG, "null pointer");
+    for (call_slot& c : g->slots) {
+        sl = &c;
+        if (c.key_stream && !c.host_owned) note_key_feedback();
+    }
+    out[0] = g->memo_stats[0]; out[1] = g->memo_stats[1];
     return JJS_OK;
 }
 int jjs_debug_allow_virtual_devices(int allow) {

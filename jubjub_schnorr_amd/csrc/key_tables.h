@@ -21,6 +21,11 @@
 //                 then  acc = sum_i digit_i(c) * B_i  (51 or 43 additions, no doubling) + u*G from the fixed-base comb
 //                 (16 additions), compared with R projectively: the reference's own equation u*G + c*PK == R
 //                 (src/keys/public.rs:128-130), computed exactly by the complete addition law.
+//   5. memo      a slot's pool outlives the call, and so do the keys of real callers (the validator set of the next block): the
+//                 slot remembers which key bytes its last key-table call left at which pool index, with which flags and at
+//                 which window width (key_memo).  A key of the new call that is byte for byte in the memo skips step 3 and
+//                 reads the tables where they lie; every other key is built as before, at a pool index no key of this call
+//                 holds.  Key ids stay dense and per call; key_column::pool_of maps them to pool indices.
 //   Subgroup membership of R: if the equation holds and the key is torsion-free then R = u*G + c*PK is in the
 //   prime-order subgroup, and R != identity, on-curve are checked per item; if it fails, R's own test decides
 //   between InvalidPoint and InvalidSignature in the resolve pass (as for the per-item generator scheme).
@@ -78,9 +83,29 @@ struct key_column {
     uint8_t* key_undecodable;// [max_keys] wire calls: the key's encoding is not a point (decode.h)
     uint32_t* valid_ids;     // [max_keys] the ids of the keys whose point is valid, in the order the chain kernel found them (their
                              // number: key_params::counters[5 + column]): only these get window tables
-    uint32_t* bases;         // [keys][positions][36]: 2^(w i) * P in extended coordinates (w = the window width of this batch)
-    uint32_t* tables;        // [keys][positions][table words]: {0 .. 2^(w-1)} * base, cached-addend form
+    uint32_t* bases;         // [pool index][positions][36]: 2^(w i) * P in extended coordinates (w = the window width of this batch)
+    uint32_t* tables;        // [pool index][positions][table words]: {0 .. 2^(w-1)} * base, cached-addend form
+    uint32_t* pool_of;       // [max_keys] the pool index of a key id; null = the identity (registered key sets: keyset.h)
 };
+// What a slot remembers of its last key-table call, per key column (device memory, allocated beside the pool and sized by its
+// capacity; verify_job.h ensure_key_pool).  ONE open-addressing table whose entries carry the number of the call that put
+// them there, (call << 32) | (pool index + 1): an entry of any other call than the memo's counts as an empty slot, so nothing
+// is cleared between calls and a call that turned the tables down cannot leave two tables out of step (what a pair of
+// tables swapped per call would need).  A hit needs the 64 bytes to be equal; the hash only finds the candidate.
+constexpr uint32_t KT_MEMO_NONE = 0xffffffffu;
+struct key_memo {
+    unsigned long long* hash;// [hash_mask + 1]
+    uint32_t hash_mask;
+    uint32_t cap;            // pool indices the arrays below hold
+    uint32_t* key;           // [cap][16] the key bytes at a pool index
+    uint8_t* flags;          // [cap] KT_KEY_* of that key
+    uint32_t* stamp;         // [cap] the last call that claimed the pool index
+    uint32_t* todo;          // [max_keys] the ids of the keys that missed: these get flags, chains and tables (their number:
+                             // key_params::counters[8 + column])
+    uint32_t* hit;           // [max_keys] the pool index an id was found at, or KT_MEMO_NONE
+    uint32_t* hdr;           // [0] the window width of the tables the memo describes (0: nothing), [1] the call that wrote it
+};
+enum : uint32_t { KT_MEMO_LIVE = 0, KT_MEMO_FLUSH = 1, KT_MEMO_OFF = 2 };
 struct key_params {
     uint32_t n_cols;
     uint32_t max_keys;       // keys per column whose narrow-window tables fit the slot's table pool (also the bound of the ids
@@ -91,7 +116,15 @@ struct key_params {
     key_column col[2];
     uint32_t* counters;      // [c] distinct keys of column c; [2] the decision: 0 = throughput path, else the window width of
                              // the key-table path; [3] a probe sequence overflowed; [4] the keys repeat but their tables do
-                             // not fit the pool (the host grows it for the next call); [5 + c] valid keys of column c
+                             // not fit the pool (the host grows it for the next call); [5 + c] valid keys of column c among
+                             // those that are built; [8 + c] keys of column c that missed the memo; [10 + c] pool indices
+                             // handed to them; [12 + c] keys that hit
+    key_memo memo[2];        // all null: no memo (registered key sets), every key is built and id == pool index
+    uint64_t memo_seed;      // seed of the memo's hash: drawn once per slot
+    uint32_t memo_call;      // number of this call among the slot's key-table calls (never 0)
+    uint32_t memo_mode;      // KT_MEMO_LIVE; KT_MEMO_FLUSH = what the memo says is not to be trusted, every key misses and the memo
+                             // starts afresh; KT_MEMO_OFF = the call neither reads nor writes it (and leaves it empty)
+    uint32_t pool_cap;       // pool indices of a column with narrow windows (with wide ones: max_keys_wide)
     uint32_t force_window;   // profiling build only (0 in the product): KT_WINDOW_NARROW = never the wide windows
     uint32_t keep_order;     // profiling build only (0 in the product): the lanes take the items in the caller's order
     uint64_t n;
@@ -112,8 +145,17 @@ JJS_HD key_column kt_col(const key_params& K, int32_t idx) {
     c.hash = z ? a.hash : b.hash; c.hash_mask = z ? a.hash_mask : b.hash_mask; c.key_bytes = z ? a.key_bytes : b.key_bytes;
     c.rep = z ? a.rep : b.rep; c.keyid = z ? a.keyid : b.keyid; c.key_item = z ? a.key_item : b.key_item;
     c.key_flags = z ? a.key_flags : b.key_flags; c.key_undecodable = z ? a.key_undecodable : b.key_undecodable; c.bases = z ? a.bases : b.bases; c.tables = z ? a.tables : b.tables;
-    c.valid_ids = z ? a.valid_ids : b.valid_ids;
+    c.valid_ids = z ? a.valid_ids : b.valid_ids; c.pool_of = z ? a.pool_of : b.pool_of;
     return c;
+}
+JJS_HD key_memo kt_memo(const key_params& K, int32_t idx) {
+    const key_memo &a = K.memo[0], &b = K.memo[1];
+    const bool z = idx == 0;
+    key_memo m;
+    m.hash = z ? a.hash : b.hash; m.hash_mask = z ? a.hash_mask : b.hash_mask; m.cap = z ? a.cap : b.cap; m.key = z ? a.key : b.key;
+    m.flags = z ? a.flags : b.flags; m.stamp = z ? a.stamp : b.stamp; m.todo = z ? a.todo : b.todo; m.hit = z ? a.hit : b.hit;
+    m.hdr = z ? a.hdr : b.hdr;
+    return m;
 }
 
 // seed: drawn by the host for every call (key_params::seed), so that keys which share a probe sequence cannot be computed
@@ -145,11 +187,14 @@ JJS_HD bool kt_same_key(const fe_src& src, uint64_t a, uint64_t b, uint32_t byte
     return diff == 0;
 }
 
-JJS_HD uint32_t* kt_base(const key_column& C, uint32_t id, uint32_t pos, int w) {
-    return C.bases + ((size_t)id * kt_positions(w) + pos) * KT_BASE_WORDS;
+// where the bases and tables of key `id` lie in the pool
+JJS_HD uint32_t kt_pool(const key_column& C, uint32_t id) { return C.pool_of ? C.pool_of[id] : id; }
+// `p` is a pool index (kt_pool), not a key id
+JJS_HD uint32_t* kt_base(const key_column& C, uint32_t p, uint32_t pos, int w) {
+    return C.bases + ((size_t)p * kt_positions(w) + pos) * KT_BASE_WORDS;
 }
-JJS_HD uint32_t* kt_table(const key_column& C, uint32_t id, uint32_t pos, int w) {
-    return C.tables + ((size_t)id * kt_positions(w) + pos) * kt_table_words(w);
+JJS_HD uint32_t* kt_table(const key_column& C, uint32_t p, uint32_t pos, int w) {
+    return C.tables + ((size_t)p * kt_positions(w) + pos) * kt_table_words(w);
 }
 JJS_HD void kt_store_ext(uint32_t* dst, const ext_pt& p) {
 #pragma unroll
@@ -192,12 +237,13 @@ JJS_HD bool kt_chain_key(const key_column& C, uint32_t id, int w) {
     const bool valid = canonical && point_on_curve_not_identity(pu, pv) && is_torsion_free(pu, pv);
     C.key_flags[id] = (uint8_t)((canonical ? 0u : KT_KEY_MALFORMED) | (valid ? KT_KEY_VALID : 0u));
     ext_pt p = ext_from_affine(pu, pv);
-    kt_store_ext(kt_base(C, id, 0, w), p);
+    const uint32_t pi = kt_pool(C, id);
+    kt_store_ext(kt_base(C, pi, 0, w), p);
     const uint32_t positions = (uint32_t)kt_positions(w);
     for (uint32_t pos = 1; pos < positions; ++pos) {
 #pragma unroll 1
         for (int j = 0; j < w; ++j) p = ext_double(p, j == w - 1);
-        kt_store_ext(kt_base(C, id, pos, w), p);
+        kt_store_ext(kt_base(C, pi, pos, w), p);
     }
     return valid;
 }
@@ -210,13 +256,14 @@ __device__ __forceinline__ void kt_chain_key_quad(const key_column& C, uint32_t 
     const uint64_t item = C.key_item[id];
     const fe_n pu = fq_from_words(load_words(C.src, item)), pv = fq_from_words(load_words(C.src, item, 32));
     ext_pt p = ext_from_affine(pu, pv);
-    if (j == 0) kt_store_ext(kt_base(C, id, 0, w), p);
+    const uint32_t pi = kt_pool(C, id);
+    if (j == 0) kt_store_ext(kt_base(C, pi, 0, w), p);
     const uint32_t positions = (uint32_t)kt_positions(w);
     for (uint32_t pos = 1; pos < positions; ++pos) {
         fe_n own;
 #pragma unroll 1
         for (int k = 0; k < w; ++k) p = ext_double_quad(p, j, own);
-        uint32_t* dst = kt_base(C, id, pos, w) + 9 * j;           // lane j holds coordinate j of the new base
+        uint32_t* dst = kt_base(C, pi, pos, w) + 9 * j;           // lane j holds coordinate j of the new base
 #pragma unroll
         for (int i = 0; i < 9; ++i) dst[i] = own.l[i];
     }
@@ -233,6 +280,80 @@ JJS_HD bool kt_key_flags(const key_column& C, uint32_t id) {
     return valid;
 }
 
+// ---- the memo of the slot's last key-table call (step 5) ---------------------------------------------------
+// The match step runs per distinct key behind the decision, the place step behind it; both are a launch of their own
+// (device_kernels.h key_match_kernel, key_place_kernel), so that whatever one of them reads the other does not write.
+JJS_HD bool kt_memo_same(const key_column& C, uint64_t item, const uint32_t* mk) {
+    const words8 a = load_words(C.src, item), b = load_words(C.src, item, 32);
+    uint32_t diff = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) diff |= (a.w[i] ^ mk[i]) | (b.w[i] ^ mk[8 + i]);
+    return diff == 0;
+}
+// Key `id` against the memo (`live`: the memo describes tables of this call's width and nothing told the host to distrust it).
+// A hit takes over the pool index and the flags and claims the index for this call; running past the probe limit is a miss.
+JJS_HD bool kt_memo_match(const key_column& C, const key_memo& M, uint32_t id, bool live, uint64_t seed, uint32_t call) {
+    uint32_t p = KT_MEMO_NONE;
+    if (live) {
+        const uint64_t item = C.key_item[id];
+        const unsigned long long wrote = M.hdr[1];
+        uint32_t slot = (uint32_t)kt_hash(C.src, item, 64, seed) & M.hash_mask;
+        for (uint32_t probe = 0; probe < KT_MAX_PROBES; ++probe) {
+            const unsigned long long e = M.hash[slot];
+            if ((e >> 32) != wrote || (uint32_t)e == 0u) break;               // an empty slot: the key is not in the memo
+            const uint32_t q = (uint32_t)e - 1u;
+            if (q < M.cap && kt_memo_same(C, item, M.key + (size_t)16 * q)) { p = q; break; }
+            slot = (slot + 1u) & M.hash_mask;
+        }
+    }
+    M.hit[id] = p;
+    if (p == KT_MEMO_NONE) {
+        C.pool_of[id] = id;           // an index inside the pool whatever happens; kt_memo_claim gives the key its own
+        return false;
+    }
+    C.pool_of[id] = p;
+    C.key_flags[id] = M.flags[p];
+    M.stamp[p] = call;
+    return true;
+}
+// a pool index no key of this call holds (hits have stamped theirs before the place step starts)
+JJS_HD bool kt_memo_free(const key_memo& M, uint32_t p, uint32_t call) { return M.stamp[p] != call; }
+// Key `id`, which lies at pool index p, into the hash table as an entry of this call.  Slots that carry another call's
+// number are free.  Past the probe limit the key stays out of the table: the next call misses it and builds it again.
+JJS_HD void kt_memo_insert(const key_column& C, const key_memo& M, uint32_t id, uint32_t p, uint64_t seed, uint32_t call) {
+    const unsigned long long mine = ((unsigned long long)call << 32) | (unsigned long long)(p + 1u);
+    uint32_t slot = (uint32_t)kt_hash(C.src, C.key_item[id], 64, seed) & M.hash_mask;
+    for (uint32_t probe = 0; probe < KT_MAX_PROBES; ++probe) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        unsigned long long e = __atomic_load_n(&M.hash[slot], __ATOMIC_RELAXED);
+        while ((e >> 32) != call) {
+            const unsigned long long seen = atomicCAS(&M.hash[slot], e, mine);
+            if (seen == e) return;
+            e = seen;
+        }
+#else
+        if ((M.hash[slot] >> 32) != call) { M.hash[slot] = mine; return; }
+#endif
+        slot = (slot + 1u) & M.hash_mask;
+    }
+}
+// A key that missed gets the free pool index p: its bytes go into the memo (its flags follow with kt_memo_flags, once
+// `is_valid` has run).
+JJS_HD void kt_memo_claim(const key_column& C, const key_memo& M, uint32_t id, uint32_t p, uint64_t seed, uint32_t call) {
+    const uint64_t item = C.key_item[id];
+    const words8 a = load_words(C.src, item), b = load_words(C.src, item, 32);
+    uint32_t* mk = M.key + (size_t)16 * p;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { mk[i] = a.w[i]; mk[8 + i] = b.w[i]; }
+    M.flags[p] = 0;
+    M.stamp[p] = call;
+    C.pool_of[id] = p;
+    kt_memo_insert(C, M, id, p, seed, call);
+}
+JJS_HD void kt_memo_flags(const key_column& C, const key_memo& M, uint32_t id) {
+    if (M.flags) M.flags[kt_pool(C, id)] = C.key_flags[id];
+}
+
 // table[j] = j * P for j = 0 .. entries-1, P in extended coordinates (the cached-addend entries keep their Z)
 JJS_HD void kt_build_table(uint32_t* tab, const ext_pt& p1, int entries) {
     const niels_pt n1 = to_niels(p1);
@@ -246,7 +367,8 @@ JJS_HD void kt_build_table(uint32_t* tab, const ext_pt& p1, int entries) {
     }
 }
 JJS_HD void kt_table_lane(const key_column& C, uint32_t id, uint32_t pos, int w) {
-    kt_build_table(kt_table(C, id, pos, w), kt_load_ext(kt_base(C, id, pos, w)), kt_entries(w));
+    const uint32_t pi = kt_pool(C, id);
+    kt_build_table(kt_table(C, pi, pos, w), kt_load_ext(kt_base(C, pi, pos, w)), kt_entries(w));
 }
 
 // s + sum_{i < positions-1} 2^(w-1) * 2^(w i): digit i of the sum, minus 2^(w-1), is signed digit i of s; the top
@@ -293,7 +415,8 @@ JJS_HD ext_pt kt_add_digit(const ext_pt& acc, const uint32_t* tab, const words8&
 // acc + s * P for the key `id` of column C, s < 2^252: one addition per position, no doubling.  T of the result is valid.
 JJS_HD ext_pt kt_add_scalar(ext_pt acc, const key_column& C, uint32_t id, const words8& s, int w) {
     const words8 sc = kt_recode(s, w);
-    for (int pos = kt_positions(w) - 1; pos >= 0; --pos) acc = kt_add_digit(acc, kt_table(C, id, (uint32_t)pos, w), sc, pos, w);
+    const uint32_t pi = kt_pool(C, id);            // one 4-byte load per item and column; the items are grouped by key
+    for (int pos = kt_positions(w) - 1; pos >= 0; --pos) acc = kt_add_digit(acc, kt_table(C, pi, (uint32_t)pos, w), sc, pos, w);
     return acc;
 }
 

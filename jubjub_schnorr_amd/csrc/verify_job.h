@@ -55,6 +55,7 @@ void note_key_feedback() {
     sl->seen_pending = false;
     const uint32_t* c = sl->seen->counters;
     sl->keys_repeated = c[2] != 0;
+    if (c[2]) { g->memo_stats[0] += (uint64_t)c[12] + c[13]; g->memo_stats[1] += (uint64_t)c[8] + c[9]; }
     if (c[2] == (uint32_t)KT_WINDOW_WIDE) ++g->stats[JJS_PATH_KEY_TABLES_WIDE];
     else if (c[2] == (uint32_t)KT_WINDOW_NARROW) ++g->stats[JJS_PATH_KEY_TABLES_NARROW];
     else if (c[3]) ++g->stats[JJS_PATH_KEYS_PROBE_LIMIT];
@@ -71,6 +72,22 @@ void note_key_feedback() {
     } else ++g->stats[JJS_PATH_KEYS_DO_NOT_REPEAT];
 }
 
+// One column's share of the memo for `cap` pool indices (key_memo): the header, a hash table of at least two slots per index,
+// the key bytes, and the small per-index and per-id arrays.
+struct memo_layout {
+    size_t hash_slots, hash_bytes, key_bytes, word_bytes, flag_bytes, col_bytes;
+};
+memo_layout key_memo_layout(uint32_t cap) {
+    memo_layout M{};
+    M.hash_slots = 64;
+    while (M.hash_slots < 2 * (size_t)cap) M.hash_slots <<= 1;
+    M.hash_bytes = M.hash_slots * 8;
+    M.key_bytes = pad256((size_t)cap * 64);
+    M.word_bytes = pad256(((size_t)cap + 1) * 4);
+    M.flag_bytes = pad256(cap);
+    M.col_bytes = 256 + M.hash_bytes + M.key_bytes + 4 * M.word_bytes + M.flag_bytes;      // stamp, pool_of, todo, hit
+    return M;
+}
 int ensure_key_index(size_t bytes) {
     if (bytes <= sl->keys_bytes) return JJS_OK;
     const size_t cap = grown(bytes);
@@ -104,9 +121,13 @@ int ensure_key_pool(const verify_params& P) {
     const bool refused = sl->key_pool_refused && want >= sl->key_pool_refused;     // hipMalloc has said no to this much before
     if (sl->key_pool && (want <= sl->key_pool_bytes || refused)) return JJS_OK;
     if (!sl->key_pool && refused) want = first < sl->key_pool_refused ? first : sl->key_pool_refused / 2;
-    uint8_t* fresh = nullptr;
-    if (hipMalloc(&fresh, want) != hipSuccess) {
+    uint8_t *fresh = nullptr, *memo = nullptr;
+    // the memo holds as many pool indices per column as one column has when it owns the whole pool, for either of two columns
+    const uint32_t memo_cap = key_pool_layout(want & ~size_t(255)).cap_narrow;
+    const size_t memo_bytes = 2 * key_memo_layout(memo_cap).col_bytes;
+    if (hipMalloc(&fresh, want) != hipSuccess || hipMalloc(&memo, memo_bytes) != hipSuccess) {
         (void)hipGetLastError();
+        if (fresh) (void)hipFree(fresh);
         sl->key_pool_refused = want;
         ++g->stats[JJS_PATH_KEYS_NO_MEMORY];
         return sl->key_pool ? JJS_OK : fail(JJS_ERR_HIP, "hipMalloc of the key-table pool (%zu bytes) failed", want);
@@ -114,6 +135,11 @@ int ensure_key_pool(const verify_params& P) {
     retire(sl->key_pool, false, sl->key_pool_bytes);        // earlier launches may still read the old pool
     sl->key_pool = fresh;
     sl->key_pool_bytes = want;
+    retire(sl->key_memo, false, sl->key_memo_bytes);
+    sl->key_memo = memo;
+    sl->key_memo_bytes = memo_bytes;
+    sl->memo_cap = memo_cap;
+    sl->memo_flush = sl->memo_dirty = true;
     return JJS_OK;
 }
 
@@ -189,7 +215,21 @@ int carve_keys(const verify_params& P, key_params& K, uint8_t** cleared, size_t*
         C.key_undecodable = q; q += L.flag_bytes;
         C.bases = reinterpret_cast<uint32_t*>(q); q += L.base_bytes;
         C.tables = reinterpret_cast<uint32_t*>(q);
+        const memo_layout ML = key_memo_layout(sl->memo_cap);
+        key_memo& M = K.memo[c];
+        uint8_t* m = sl->key_memo + (size_t)c * ML.col_bytes;
+        M.hdr = reinterpret_cast<uint32_t*>(m); m += 256;
+        M.hash = reinterpret_cast<unsigned long long*>(m); M.hash_mask = (uint32_t)(ML.hash_slots - 1); m += ML.hash_bytes;
+        M.key = reinterpret_cast<uint32_t*>(m); m += ML.key_bytes;
+        M.stamp = reinterpret_cast<uint32_t*>(m); m += ML.word_bytes;
+        C.pool_of = reinterpret_cast<uint32_t*>(m); m += ML.word_bytes;
+        M.todo = reinterpret_cast<uint32_t*>(m); m += ML.word_bytes;
+        M.hit = reinterpret_cast<uint32_t*>(m); m += ML.word_bytes;
+        M.flags = m;
+        M.cap = sl->memo_cap;
     }
+    K.pool_cap = L.cap_narrow;
+    if (L.cap_narrow > sl->memo_cap) return fail(JJS_ERR_HIP, "internal: the key memo is smaller than its pool");
     return JJS_OK;
 }
 // The key buffers of this call, and their clearing on `s`.
@@ -205,6 +245,20 @@ int setup_keys(const verify_params& P, key_params& K, hipStream_t s) {
     size_t cleared_bytes = 0;
     if (int rc = carve_keys(P, K, &cleared, &cleared_bytes)) return rc;
     HIP_TRY(hipMemsetAsync(cleared, 0, cleared_bytes, s));
+    // The memo: trusted when nothing has happened to the pool since the slot's last key-table call and that call laid its
+    // columns out the same way.  What only the device knows -- the window width, whether that call took the tables at all --
+    // is in the memo's header and is checked there (key_match_kernel).  Nothing here waits for the device.
+    if (!sl->memo_seeded) { sl->memo_seed = next_seed(); sl->memo_seeded = true; }
+    K.memo_seed = sl->memo_seed;
+    if (++sl->memo_call == 0) { sl->memo_call = 1; sl->memo_dirty = true; }      // the stamps of 2^32 calls ago must not pass for this call's
+    K.memo_call = sl->memo_call;
+    K.memo_mode = sl->memo_flush || sl->memo_cols != K.n_cols ? KT_MEMO_FLUSH : KT_MEMO_LIVE;
+#if defined(JJS_PROFILING)
+    if (g_force_path || g_force_window || g_keep_order) K.memo_mode = KT_MEMO_FLUSH;      // A/B runs measure a call that builds its tables
+#endif
+    if (sl->memo_dirty) HIP_TRY(hipMemsetAsync(sl->key_memo, 0, sl->key_memo_bytes, s));
+    sl->memo_dirty = sl->memo_flush = false;
+    sl->memo_cols = K.n_cols;
     return JJS_OK;
 }
 
@@ -407,6 +461,8 @@ int job_keys(verify_job& J) {
     // (nor does a host-fed 2^20 call gain from them, although its key kernels end with its hashes: profiles/r04_host_ext_ab.jsonl)
     K.quad_chains = (P.n <= KEYS_AHEAD_MAX_ITEMS || K.n_cols >= 2) ? 1u : 0u;
 #endif
+    // a wire call deduplicates 32-byte encodings, which the memo does not hold: it neither reads nor writes it
+    if (J.C.wire) K.memo_mode = KT_MEMO_OFF;
     J.Kd = K;                                   // a wire call deduplicates the 32-byte encodings
     if (J.C.wire)
         for (uint32_t c = 0; c < K.n_cols; ++c) { J.Kd.col[c].src = J.C.W.comp[c]; J.Kd.col[c].key_bytes = 32; }
@@ -426,6 +482,9 @@ int job_keys(verify_job& J) {
     hipLaunchKernelGGL(key_scan_kernel, dim3(1), dim3(1024), 0, ks, K);
     hipLaunchKernelGGL(key_scatter_kernel, dim3(item_blocks), dim3(BLOCK), 0, ks, K);
     HIP_TRY(hipEventRecord(sl->key_ahead, ks));                // the keys are counted and grouped: see launch_staged
+    // the keys the slot's last call left tables of keep them; the chains and tables below are those of the others
+    hipLaunchKernelGGL(key_match_kernel, dim3(key_blocks), dim3(BLOCK), 0, ks, K);
+    hipLaunchKernelGGL(key_place_kernel, dim3((K.n_cols * (K.pool_cap + K.max_keys) + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ks, K);
     hipLaunchKernelGGL(key_chain_kernel, dim3(((K.quad_chains ? 5 : 1) * K.n_cols * K.max_keys + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ks, K);
     // The tables are throughput work (2 700 waves of 50 k instructions for 4 096 keys).  In a batch whose hashes outlast the
     // key kernels nothing needs them before the hashes have ended: on a stream of the LOWEST priority their blocks are
@@ -522,6 +581,7 @@ int job_finish(verify_job& J) {
 // the caller's stream joins both and the slot's event covers them (the error itself goes back to the caller).
 void job_abandon(verify_job& J) {
     if (!J.open) return;
+    if (J.try_keys) sl->memo_flush = true;          // the memo may name keys whose tables were never queued
     (void)hipGetLastError();
     if (J.forked) {        // the key stream, and the table stream behind it
         if (hipEventRecord(sl->key_chains, sl->key_stream) == hipSuccess && hipStreamWaitEvent(sl->table_stream, sl->key_chains, 0) == hipSuccess &&
