@@ -357,6 +357,47 @@ int jjs_multisig_combine_dev(const void* z, const void* PK, const void* R, const
                              const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
                              void* agg_pk, void* sig_u, void* sig_R, void* stream);
 
+/* ---- multisig signer groups: register the signers once, combine by group ------------------------------------
+ * A committee that signs many messages pays, in the call above, for work that depends on its ordered key vector alone: the n
+ * delinearisation hashes of (2 + 2n) / 4 permutations each, d_i * PK_i, the aggregate key, and a window table of every key
+ * built inside the lane.  jjs_msig_group_create(PK, n, out) does that once (PK: HOST, n x 64 affine, the ordered pk_vec; the
+ * bytes are copied) and keeps on every driven device d_i, aggregate_pk(pk_vec), the tag of the binding hash and the window
+ * tables {0 .. 32} * 2^(6 i) * PK_i of every key: 32 B + 43 x 33 x 144 B = 204 KB per participant.  Blocking; built outside the
+ * engine's mutex on streams of its own and published under it, as jjs_keyset_create.  Points are NOT validated, as in the
+ * reference: the identity, small-order points and repeated keys register.  -1 for n == 0 (the reference's
+ * InvalidMultisigTranscript belongs to the vector: there is no group), for more than 2^24 participants and for a coordinate
+ * >= q (which keeps the per-call statuses defined); -2 when the group's memory cannot be allocated (nothing is left behind).
+ *   jjs_msig_group_combine_dev(g, z, R, S, m, n_transcripts, ...): every transcript has exactly the group's n participants in
+ *     the group's order; share (t, i) is row t n + i of z (B n x 32), R and S (B n x 64 affine); m is B x 32.  Device pointers,
+ *     16-byte aligned, asynchronous on `stream` on the calling thread's current device.  share_status (B n bytes),
+ *     transcript_status (B bytes, nullable), sig_u (B x 32) and sig_R (B x 64) are, byte for byte, what
+ *     jjs_multisig_combine_dev writes for the same transcripts with PK tiled B times and offsets[t] = t n, the zeroed outputs
+ *     of a transcript whose status is not 0 included (the lane computes the same equation, (c d_i mod r) * PK_i over the stored
+ *     tables of PK_i, so this holds for keys with a small-order part as well; for a "key" that is not on the curve neither call
+ *     is defined).  agg_pk is not a per-call output: jjs_msig_group_aggregate_pk(g, out) gives the 64 host bytes every row of
+ *     the inline call's agg_pk holds.  n_transcripts == 0 returns 0 and writes nothing; n_transcripts * n >= 2^32 returns -1.
+ *     Per share the call runs its 1/n part of the binding hash, ONE variable-base multiplication (a * S_i), a comb and one walk
+ *     of 43 additions over the stored tables, against (2 + 2n) / 4 more permutations, three variable-base multiplications and
+ *     a comb inline (12.0-12.7 M shares/s at 8 participants).  These are operation counts; the rates of the group call are
+ *     taken by tools/msig_group_rate.py into profiles/r09_msig_group.jsonl, not by this header.
+ *   jjs_msig_group_destroy(g): the handle becomes stale (-1 from then on); launches already queued still read the group's
+ *     memory, which jjs_trim or jjs_shutdown frees; jjs_trim never frees a live group, jjs_shutdown frees every group.
+ *   jjs_msig_group_info(g, out): JJS_MSIG_GROUP_* words below (the group's memory is reported here, not in jjs_memory_stats).
+ * -4 before jjs_init; -1 for an unknown or destroyed handle.  Every call may come from any thread. */
+typedef uint64_t jjs_msig_group;                  /* 0 is never a valid handle */
+#define JJS_MSIG_GROUP_PARTICIPANTS 0
+#define JJS_MSIG_GROUP_WINDOW_BITS 1
+#define JJS_MSIG_GROUP_DEVICE_BYTES 2             /* per device */
+#define JJS_MSIG_GROUP_CALLS 3                    /* calls served */
+#define JJS_MSIG_GROUP_INFO 4
+int jjs_msig_group_create(const uint8_t* PK, size_t n, jjs_msig_group* out);
+int jjs_msig_group_destroy(jjs_msig_group g);
+int jjs_msig_group_info(jjs_msig_group g, uint64_t out[JJS_MSIG_GROUP_INFO]);
+int jjs_msig_group_aggregate_pk(jjs_msig_group g, uint8_t out[64]);
+int jjs_msig_group_combine_dev(jjs_msig_group g, const void* z, const void* R, const void* S, const void* m,
+                               size_t n_transcripts, void* share_status, void* transcript_status, void* sig_u, void* sig_R,
+                               void* stream);
+
 /* ---- transcript parity (debug export): c_out = n x 32 bytes, the 250-bit challenge per item ---- */
 int jjs_challenge_single_dev(const void* R, const void* PK, const void* m, size_t n, void* c_out, void* stream);
 int jjs_challenge_double_dev(const void* R, const void* R_prime, const void* PK, const void* PK_prime, const void* m,

@@ -23,7 +23,8 @@ int jjs_debug_skip_phases(unsigned mask);
  * point), 2 = the latency path for every single / double call of at most 16 384 items; 0x42 / 0x82 = the
  * latency path with the scalars cut into 4 / 8 pieces whatever the size; 0x500 = 5-bit windows whenever the key
  * tables engage (the product takes 6-bit windows from 128 signatures per key); 0x1000 = the key-table path takes the
- * items in the caller's order instead of grouping them by key; for jjs_verify_all_*: 0x2000 = the verdict algorithm at
+ * items in the caller's order instead of grouping them by key, and so does the share pass of jjs_msig_group_combine_dev
+ * instead of running a wave over the transcripts of one participant; for jjs_verify_all_*: 0x2000 = the verdict algorithm at
  * any size, 0x4000 = the per-item path and its tally at any size, plus (w << 16) = the MSM's window width w (8-16; 0 by
  * size). */
 int jjs_debug_force_path(int which);

@@ -406,4 +406,58 @@ class KeySet {
     std::vector<uint8_t> status_;
 };
 
+// Multisig signer groups (include/jjs_gpu.h jjs_msig_group_*): the ordered key vector of a committee registered once; its
+// delinearisation coefficients, aggregate key and window tables stay on the device.  Move-only; the destructor destroys the
+// group (calls already queued on a stream still complete).
+namespace multisig {
+class SignerGroup {
+  public:
+    // PK: host, n x 64 affine, the ordered pk_vec
+    SignerGroup(const uint8_t* PK, size_t n) : participants_(n) {
+        int rc = jjs_msig_group_create(PK, n, &handle_);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_create");
+        rc = jjs_msig_group_aggregate_pk(handle_, aggregate_pk_.data());
+        if (rc != JJS_OK) { reset(); throw EngineError(rc, "jjs_msig_group_aggregate_pk"); }
+    }
+    explicit SignerGroup(const std::vector<AffinePoint>& keys) : SignerGroup(flat(keys).data(), keys.size()) {}
+    SignerGroup(SignerGroup&& o) noexcept : handle_(o.handle_), participants_(o.participants_), aggregate_pk_(o.aggregate_pk_) { o.handle_ = 0; }
+    SignerGroup& operator=(SignerGroup&& o) noexcept {
+        if (this != &o) { reset(); handle_ = o.handle_; participants_ = o.participants_; aggregate_pk_ = o.aggregate_pk_; o.handle_ = 0; }
+        return *this;
+    }
+    SignerGroup(const SignerGroup&) = delete;
+    SignerGroup& operator=(const SignerGroup&) = delete;
+    ~SignerGroup() { reset(); }
+
+    jjs_msig_group handle() const { return handle_; }
+    size_t participants() const { return participants_; }
+    // aggregate_pk(pk_vec), 64 bytes affine
+    const AffinePoint& aggregate_pk() const { return aggregate_pk_; }
+    std::array<uint64_t, JJS_MSIG_GROUP_INFO> info() const {
+        std::array<uint64_t, JJS_MSIG_GROUP_INFO> out{};
+        int rc = jjs_msig_group_info(handle_, out.data());
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_info");
+        return out;
+    }
+    // device pointers (16-byte aligned), asynchronous on `stream` (a hipStream_t): the columns and outputs of
+    // jjs_msig_group_combine_dev for n_transcripts transcripts of participants() shares each
+    void combine_dev(const void* z, const void* R, const void* S, const void* m, size_t n_transcripts, void* share_status,
+                     void* transcript_status, void* sig_u, void* sig_R, void* stream = nullptr) const {
+        int rc = jjs_msig_group_combine_dev(handle_, z, R, S, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, stream);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_combine_dev");
+    }
+
+  private:
+    static std::vector<uint8_t> flat(const std::vector<AffinePoint>& keys) {
+        std::vector<uint8_t> out(keys.size() * 64);
+        for (size_t i = 0; i < keys.size(); ++i) std::memcpy(out.data() + 64 * i, keys[i].data(), 64);
+        return out;
+    }
+    void reset() { if (handle_) { (void)jjs_msig_group_destroy(handle_); handle_ = 0; } }
+    jjs_msig_group handle_ = 0;
+    size_t participants_ = 0;
+    AffinePoint aggregate_pk_{};
+};
+}  // namespace multisig
+
 }  // namespace jjs

@@ -72,6 +72,11 @@ SIGNATURES = {
     "jjs_keyset_verify_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P],
     "jjs_keyset_verify_all": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_keyset_verify_all_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P],
+    "jjs_msig_group_create": [_P, _Z, _P],
+    "jjs_msig_group_destroy": [ctypes.c_uint64],
+    "jjs_msig_group_info": [ctypes.c_uint64, _P],
+    "jjs_msig_group_aggregate_pk": [ctypes.c_uint64, _P],
+    "jjs_msig_group_combine_dev": [ctypes.c_uint64, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P],
     "jjs_verify_all_single": [_P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_double": [_P, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_vargen": [_P, _P, _P, _P, _P, _Z, _P, _P],

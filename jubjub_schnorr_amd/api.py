@@ -262,6 +262,11 @@ class Engine:
                                                       o(sr), self._stream()), "jjs_multisig_combine_dev")
         return status, agg, su, sr, tstatus
 
+    def multisig_group(self, PK) -> "SignerGroup":
+        """Register the ordered key vector of a committee once (jjs_msig_group_create): its delinearisation coefficients, its
+        aggregate key and the window tables of its keys are built on every driven device and kept until `close()`."""
+        return SignerGroup(self, PK)
+
     def challenge(self, scheme: str, *arrays):
         """250-bit challenge per item (torch CUDA tensors): single (R, PK, m); double (R, R', PK, PK', m);
         vargen (R, PK, Gen, m)."""
@@ -672,6 +677,62 @@ class KeySet:
         if self.handle:
             h, self.handle = self.handle, 0
             _ffi.check(self._lib.jjs_keyset_destroy(h), "jjs_keyset_destroy")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+# ------------------------------------------------------------------------------------------------
+# multisig signer groups (include/jjs_gpu.h jjs_msig_group_*)
+# ------------------------------------------------------------------------------------------------
+class SignerGroup:
+    """The signers of a multisignature registered once (`Engine.multisig_group`); `combine` then takes transcripts of exactly
+    these participants, in this order.  `aggregate_pk`: the 64 bytes of aggregate_pk(pk_vec).  Usable as a context manager;
+    `close()` destroys the group (queued device calls still complete)."""
+    INFO_NAMES = ("participants", "window_bits", "device_bytes", "calls")
+
+    def __init__(self, eng: Engine, PK):
+        self._eng, self._lib = eng, eng._lib
+        pk = eng._host(PK, 64)
+        h = ctypes.c_uint64(0)
+        _ffi.check(self._lib.jjs_msig_group_create(pk.ctypes.data_as(ctypes.c_void_p) if len(pk) else None, len(pk), ctypes.byref(h)),
+                   "jjs_msig_group_create")
+        self.handle = h.value
+        self.participants = len(pk)
+        self.aggregate_pk = np.zeros(64, np.uint8)
+        _ffi.check(self._lib.jjs_msig_group_aggregate_pk(self.handle, self.aggregate_pk.ctypes.data_as(ctypes.c_void_p)),
+                   "jjs_msig_group_aggregate_pk")
+
+    def combine(self, z, R, S, m):
+        """Batch `verify_share` + `combine` over B transcripts of the group's n participants: z (B n, 32), R / S (B n, 64),
+        m (B, 32), torch CUDA uint8, share (t, i) at row t n + i.  Returns (share_status (B n,), sig_u (B, 32), sig_R (B, 64),
+        transcript_status (B,)): the tuple of `Engine.multisig_combine` without agg_pk, byte for byte."""
+        import torch
+        B = m.shape[0]
+        N = B * self.participants
+        dev_ = z.device
+        new = lambda rows, w: torch.empty((max(rows, 1), w), dtype=torch.uint8, device=dev_)[:rows]  # noqa: E731
+        status = torch.empty(max(N, 1), dtype=torch.uint8, device=dev_)[:N]
+        tstatus = torch.empty(max(B, 1), dtype=torch.uint8, device=dev_)[:B]
+        su, sr = new(B, 32), new(B, 64)
+        o = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        d = Engine._dev_ptr
+        _ffi.check(self._lib.jjs_msig_group_combine_dev(self.handle, d(z, 32, N), d(R, 64, N), d(S, 64, N), d(m, 32, B), B, o(status),
+                                                        o(tstatus), o(su), o(sr), Engine._stream()), "jjs_msig_group_combine_dev")
+        return status, su, sr, tstatus
+
+    def info(self) -> dict:
+        out = (ctypes.c_uint64 * len(self.INFO_NAMES))()
+        _ffi.check(self._lib.jjs_msig_group_info(self.handle, out), "jjs_msig_group_info")
+        return dict(zip(self.INFO_NAMES, (int(x) for x in out)))
+
+    def close(self) -> None:
+        h, self.handle = self.handle, 0
+        if h:
+            _ffi.check(self._lib.jjs_msig_group_destroy(h), "jjs_msig_group_destroy")
 
     def __enter__(self):
         return self

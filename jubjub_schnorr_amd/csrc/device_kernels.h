@@ -736,3 +736,41 @@ __global__ __launch_bounds__(BLOCK, 2) void keyset_small_b_kernel(verify_params 
     if (st == ST_PENDING_EQ_FAILED) st = resolve_status(r_ok[2 * item] != 0 && (P.resolve_lanes_keyed < 2 || r_ok[2 * item + 1] != 0), false);
     publish_status(P, item, active && sub == 0, st);
 }
+
+// ---- multisig signer groups (msig_group.h) ---------------------------------------------------------------
+// Registration: the chains of bases (a lane per key) and the window tables (a lane per key and position) of every key, and
+// the aggregate key (one lane: the sum runs in the order of the inline call's pass 2, over the D_j its pass 1 left in dpk).
+__global__ __launch_bounds__(BLOCK, 2) void msig_group_chain_kernel(const uint8_t* PK, uint32_t n, uint32_t* bases) {
+    const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j < n) mg_chain_item(PK, j, bases);
+}
+__global__ __launch_bounds__(BLOCK, 2) void msig_group_table_kernel(const uint32_t* bases, uint32_t* tables, uint32_t n) {
+    const uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t positions = (uint32_t)kt_positions(MG_WINDOW);
+    if (t < (uint64_t)n * positions) mg_table_item(bases, tables, (uint32_t)(t / positions), (uint32_t)(t % positions));
+}
+__global__ void msig_group_agg_kernel(const uint32_t* dpk, uint32_t n, uint8_t* agg_pk) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) store_point(agg_pk, 0, sum_points_affine(dpk, 0, n));
+}
+// The passes of a call but the share pass: 0 binding hash, 1 commitments, 2 RSa + c + u, 4 verdicts (msig_kernel's lane rules)
+__global__ __launch_bounds__(BLOCK) void msig_group_kernel(msig_group_params G, int pass) {
+    const uint64_t gtid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    uint32_t* ws = G.M.lane_ws + gtid * WS_WORDS_PER_LANE;
+    const uint64_t count = pass == 1 ? G.M.n_total : G.M.n_transcripts;
+    const uint32_t hl = (pass == 0 || pass == 2) ? G.M.hash_lanes : 1u;
+    const int coop = hl > 1 ? (int)(gtid % hl) : -1;
+    for (uint64_t i = gtid / hl; i < count; i += total / hl) {
+        switch (pass) {
+        case 0: mg_binding_item(G, (uint32_t)i, coop); break;
+        case 1: mg_commit_item(G, i, ws); break;
+        case 2: mg_final_item(G, (uint32_t)i, coop); break;
+        default: mg_verdict_item(G, (uint32_t)i); break;
+        }
+    }
+}
+// pass 3: a comb and a walk over the group's tables per share; no workspace
+__global__ __launch_bounds__(BLOCK, 2) void msig_group_share_kernel(msig_group_params G) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t k = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; k < G.M.n_total; k += total) mg_share_item(G, mg_share_of_lane(G, k));
+}

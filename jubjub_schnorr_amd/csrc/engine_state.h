@@ -330,8 +330,27 @@ struct keyset_entry {
     std::vector<keyset_copy> copies;       // one per device of L.devs, in that order
     uint64_t small_calls = 0, large_calls = 0;
 };
+// Multisig signer groups (msig_group.h; jjs_msig_group_*): immutable once built, one copy per driven device, handles and
+// lifetime as for key sets (the generation counter is shared with them, so no handle of one kind is a handle of the other).
+struct msig_group_copy {
+    device_state* dev = nullptr;
+    uint8_t* mem = nullptr;                // one allocation: the regions below
+    size_t bytes = 0;
+    uint8_t* agg_pk = nullptr;             // 64 B affine
+    uint32_t* tag_a = nullptr;             // [2][9]: the tags of the delinearisation hash (registration only) and of the binding hash
+    uint32_t* d_words = nullptr;           // [n][8]
+    uint32_t* tables = nullptr;            // [n][positions][table words]
+};
+struct msig_group_entry {
+    uint32_t generation = 0;
+    uint32_t participants = 0;
+    uint8_t agg_pk[64] = {};
+    std::vector<msig_group_copy> copies;   // one per device of L.devs, in that order
+    uint64_t calls = 0;
+};
 library_state L;
 std::vector<std::unique_ptr<keyset_entry>> g_keysets;   // the registry (under L.mu)
+std::vector<std::unique_ptr<msig_group_entry>> g_msig_groups;   // ... and the signer groups' (under L.mu)
 uint32_t g_keyset_generation = 0;                       // never reset: a handle from before jjs_shutdown stays stale
 uint32_t g_keyset_host_calls = 0;                       // host-buffer keyset calls between their first and last use of L.mu:
                                                         // jjs_shutdown waits for them before it frees a device (under L.mu)

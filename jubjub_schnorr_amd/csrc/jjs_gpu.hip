@@ -58,6 +58,7 @@
 #include "keyset.h"
 #include "sign_core.h"
 #include "multisig_core.h"
+#include "msig_group.h"
 #include "batch_verdict.h"
 #include "keyset_verdict.h"
 #include "jjs_sponge_tags_long.inc"
@@ -289,6 +290,11 @@ void retire_keyset(keyset_entry& k) {      // under L.mu; the devices of its cop
     for (keyset_copy& c : k.copies) { g = c.dev; retire(c.mem, false, c.bytes); c.mem = nullptr; }
     g = keep;
 }
+void retire_msig_group(msig_group_entry& k) {      // the same for a signer group
+    device_state* const keep = g;
+    for (msig_group_copy& c : k.copies) { g = c.dev; retire(c.mem, false, c.bytes); c.mem = nullptr; }
+    g = keep;
+}
 
 void shutdown_locked() {
     int prev = -1;
@@ -296,6 +302,9 @@ void shutdown_locked() {
     for (std::unique_ptr<keyset_entry>& k : g_keysets)       // freed with the other retired buffers by free_device
         if (k) retire_keyset(*k);
     g_keysets.clear();
+    for (std::unique_ptr<msig_group_entry>& k : g_msig_groups)
+        if (k) retire_msig_group(*k);
+    g_msig_groups.clear();
     for (device_state* d : L.devs)
         if (d->stream) { (void)hipSetDevice(d->device); (void)hipStreamSynchronize(d->stream); }
     if (L.comms_up) {
@@ -874,6 +883,20 @@ int jjs_compress_dev(const void* affine, size_t n, void* out, void* stream) {
 }
 
 // ---- multisig: batch verify_share / combine -------------------------------------------
+// the device's multisignature scratch (grow-only), for n shares in n_transcripts transcripts: tr_of, d_words, dpk, e_pt per
+// share; a_words, c_words, the offsets and the long tags per transcript
+static int ensure_msig_scratch(size_t n, size_t n_transcripts) {
+    if (n <= g->msig_items && n_transcripts <= g->msig_transcripts) return JJS_OK;
+    size_t ci = grown(n < 4096 ? 4096 : n), ct = grown(n_transcripts < 1024 ? 1024 : n_transcripts);
+    if (ci < g->msig_items) ci = g->msig_items;
+    if (ct < g->msig_transcripts) ct = g->msig_transcripts;
+    uint8_t* fresh = nullptr;
+    HIP_TRY(hipMalloc(&fresh, ci * 4 * (1 + 8 + 2 * EXT_WORDS) + ct * 4 * (16 + 1 + 18) + 64));
+    retire(g->msig, false, g->msig_items * 4 * (1 + 8 + 2 * EXT_WORDS) + g->msig_transcripts * 4 * (16 + 1 + 18) + 64);
+    g->msig = fresh;
+    g->msig_items = ci; g->msig_transcripts = ct;
+    return JJS_OK;
+}
 int jjs_multisig_combine_dev(const void* z, const void* PK, const void* R, const void* S, const void* m,
                              const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
                              void* agg_pk, void* sig_u, void* sig_R, void* stream) {
@@ -894,16 +917,7 @@ int jjs_multisig_combine_dev(const void* z, const void* PK, const void* R, const
     const size_t n = offsets_host[n_transcripts];
     if ((n && !all_ok(z, PK, R, S)) || !all_ok(m, agg_pk, sig_u, sig_R) || (n && !share_status)) return fail(JJS_ERR_ARG, "null or misaligned pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (n > g->msig_items || n_transcripts > g->msig_transcripts) {
-        size_t ci = grown(n < 4096 ? 4096 : n), ct = grown(n_transcripts < 1024 ? 1024 : n_transcripts);
-        if (ci < g->msig_items) ci = g->msig_items;
-        if (ct < g->msig_transcripts) ct = g->msig_transcripts;
-        uint8_t* fresh = nullptr;
-        HIP_TRY(hipMalloc(&fresh, ci * 4 * (1 + 8 + 2 * EXT_WORDS) + ct * 4 * (16 + 1 + 18) + 64));
-        retire(g->msig, false, g->msig_items * 4 * (1 + 8 + 2 * EXT_WORDS) + g->msig_transcripts * 4 * (16 + 1 + 18) + 64);
-        g->msig = fresh;
-        g->msig_items = ci; g->msig_transcripts = ct;
-    }
+    if (int rc = ensure_msig_scratch(n, n_transcripts)) return rc;
     msig_params P{};
     P.z = (const uint8_t*)z; P.PK = (const uint8_t*)PK; P.R = (const uint8_t*)R; P.S = (const uint8_t*)S; P.m = (const uint8_t*)m;
     P.n_transcripts = (uint32_t)n_transcripts; P.n_total = n;
@@ -939,6 +953,8 @@ int jjs_multisig_combine_dev(const void* z, const void* PK, const void* R, const
     const int rc2 = end_shared(s);              // the slot's event covers whatever was queued, also when a step failed
     return rc ? rc : rc2;
 }
+
+#include "msig_group_calls.h"
 
 // ---- challenge export ---------------------------------------------------------------------------
 static int launch_challenge(challenge_params P, void* stream) {

@@ -91,15 +91,13 @@ JJS_HD affine_words sum_points_affine(const uint32_t* pts, uint32_t lo, uint32_t
     for (uint32_t i = lo; i < hi; ++i) acc = ext_add_niels(acc, to_niels(load_ext(pts + (size_t)EXT_WORDS * i)), false, true);
     return to_affine_words(acc);
 }
-// pass 2 (lane per transcript): pk_agg = sum D_i;  a = H(pk_agg, m, R_lo, S_lo, ...)
-JJS_HD void msig_agg_item(const msig_params& P, uint32_t t, int coop = -1) {
-    const uint32_t lo = P.offsets[t], hi = P.offsets[t + 1];
-    const affine_words agg = sum_points_affine(P.dpk, lo, hi);
-    store_point(P.agg_pk, t, agg);
+// a = H(pk_agg, m, R_lo, S_lo, ...) of transcript t = participants [lo, hi), with the aggregate key at row `agg_row` of `agg`
+JJS_HD void msig_binding_hash(const msig_params& P, uint32_t t, uint64_t lo, uint64_t hi, const fe_n& tag, const uint8_t* agg, uint64_t agg_row,
+                              int coop) {
     const int n_in = 3 + 4 * (int)(hi - lo);
-    const fe_src aggs{P.agg_pk, 64, 0}, ms{P.m, 32, 0}, rs{P.R, 64, 0}, ss{P.S, 64, 0};
-    fe_n dg = poseidon_digest_tagged(n_in, msig_tag(P, t, hi - lo, 1, n_in), [&](int e) {
-        if (e < 2) return load_fq(aggs, t, 32u * (uint32_t)e);
+    const fe_src aggs{agg, 64, 0}, ms{P.m, 32, 0}, rs{P.R, 64, 0}, ss{P.S, 64, 0};
+    fe_n dg = poseidon_digest_tagged(n_in, tag, [&](int e) {
+        if (e < 2) return load_fq(aggs, agg_row, 32u * (uint32_t)e);
         if (e == 2) return load_fq(ms, t);
         const int k = e - 3;                     // R_i.u, R_i.v, S_i.u, S_i.v per participant
         const uint64_t idx = lo + (uint64_t)(k >> 2);
@@ -107,23 +105,30 @@ JJS_HD void msig_agg_item(const msig_params& P, uint32_t t, int coop = -1) {
     }, coop);
     store_w8(P.a_words + 8 * t, truncate250(dg));
 }
+// pass 2 (lane per transcript): pk_agg = sum D_i;  a = H(pk_agg, m, R_lo, S_lo, ...)
+JJS_HD void msig_agg_item(const msig_params& P, uint32_t t, int coop = -1) {
+    const uint32_t lo = P.offsets[t], hi = P.offsets[t + 1];
+    const affine_words agg = sum_points_affine(P.dpk, lo, hi);
+    store_point(P.agg_pk, t, agg);
+    msig_binding_hash(P, t, lo, hi, msig_tag(P, t, hi - lo, 1, 3 + 4 * (int)(hi - lo)), P.agg_pk, t, coop);
+}
 // pass 3 (lane per participant): E_i = R_i + a * S_i
-JJS_HD void msig_commit_item(const msig_params& P, uint64_t i, uint32_t* ws) {
-    const uint32_t t = P.tr_of[i];
+JJS_HD void msig_commit_share(const msig_params& P, uint64_t i, uint32_t t, uint32_t* ws) {
     const fe_src rs{P.R, 64, 0}, ss{P.S, 64, 0};
     build_point_table(ws, load_fq(ss, i), load_fq(ss, i, 32));
     ext_pt as = table_mul(ws, load_w8(P.a_words + 8 * t), true);
     ext_pt r = ext_from_affine(load_fq(rs, i), load_fq(rs, i, 32));
     store_ext(P.e_pt + EXT_WORDS * i, ext_add_niels(as, to_niels(r), false, true));
 }
+JJS_HD void msig_commit_item(const msig_params& P, uint64_t i, uint32_t* ws) { msig_commit_share(P, i, P.tr_of[i], ws); }
 // pass 4 (lane per transcript): RSa = sum E_i, c = H(RSa, pk_agg, m), u = sum z_i
-JJS_HD void msig_final_item(const msig_params& P, uint32_t t, int coop = -1) {
-    const uint32_t lo = P.offsets[t], hi = P.offsets[t + 1];
+// (transcript t = participants [lo, hi), its aggregate key at row `agg_row` of `agg`)
+JJS_HD void msig_final_range(const msig_params& P, uint32_t t, uint32_t lo, uint32_t hi, const uint8_t* agg, uint64_t agg_row, int coop) {
     const affine_words rsa = sum_points_affine(P.e_pt, lo, hi);
     store_point(P.sig_R, t, rsa);
-    const fe_src sr{P.sig_R, 64, 0}, aggs{P.agg_pk, 64, 0}, ms{P.m, 32, 0}, zs{P.z, 32, 0};
+    const fe_src sr{P.sig_R, 64, 0}, aggs{agg, 64, 0}, ms{P.m, 32, 0}, zs{P.z, 32, 0};
     fe_n dg = poseidon_digest(5, [&](int e) {
-        return e < 2 ? load_fq(sr, t, 32u * (uint32_t)e) : (e < 4 ? load_fq(aggs, t, 32u * (uint32_t)(e - 2)) : load_fq(ms, t));
+        return e < 2 ? load_fq(sr, t, 32u * (uint32_t)e) : (e < 4 ? load_fq(aggs, agg_row, 32u * (uint32_t)(e - 2)) : load_fq(ms, t));
     }, coop);
     store_w8(P.c_words + 8 * t, truncate250(dg));
     // u = sum z_i mod r
@@ -138,6 +143,9 @@ JJS_HD void msig_final_item(const msig_params& P, uint32_t t, int coop = -1) {
         u = select_words(borrow != 0, s, d);      // both addends < r < 2^252: no carry out of 256 bits
     }
     store_words(P.sig_u, t, u);
+}
+JJS_HD void msig_final_item(const msig_params& P, uint32_t t, int coop = -1) {
+    msig_final_range(P, t, P.offsets[t], P.offsets[t + 1], P.agg_pk, t, coop);
 }
 // pass 5 (lane per participant): z_i*G + (c*d_i)*PK_i == E_i
 JJS_HD void msig_share_item(const msig_params& P, uint64_t i, uint32_t* ws) {
@@ -165,20 +173,24 @@ JJS_HD void msig_share_item(const msig_params& P, uint64_t i, uint32_t* ws) {
 // outputs are cleared so that a caller who ignores the statuses cannot pick up an aggregate built from bad shares.
 // A transcript without participants is the reference's InvalidMultisigTranscript (src/multisig.rs:332-338): status 5 for
 // that transcript alone, nothing out (its aggregate key is cleared as well).
-JJS_HD void msig_verdict_item(const msig_params& P, uint32_t t) {
-    uint32_t st = ST_OK;
-    for (uint32_t i = P.offsets[t + 1]; i-- > P.offsets[t];) st = P.share_status[i] ? P.share_status[i] : st;
-    if (P.offsets[t + 1] == P.offsets[t]) {
-        st = ST_INVALID_TRANSCRIPT;
-        store_words(P.agg_pk, 2 * (uint64_t)t, small_words(0));
-        store_words(P.agg_pk, 2 * (uint64_t)t + 1, small_words(0));
-    }
+// (a transcript with participants [lo, hi), hi > lo)
+JJS_HD void msig_verdict_range(const msig_params& P, uint32_t t, uint32_t lo, uint32_t hi, uint32_t st = ST_OK) {
+    for (uint32_t i = hi; i-- > lo;) st = P.share_status[i] ? P.share_status[i] : st;
     if (P.transcript_status) P.transcript_status[t] = (uint8_t)st;
     if (st != ST_OK) {
         store_words(P.sig_u, t, small_words(0));
         store_words(P.sig_R, 2 * (uint64_t)t, small_words(0));
         store_words(P.sig_R, 2 * (uint64_t)t + 1, small_words(0));
     }
+}
+JJS_HD void msig_verdict_item(const msig_params& P, uint32_t t) {
+    uint32_t st = ST_OK;
+    if (P.offsets[t + 1] == P.offsets[t]) {
+        st = ST_INVALID_TRANSCRIPT;
+        store_words(P.agg_pk, 2 * (uint64_t)t, small_words(0));
+        store_words(P.agg_pk, 2 * (uint64_t)t + 1, small_words(0));
+    }
+    msig_verdict_range(P, t, P.offsets[t], P.offsets[t + 1], st);
 }
 
 }  // namespace jjs
