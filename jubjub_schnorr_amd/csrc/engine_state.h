@@ -307,60 +307,7 @@ struct library_state {
     bool comms_up = false;
 };
 
-// Registered key sets (keyset.h; jjs_keyset_*).  A set is immutable once built and has one copy per driven device: its
-// affine keys (64 B per point, the challenge hash reads them), the flags of its points, their window tables (KEYSET_WINDOW bits)
-// and three device words (n_keys, n_keys, the window width: the counters the grouping kernels read, and the key-table flag
-// of verify_params).  Handles are (generation << 32) | (registry index + 1): a destroyed set's index may be reused, its
-// generation never is, so a stale handle finds nothing (JJS_ERR_ARG) and never reaches freed memory.  The registry is only
-// read or changed under the engine's mutex; a destroyed set's device memory is retired (retire()), so that launches already
-// queued on a stream still read valid tables, and freed by jjs_trim / jjs_shutdown.
-struct keyset_copy {
-    device_state* dev = nullptr;
-    uint8_t* mem = nullptr;                // one allocation: the regions below
-    size_t bytes = 0;
-    uint8_t* keys[2] = {};                 // n_keys x 64 affine, per point column
-    uint8_t* flags[2] = {};                // n_keys KT_KEY_* flags, per point column
-    uint32_t* tables[2] = {};              // n_keys x kt_positions(w) x kt_table_words(w), per point column
-    uint32_t* words = nullptr;             // [0], [1] n_keys, [2] the window width
-};
-struct keyset_entry {
-    uint32_t generation = 0;
-    int scheme = 0;
-    uint32_t n_keys = 0, n_cols = 0, valid = 0;
-    std::vector<keyset_copy> copies;       // one per device of L.devs, in that order
-    uint64_t small_calls = 0, large_calls = 0;
-};
-// Multisig signer groups (msig_group.h; jjs_msig_group_*): immutable once built, one copy per driven device, handles and
-// lifetime as for key sets (the generation counter is shared with them, so no handle of one kind is a handle of the other).
-struct msig_group_copy {
-    device_state* dev = nullptr;
-    uint8_t* mem = nullptr;                // one allocation: the regions below
-    size_t bytes = 0;
-    uint8_t* agg_pk = nullptr;             // 64 B affine
-    uint32_t* tag_a = nullptr;             // [2][9]: the tags of the delinearisation hash (registration only) and of the binding hash
-    uint32_t* d_words = nullptr;           // [n][8]
-    uint32_t* tables = nullptr;            // [n][positions][table words]
-};
-struct msig_group_entry {
-    uint32_t generation = 0;
-    uint32_t participants = 0;
-    uint8_t agg_pk[64] = {};
-    std::vector<msig_group_copy> copies;   // one per device of L.devs, in that order
-    uint64_t calls = 0;
-};
 library_state L;
-std::vector<std::unique_ptr<keyset_entry>> g_keysets;   // the registry (under L.mu)
-std::vector<std::unique_ptr<msig_group_entry>> g_msig_groups;   // ... and the signer groups' (under L.mu)
-uint32_t g_keyset_generation = 0;                       // never reset: a handle from before jjs_shutdown stays stale
-uint32_t g_keyset_host_calls = 0;                       // host-buffer keyset calls between their first and last use of L.mu:
-                                                        // jjs_shutdown waits for them before it frees a device (under L.mu)
-struct keyset_host_call_leave {                         // ... the way out of such a call, on every path
-    ~keyset_host_call_leave() {
-        std::lock_guard<std::mutex> lock(L.mu);
-        --g_keyset_host_calls;
-        L.lane_cv.notify_all();
-    }
-};
 // Device bound to the work in progress on THIS host thread: set by check_ready for an entry point and by each
 // per-device worker of run_host for its own block (the workers run concurrently, one device each).
 thread_local device_state* g = nullptr;
@@ -395,6 +342,7 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 // SIMD: a transcript's sponge is ONE chain of (3 + 4 n) / 4 permutations, and eight lanes run a permutation in 0.12 ms instead
 // of 0.25 (hades29.h, coop).  Beyond, the passes are throughput-bound and eight lanes per item would be eight times the work.
 constexpr size_t MSIG_COOP_MAX_ITEMS = 8192;
+constexpr uint32_t msig_hash_lanes(size_t count) { return count <= MSIG_COOP_MAX_ITEMS ? 8u : 1u; }      // of a pass that hashes, over `count` items
 int grid_for(int resident, size_t n) {
     size_t want = (n + BLOCK - 1) / BLOCK;
     if (want < 1) want = 1;
@@ -487,6 +435,104 @@ int regrow(T*& buf, size_t& have, size_t old_bytes, size_t want_units, size_t by
     have = want_units;
     return JJS_OK;
 }
+
+// Registered objects: key sets (keyset.h; jjs_keyset_*) and multisig signer groups (msig_group.h; jjs_msig_group_*).  An object
+// is immutable once built and has one copy per driven device.  Handles are (generation << 32) | (registry index + 1): a
+// destroyed object's index may be reused, its generation never is, so a stale handle finds nothing (JJS_ERR_ARG) and never
+// reaches freed memory -- and the generation counter is ONE for every kind, so a handle of one kind is no handle of another.
+// A registry is only read or changed under the engine's mutex; a destroyed object's device memory is retired (retire()), so
+// that launches already queued on a stream still read valid tables, and freed by jjs_trim / jjs_shutdown.
+struct device_copy {
+    device_state* dev = nullptr;
+    uint8_t* mem = nullptr;                // one allocation: the regions its owner carves from it
+    size_t bytes = 0;
+};
+template <class Copy>
+struct registered {
+    uint32_t generation = 0;
+    std::vector<Copy> copies;              // one per device of L.devs, in that order
+};
+uint32_t g_object_generation = 0;          // registered-object generation: never reset (a handle from before jjs_shutdown stays stale), never 0
+template <class Entry>
+struct registry {                          // every member: under L.mu
+    std::vector<std::unique_ptr<Entry>> entries;
+    Entry* find(uint64_t h) const {
+        const uint32_t idx = (uint32_t)(h & 0xffffffffu), gen = (uint32_t)(h >> 32);
+        if (idx == 0 || idx > entries.size()) return nullptr;
+        Entry* e = entries[idx - 1].get();
+        return e && e->generation == gen ? e : nullptr;
+    }
+    uint64_t publish(std::unique_ptr<Entry>& e) {     // takes `e` once its slot exists: if this throws, the caller still owns it
+        size_t slot = 0;
+        while (slot < entries.size() && entries[slot]) ++slot;
+        if (slot == entries.size()) entries.emplace_back();
+        if (++g_object_generation == 0) ++g_object_generation;       // 0 is never a generation: no valid handle is 0
+        e->generation = g_object_generation;
+        entries[slot] = std::move(e);
+        return ((uint64_t)g_object_generation << 32) | (uint64_t)(slot + 1);
+    }
+    static void retire_copies(Entry& e) {             // the devices of its copies are alive
+        device_state* const keep = g;
+        for (auto& c : e.copies) { g = c.dev; retire(c.mem, false, c.bytes); c.mem = nullptr; }
+        g = keep;
+    }
+    bool destroy(uint64_t h) {             // launches already queued still read it: freed by jjs_trim / jjs_shutdown
+        Entry* e = find(h);
+        if (!e) return false;
+        retire_copies(*e);
+        entries[(h & 0xffffffffu) - 1].reset();
+        return true;
+    }
+    void retire_all() {                    // jjs_shutdown: freed with the other retired buffers by free_device
+        for (std::unique_ptr<Entry>& e : entries)
+            if (e) retire_copies(*e);
+        entries.clear();
+    }
+};
+template <class Entry>
+auto copy_for(const Entry& e, const device_state* d) -> decltype(&e.copies[0]) {
+    for (const auto& c : e.copies)
+        if (c.dev == d) return &c;
+    return nullptr;
+}
+// A set's copy: its affine keys (64 B per point, the challenge hash reads them), the flags of its points, their window tables
+// (KEYSET_WINDOW bits) and three device words (n_keys, n_keys, the window width: the counters the grouping kernels read, and
+// the key-table flag of verify_params).
+struct keyset_copy : device_copy {
+    uint8_t* keys[2] = {};                 // n_keys x 64 affine, per point column
+    uint8_t* flags[2] = {};                // n_keys KT_KEY_* flags, per point column
+    uint32_t* tables[2] = {};              // n_keys x kt_positions(w) x kt_table_words(w), per point column
+    uint32_t* words = nullptr;             // [0], [1] n_keys, [2] the window width
+};
+struct keyset_entry : registered<keyset_copy> {
+    int scheme = 0;
+    uint32_t n_keys = 0, n_cols = 0, valid = 0;
+    uint64_t small_calls = 0, large_calls = 0;
+};
+struct msig_group_copy : device_copy {
+    uint8_t* agg_pk = nullptr;             // 64 B affine
+    uint32_t* tag_a = nullptr;             // [2][9]: the tags of the delinearisation hash (registration only) and of the binding hash
+    uint32_t* d_words = nullptr;           // [n][8]
+    uint32_t* tables = nullptr;            // [n][positions][table words]
+};
+struct msig_group_entry : registered<msig_group_copy> {
+    uint32_t participants = 0;
+    uint8_t agg_pk[64] = {};
+    uint64_t calls = 0;
+};
+registry<keyset_entry> g_keysets;
+registry<msig_group_entry> g_msig_groups;
+// Blocking calls that hold a device pointer outside L.mu, between their first and last use of the mutex (the create calls, the
+// host-buffer calls against a key set, the verdict algorithm's host route): jjs_shutdown waits for them before it frees a
+// device.  Counted in under L.mu ...
+uint32_t g_blocking_calls = 0;
+struct blocking_call_leave {               // ... and out here, on every path
+    ~blocking_call_leave() {
+        std::lock_guard<std::mutex> lock(L.mu);
+        --g_blocking_calls;
+        L.lane_cv.notify_all();
+    }
+};
 
 int ensure_pending(size_t n) {
     if (n <= sl->pending_items) return JJS_OK;

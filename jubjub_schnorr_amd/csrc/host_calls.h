@@ -217,13 +217,19 @@ void stage_slice(void* ctx, unsigned t) {
     }
 }
 
-// Builds the call of one block from its device arrays (cols[k] of the block at dev[k]; nl items; statuses to st,
-// counters to tl): what the *_locked functions below do for a resident call, minus the launch.
-typedef int (*call_builder)(const void* const* dev, size_t nl, void* st, void* tl, hipStream_t s, staged_call& out);
+// The two upload plans of a block of nl items of shape S (plan_pieces), and the largest piece of either.
+void plan_block(const call_shape& S, size_t nl, std::vector<host_piece> plans[2], size_t& largest_bytes) {
+    size_t row_keys = 0, row_rest = 0, row_late = 0;
+    for (size_t k = 0; k < S.n_cols; ++k)
+        (S.col[k].group == COLS_KEYS ? row_keys : S.col[k].group == COLS_LATE ? row_late : row_rest) += S.col[k].width;
+    plan_pieces(plans[0], largest_bytes, nl, row_keys, row_rest, row_late, S.wire_points, false);
+    plan_pieces(plans[1], largest_bytes, nl, row_keys, row_rest, row_late, S.wire_points, true);
+}
 
-// The pipeline of one device's block; runs on the calling thread (one device) or on a thread of its own.
-int run_host_block(device_state* dev, const host_col* cols, size_t n_cols, host_block& b, uint8_t* status, call_builder build,
-                   verify_job& J) {
+// The pipeline of one device's block (cols: the caller's columns, in the order and with the widths and groups of S); runs on
+// the calling thread (one device) or on a thread of its own.
+int run_host_block(device_state* dev, const call_shape& S, const host_col* cols, host_block& b, uint8_t* status, verify_job& J) {
+    const size_t n_cols = S.n_cols;
     g = dev;
 #if defined(JJS_PROFILING)
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -261,7 +267,7 @@ int run_host_block(device_state* dev, const host_col* cols, size_t n_cols, host_
         // the builder picks the call slot (the engine's state): under the engine's mutex when this call does not hold it anyway
         std::unique_lock<std::mutex> lock(L.mu, std::defer_lock);
         if (b.unlocked) lock.lock();
-        if (int rc = build(in, nl, st, g->tally, g->stream, J.C)) return rc;
+        if (int rc = build_call(S, in, nl, st, g->tally, g->stream, J.C)) return rc;
         if (b.unlocked) { sl->host_owned = true; b.owned = sl; }
     }
     bool late = false;
@@ -442,27 +448,24 @@ int run_host_block(device_state* dev, const host_col* cols, size_t n_cols, host_
     return JJS_OK;
 }
 
-// jjs_reserve: the device arena and the pinned staging a block of nl items with these columns needs (current device)
-int reserve_host_block(const host_col* cols, size_t n_cols, size_t nl, int wire_points) {
-    size_t row_keys = 0, row_rest = 0, row_late = 0, bytes = 0, largest = 256;
-    for (size_t k = 0; k < n_cols; ++k) {
-        (cols[k].group == COLS_KEYS ? row_keys : cols[k].group == COLS_LATE ? row_late : row_rest) += cols[k].width;
-        bytes += pad256(nl * cols[k].width);
-    }
-    std::vector<host_piece> plan;
-    plan_pieces(plan, largest, nl, row_keys, row_rest, row_late, wire_points, false);
-    plan_pieces(plan, largest, nl, row_keys, row_rest, row_late, wire_points, true);
+// jjs_reserve: the device arena and the pinned staging a block of nl items of shape S needs (current device)
+int reserve_host_block(const call_shape& S, size_t nl) {
+    size_t bytes = 0, largest = 256;
+    for (size_t k = 0; k < S.n_cols; ++k) bytes += pad256(nl * S.col[k].width);
+    std::vector<host_piece> plans[2];
+    plan_block(S, nl, plans, largest);
     if (int rc = ensure_stage(bytes + pad256(nl))) return rc;
     return ensure_pinned(HOST_SLOTS * pad256(largest) + pad256(nl) + 256);
 }
 
 // `unlocked`: the caller does NOT hold the engine's mutex (one driven device: the call holds that device's host_mu instead, so
 // that calls of other threads -- resident ones, and host-buffer calls on the lanes -- are queued while this one uploads and waits)
-int run_host(const host_col* cols, size_t n_cols, size_t n, uint8_t* status, uint64_t tally[4], call_builder build, int wire_points,
-             bool unlocked = false) {
-    if (n_cols > 8) return fail(JJS_ERR_ARG, "internal: too many columns");
-    for (size_t k = 0; k < n_cols; ++k)
-        if (n && !cols[k].p) return fail(JJS_ERR_ARG, "null input pointer");
+int run_host(const call_shape& S, const uint8_t* const* ptrs, size_t n, uint8_t* status, uint64_t tally[4], bool unlocked = false) {
+    host_col cols[8];
+    for (size_t k = 0; k < S.n_cols; ++k) {
+        if (n && !ptrs[k]) return fail(JJS_ERR_ARG, "null input pointer");
+        cols[k] = host_col{ptrs[k], S.col[k].width, S.col[k].group};
+    }
     std::vector<device_state*> targets;
     if (L.devs.size() == 1) targets.push_back(g); else targets = L.devs;
     const size_t nd = targets.size();
@@ -479,23 +482,19 @@ int run_host(const host_col* cols, size_t n_cols, size_t n, uint8_t* status, uin
         if (staging_threads > HOST_STAGING_THREADS_MAX) staging_threads = HOST_STAGING_THREADS_MAX;
         if (staging_threads < 1) staging_threads = 1;
     }
-    size_t row_keys = 0, row_rest = 0, row_late = 0;
-    for (size_t k = 0; k < n_cols; ++k)
-        (cols[k].group == COLS_KEYS ? row_keys : cols[k].group == COLS_LATE ? row_late : row_rest) += cols[k].width;
     for (size_t d = 0; d < nd; ++d) {
         host_block& b = blocks[d];
         b.lo = d * per < n ? d * per : n;
         b.hi = b.lo + per < n ? b.lo + per : n;
         b.largest_bytes = 256;
-        plan_pieces(b.plans[0], b.largest_bytes, b.hi - b.lo, row_keys, row_rest, row_late, wire_points, false);
-        plan_pieces(b.plans[1], b.largest_bytes, b.hi - b.lo, row_keys, row_rest, row_late, wire_points, true);
+        plan_block(S, b.hi - b.lo, b.plans, b.largest_bytes);
         b.staging_threads = staging_threads;
         b.unlocked = unlocked && nd == 1;
     }
     auto work = [&](size_t d) {
         host_block& b = blocks[d];
         verify_job J;
-        b.rc = no_throw([&] { return run_host_block(targets[d], cols, n_cols, b, status, build, J); });
+        b.rc = no_throw([&] { return run_host_block(targets[d], S, cols, b, status, J); });
         if (b.rc != JJS_OK) {
             // leave nothing in flight into the caller's arrays, the pinned slots or the counters
             snprintf(b.err, sizeof(b.err), "%s", t_err);

@@ -79,7 +79,7 @@ static int lane_launch(device_state* dev, host_lane& lane, const call_shape& S) 
         for (size_t k = 0; k < S.n_cols; ++k) in[k] = lane.dev + Y.off[k];
         staged_call C;
         // no device tally: every member counts its own statuses
-        if (int r = S.build(in, n, lane.dev + Y.status_off, nullptr, lane.stream, C)) return r;
+        if (int r = build_call(S, in, n, lane.dev + Y.status_off, nullptr, lane.stream, C)) return r;
         if (int r = launch_staged(C, lane.stream)) return r;
     }
     HIP_TRY(hipMemcpyAsync(lane.pinned + Y.status_off, lane.dev + Y.status_off, n, hipMemcpyDeviceToHost, lane.stream));

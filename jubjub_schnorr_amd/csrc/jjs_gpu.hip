@@ -21,7 +21,7 @@
 //   host_calls.h       the large blocking host-buffer calls: upload plan, staging copies, the pipeline
 //   host_lanes.h       the small ones (included among the entry points, behind the table of call shapes): staging lanes
 //                      outside the engine's mutex, calls of several threads in one launch
-//   (here)             the extern "C" entry points: one staged_call builder per scheme and input format
+//   (here)             the table of call shapes and the staged_call builder it drives; the extern "C" entry points
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -33,6 +33,7 @@
 #include <condition_variable>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <random>
 #include <sched.h>
 #include <climits>
@@ -285,26 +286,11 @@ int allreduce_tallies() {
     return JJS_OK;
 }
 
-void retire_keyset(keyset_entry& k) {      // under L.mu; the devices of its copies are alive
-    device_state* const keep = g;
-    for (keyset_copy& c : k.copies) { g = c.dev; retire(c.mem, false, c.bytes); c.mem = nullptr; }
-    g = keep;
-}
-void retire_msig_group(msig_group_entry& k) {      // the same for a signer group
-    device_state* const keep = g;
-    for (msig_group_copy& c : k.copies) { g = c.dev; retire(c.mem, false, c.bytes); c.mem = nullptr; }
-    g = keep;
-}
-
 void shutdown_locked() {
     int prev = -1;
     (void)hipGetDevice(&prev);
-    for (std::unique_ptr<keyset_entry>& k : g_keysets)       // freed with the other retired buffers by free_device
-        if (k) retire_keyset(*k);
-    g_keysets.clear();
-    for (std::unique_ptr<msig_group_entry>& k : g_msig_groups)
-        if (k) retire_msig_group(*k);
-    g_msig_groups.clear();
+    g_keysets.retire_all();
+    g_msig_groups.retire_all();
     for (device_state* d : L.devs)
         if (d->stream) { (void)hipSetDevice(d->device); (void)hipStreamSynchronize(d->stream); }
     if (L.comms_up) {
@@ -323,6 +309,136 @@ struct device_restore {   // puts the calling thread back on the device it came 
     device_restore() { (void)hipGetDevice(&prev); }
     ~device_restore() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+
+// ---- the staged_call of every scheme and input format --------------------------------------------------------------
+// The shape of every verification entry point: its columns in the order of the entry point's arguments -- width in bytes, the
+// group that decides when a large host-buffer call uploads the column (host_calls.h), and what the column is.  This table is
+// the only place that knows an entry point's argument order.
+enum col_role : uint8_t {
+    COL_SCALAR,        // u, 32 bytes
+    COL_R,             // an R point, affine or extended
+    COL_KEY,           // a key point (the generator of a var-gen signature is one), affine or extended
+    COL_MESSAGE,       // m, 32 bytes
+    COL_SIG_WIRE,      // u || R (|| R'), 32 bytes each: the R points are decoded per item
+    COL_KEYS_WIRE,     // pk (|| pk' or the generator), 32 bytes each: decoded per key or per item (job_keys / job_hash)
+};
+struct call_shape {
+    int scheme, format;
+    size_t n_cols;
+    struct { size_t width; uint32_t group; col_role role; } col[8];
+    int wire_points;              // R points per signature that a wire call decodes per item
+};
+const call_shape SHAPES[3][3] = {       // [JJS_SCHEME_*][JJS_FORMAT_*]
+    {{JJS_SCHEME_SINGLE, JJS_FORMAT_AFFINE, 4, {{32, COLS_LATE, COL_SCALAR}, {64, COLS_REST, COL_R}, {64, COLS_KEYS, COL_KEY}, {32, COLS_REST, COL_MESSAGE}}, 0},
+     {JJS_SCHEME_SINGLE, JJS_FORMAT_EXT, 4, {{32, COLS_LATE, COL_SCALAR}, {96, COLS_REST, COL_R}, {96, COLS_KEYS, COL_KEY}, {32, COLS_REST, COL_MESSAGE}}, 0},
+     {JJS_SCHEME_SINGLE, JJS_FORMAT_WIRE, 3, {{64, COLS_REST, COL_SIG_WIRE}, {32, COLS_KEYS, COL_KEYS_WIRE}, {32, COLS_REST, COL_MESSAGE}}, 1}},
+    {{JJS_SCHEME_DOUBLE, JJS_FORMAT_AFFINE, 6, {{32, COLS_LATE, COL_SCALAR}, {64, COLS_REST, COL_R}, {64, COLS_REST, COL_R}, {64, COLS_KEYS, COL_KEY},
+                                               {64, COLS_KEYS, COL_KEY}, {32, COLS_REST, COL_MESSAGE}}, 0},
+     {JJS_SCHEME_DOUBLE, JJS_FORMAT_EXT, 6, {{32, COLS_LATE, COL_SCALAR}, {96, COLS_REST, COL_R}, {96, COLS_REST, COL_R}, {96, COLS_KEYS, COL_KEY},
+                                            {96, COLS_KEYS, COL_KEY}, {32, COLS_REST, COL_MESSAGE}}, 0},
+     {JJS_SCHEME_DOUBLE, JJS_FORMAT_WIRE, 3, {{96, COLS_REST, COL_SIG_WIRE}, {64, COLS_KEYS, COL_KEYS_WIRE}, {32, COLS_REST, COL_MESSAGE}}, 2}},
+    {{JJS_SCHEME_VARGEN, JJS_FORMAT_AFFINE, 5, {{32, COLS_LATE, COL_SCALAR}, {64, COLS_REST, COL_R}, {64, COLS_KEYS, COL_KEY}, {64, COLS_KEYS, COL_KEY},
+                                               {32, COLS_REST, COL_MESSAGE}}, 0},
+     {JJS_SCHEME_VARGEN, JJS_FORMAT_EXT, 5, {{32, COLS_LATE, COL_SCALAR}, {96, COLS_REST, COL_R}, {96, COLS_KEYS, COL_KEY}, {96, COLS_KEYS, COL_KEY},
+                                            {32, COLS_REST, COL_MESSAGE}}, 0},
+     {JJS_SCHEME_VARGEN, JJS_FORMAT_WIRE, 3, {{64, COLS_REST, COL_SIG_WIRE}, {64, COLS_KEYS, COL_KEYS_WIRE}, {32, COLS_REST, COL_MESSAGE}}, 1}},
+};
+
+// A slot's wire area (wire and ext entry points, calls against a key set), per item: four point columns of 64 bytes, 16 bytes
+// of flags (the first: the encoding was rejected) and the prefix products of the normalisation (normalize.h) -- one area for
+// the key columns and one for the others, whose launches may overlap in a host-buffer call.
+constexpr size_t WIRE_FLAGS_AT = 4 * 64, WIRE_SCRATCH_AT = 4 * 64 + 16, WIRE_SCRATCH_BYTES = 48, WIRE_ITEM_BYTES = WIRE_SCRATCH_AT + 2 * WIRE_SCRATCH_BYTES;
+int ensure_wire(size_t n) {
+    if (n <= sl->wire_items) return JJS_OK;
+    const size_t cap = grown(n < 4096 ? 4096 : n);
+    return regrow(sl->wire, sl->wire_items, sl->wire_items * WIRE_ITEM_BYTES, cap, cap * WIRE_ITEM_BYTES);
+}
+uint8_t* wire_pts(int k) { return sl->wire + (size_t)k * sl->wire_items * 64; }
+uint8_t* wire_bad() { return sl->wire + sl->wire_items * WIRE_FLAGS_AT; }
+uint32_t* wire_scratch(int k) { return reinterpret_cast<uint32_t*>(sl->wire + sl->wire_items * (WIRE_SCRATCH_AT + WIRE_SCRATCH_BYTES * k)); }
+
+// the scheme's verification descriptor over affine columns (Rp, PK2: the columns the scheme has; PK2 of a var-gen call: the generator)
+verify_params scheme_params(int scheme, const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* PK, const uint8_t* PK2,
+                            const uint8_t* m, size_t n, const out_ptrs& o) {
+    if (scheme == JJS_SCHEME_SINGLE) return params_single(u, R, PK, m, n, g->comb_g, o);
+    if (scheme == JJS_SCHEME_DOUBLE) return params_double(u, R, Rp, PK, PK2, m, n, g->tag, g->comb_g, g->comb_gn, o);
+    return params_vargen(u, R, PK, PK2, m, n, o);
+}
+
+// Builds the call of shape S from the device arrays d[0..] (in the order of the entry point's arguments): picks the call slot,
+// sizes what the format needs in it and fills in the descriptors.  Resident calls launch it at once (launch_staged), host-buffer
+// calls feed it piece by piece (run_host_block).
+// Points that are converted on the device land in wire_pts(k), the R points ahead of the keys: extended coordinates (U, V, Z)
+// are normalised (N[grp]: the columns of that group), compressed R points are decoded per item (W.sig) and compressed keys per
+// key or per item (W.comp); the flags of rejected encodings are P.pre_malformed.  The descriptor then reads affine columns.
+int build_call(const call_shape& S, const void* const* d, size_t n, void* status, void* tally, hipStream_t s, staged_call& C) {
+    for (size_t k = 0; k < S.n_cols; ++k)
+        if (n && !all_ok(d[k])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
+    pick_slot(n, s);
+    const bool affine = S.format == JJS_FORMAT_AFFINE;
+    if (!affine)
+        if (int rc = ensure_wire(n)) return rc;
+    C = staged_call{};
+    const uint8_t *u = nullptr, *m = nullptr, *R[2] = {}, *PK[2] = {};
+    uint32_t n_r = 0, n_pk = 0, sig_width = 0;
+    for (size_t k = 0; k < S.n_cols; ++k) {
+        const uint8_t* const p = (const uint8_t*)d[k];
+        const uint32_t width = (uint32_t)S.col[k].width;
+        switch (S.col[k].role) {
+        case COL_SCALAR: u = p; break;
+        case COL_MESSAGE: m = p; break;
+        case COL_R: case COL_KEY: {
+            const uint8_t* point = p;
+            if (!affine) {                // normalised into the next wire column, with the other columns of its group
+                uint8_t* const out = wire_pts((int)(n_r + n_pk));
+                for (uint32_t grp = COLS_KEYS; grp <= COLS_ALL; ++grp) {
+                    normalize_params& N = C.N[grp];
+                    if (!(S.col[k].group & grp)) continue;
+                    N.src[N.n_src] = fe_src{p, width, 0};
+                    N.out[N.n_src] = out;
+                    ++N.n_src;
+                }
+                point = out;
+            }
+            (S.col[k].role == COL_R ? R[n_r++] : PK[n_pk++]) = point;
+            break;
+        }
+        case COL_SIG_WIRE:
+            u = p; sig_width = width;
+            for (; n_r < (uint32_t)S.wire_points; ++n_r) {
+                C.W.sig.src[n_r] = fe_src{p, width, 32 + 32 * n_r};
+                C.W.sig.out[n_r] = wire_pts((int)n_r);
+                R[n_r] = wire_pts((int)n_r);
+            }
+            break;
+        case COL_KEYS_WIRE:
+            for (; n_pk < width / 32; ++n_pk) {
+                C.W.comp[n_pk] = fe_src{p, width, 32 * n_pk};
+                C.W.out[n_pk] = wire_pts((int)(n_r + n_pk));
+                PK[n_pk] = wire_pts((int)(n_r + n_pk));
+            }
+            C.W.n_cols = n_pk;
+            break;
+        }
+    }
+    C.P = scheme_params(S.scheme, u, R[0], R[1], PK[0], PK[1], m, n, out_ptrs{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace});
+    if (S.format == JJS_FORMAT_EXT) {
+        C.ext = true;
+        for (uint32_t grp = COLS_KEYS; grp <= COLS_ALL; ++grp) {
+            C.N[grp].bad = wire_bad();
+            C.N[grp].scratch = wire_scratch(grp == COLS_KEYS ? 1 : 0);
+        }
+        C.P.pre_malformed = wire_bad();
+    } else if (S.format == JJS_FORMAT_WIRE) {
+        C.wire = true;
+        C.W.sig.n_src = n_r; C.W.sig.n = n; C.W.sig.bad = wire_bad();
+        C.W.bad = wire_bad();
+        C.P.u = fe_src{u, sig_width, 0};
+        C.P.pre_malformed = wire_bad();
+        C.P.decoded_points = 1;
+    }
+    return JJS_OK;
+}
 
 #include "host_calls.h"
 
@@ -381,7 +497,7 @@ void jjs_shutdown(void) {
     std::unique_lock<std::mutex> lock(L.mu);
     // host-buffer calls that hold a lane finish first (they wait for the device outside the mutex)
     L.lane_cv.wait(lock, [] {
-        if (g_keyset_host_calls) return false;          // keyset host calls that hold a device pointer outside the mutex
+        if (g_blocking_calls) return false;             // blocking calls that hold a device pointer outside the mutex
         for (device_state* d : L.devs)
             for (const host_lane& l : d->lanes)
                 if (l.state != host_lane::FREE) return false;
@@ -413,154 +529,8 @@ int jjs_stream_sync(void* stream) {
     return JJS_OK;
 }
 
-// ---- the staged_call of every scheme and input format --------------------------------------------------------------
-// A builder picks the call slot, sizes what the format needs in it and fills in the descriptors from the device arrays
-// d[0..] (in the order of the entry point's arguments).  Resident calls launch it at once (launch_staged), host-buffer
-// calls feed it piece by piece (run_host_block).
-static int ensure_wire(size_t n) {
-    if (n <= sl->wire_items) return JJS_OK;
-    const size_t cap = grown(n < 4096 ? 4096 : n);
-    return regrow(sl->wire, sl->wire_items, sl->wire_items * (4 * 64 + 16 + 2 * 48), cap, cap * (4 * 64 + 16 + 2 * 48));
-}
-static uint8_t* wire_pts(int k) { return sl->wire + (size_t)k * sl->wire_items * 64; }
-static uint8_t* wire_bad() { return sl->wire + (size_t)4 * sl->wire_items * 64; }
-// prefix products of the normalisation (normalize.h): one area for the key columns and one for the others, whose
-// launches may overlap in a host-buffer call
-static uint32_t* wire_scratch(int k) { return reinterpret_cast<uint32_t*>(sl->wire + (size_t)sl->wire_items * (4 * 64 + 16 + 48 * k)); }
-
-static int build_affine_single(const void* const* d, size_t n, void* status, void* tally, hipStream_t s, staged_call& C) {
-    if (n && !all_ok(d[0], d[1], d[2], d[3])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
-    pick_slot(n, s);
-    out_ptrs o{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace};
-    C = staged_call{};
-    C.P = params_single((const uint8_t*)d[0], (const uint8_t*)d[1], (const uint8_t*)d[2], (const uint8_t*)d[3], n, g->comb_g, o);
-    return JJS_OK;
-}
-static int build_affine_double(const void* const* d, size_t n, void* status, void* tally, hipStream_t s, staged_call& C) {
-    if (n && !all_ok(d[0], d[1], d[2], d[3], d[4], d[5])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
-    pick_slot(n, s);
-    out_ptrs o{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace};
-    C = staged_call{};
-    C.P = params_double((const uint8_t*)d[0], (const uint8_t*)d[1], (const uint8_t*)d[2], (const uint8_t*)d[3], (const uint8_t*)d[4],
-                        (const uint8_t*)d[5], n, g->tag, g->comb_g, g->comb_gn, o);
-    return JJS_OK;
-}
-static int build_affine_vargen(const void* const* d, size_t n, void* status, void* tally, hipStream_t s, staged_call& C) {
-    if (n && !all_ok(d[0], d[1], d[2], d[3], d[4])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
-    pick_slot(n, s);
-    out_ptrs o{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace};
-    C = staged_call{};
-    C.P = params_vargen((const uint8_t*)d[0], (const uint8_t*)d[1], (const uint8_t*)d[2], (const uint8_t*)d[3], (const uint8_t*)d[4], n, o);
-    return JJS_OK;
-}
-
-// wire formats: d = sig, pk, m.  The R points are decoded per item into wire_pts(0) (1), the keys per key or per item
-// (job_keys / job_hash) into the columns behind them; the flags of rejected encodings are P.pre_malformed.
-static int wire_common(staged_call& C, const void* sig, uint32_t sig_stride, uint32_t n_r, size_t n) {
-    decode_params D{};
-    D.n_src = n_r; D.n = n; D.bad = wire_bad();
-    for (uint32_t k = 0; k < n_r; ++k) { D.src[k] = fe_src{(const uint8_t*)sig, sig_stride, 32 + 32 * k}; D.out[k] = wire_pts((int)k); }
-    C.wire = true;
-    C.W.sig = D;
-    C.W.bad = wire_bad();
-    C.P.u = fe_src{(const uint8_t*)sig, sig_stride, 0};
-    C.P.pre_malformed = wire_bad();
-    C.P.decoded_points = 1;
-    return JJS_OK;
-}
-static int build_wire_single(const void* const* d, size_t n, void* status, void* tally, hipStream_t s, staged_call& C) {
-    if (n && !all_ok(d[0], d[1], d[2])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
-    pick_slot(n, s);
-    if (int rc = ensure_wire(n)) return rc;
-    out_ptrs o{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace};
-    C = staged_call{};
-    C.P = params_single((const uint8_t*)d[0], wire_pts(0), wire_pts(1), (const uint8_t*)d[2], n, g->comb_g, o);
-    C.W.n_cols = 1;
-    C.W.comp[0] = fe_src{(const uint8_t*)d[1], 32, 0};  C.W.out[0] = wire_pts(1);      // PK
-    return wire_common(C, d[0], 64, 1, n);
-}
-static int build_wire_double(const void* const* d, size_t n, void* status, void* tally, hipStream_t s, staged_call& C) {
-    if (n && !all_ok(d[0], d[1], d[2])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
-    pick_slot(n, s);
-    if (int rc = ensure_wire(n)) return rc;
-    out_ptrs o{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace};
-    C = staged_call{};
-    C.P = params_double((const uint8_t*)d[0], wire_pts(0), wire_pts(1), wire_pts(2), wire_pts(3), (const uint8_t*)d[2], n, g->tag,
-                        g->comb_g, g->comb_gn, o);
-    C.W.n_cols = 2;
-    C.W.comp[0] = fe_src{(const uint8_t*)d[1], 64, 0};  C.W.out[0] = wire_pts(2);      // PK
-    C.W.comp[1] = fe_src{(const uint8_t*)d[1], 64, 32}; C.W.out[1] = wire_pts(3);      // PK'
-    return wire_common(C, d[0], 96, 2, n);
-}
-static int build_wire_vargen(const void* const* d, size_t n, void* status, void* tally, hipStream_t s, staged_call& C) {
-    if (n && !all_ok(d[0], d[1], d[2])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
-    pick_slot(n, s);
-    if (int rc = ensure_wire(n)) return rc;
-    out_ptrs o{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace};
-    C = staged_call{};
-    C.P = params_vargen((const uint8_t*)d[0], wire_pts(0), wire_pts(1), wire_pts(2), (const uint8_t*)d[2], n, o);
-    C.W.n_cols = 2;
-    C.W.comp[0] = fe_src{(const uint8_t*)d[1], 64, 0};  C.W.out[0] = wire_pts(1);      // PK
-    C.W.comp[1] = fe_src{(const uint8_t*)d[1], 64, 32}; C.W.out[1] = wire_pts(2);      // generator
-    return wire_common(C, d[0], 64, 1, n);
-}
-
-// extended coordinates (U, V, Z): normalised on the device into wire_pts(k), then the affine descriptors.  `keys`: bit k
-// set when point column k is a key column (they arrive, and are normalised, ahead of the others in a host-buffer call).
-static void ext_common(staged_call& C, const void* const* pts, uint32_t n_pts, uint32_t keys) {
-    C.ext = true;
-    for (uint32_t grp = COLS_KEYS; grp <= COLS_ALL; ++grp) {
-        normalize_params& N = C.N[grp];
-        N = normalize_params{};
-        for (uint32_t k = 0; k < n_pts; ++k) {
-            const bool is_key = ((keys >> k) & 1u) != 0;
-            if (!((is_key ? COLS_KEYS : COLS_REST) & grp)) continue;
-            N.src[N.n_src] = fe_src{(const uint8_t*)pts[k], 96, 0};
-            N.out[N.n_src] = wire_pts((int)k);
-            ++N.n_src;
-        }
-        N.bad = wire_bad();
-        N.scratch = wire_scratch(grp == COLS_KEYS ? 1 : 0);
-    }
-    C.P.pre_malformed = wire_bad();
-}
-static int build_ext_single(const void* const* d, size_t n, void* status, void* tally, hipStream_t s, staged_call& C) {
-    if (n && !all_ok(d[0], d[1], d[2], d[3])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
-    pick_slot(n, s);
-    if (int rc = ensure_wire(n)) return rc;
-    out_ptrs o{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace};
-    C = staged_call{};
-    C.P = params_single((const uint8_t*)d[0], wire_pts(0), wire_pts(1), (const uint8_t*)d[3], n, g->comb_g, o);
-    const void* pts[] = {d[1], d[2]};                      // R, PK
-    ext_common(C, pts, 2, 2u);
-    return JJS_OK;
-}
-static int build_ext_double(const void* const* d, size_t n, void* status, void* tally, hipStream_t s, staged_call& C) {
-    if (n && !all_ok(d[0], d[1], d[2], d[3], d[4], d[5])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
-    pick_slot(n, s);
-    if (int rc = ensure_wire(n)) return rc;
-    out_ptrs o{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace};
-    C = staged_call{};
-    C.P = params_double((const uint8_t*)d[0], wire_pts(0), wire_pts(1), wire_pts(2), wire_pts(3), (const uint8_t*)d[5], n, g->tag,
-                        g->comb_g, g->comb_gn, o);
-    const void* pts[] = {d[1], d[2], d[3], d[4]};          // R, R', PK, PK'
-    ext_common(C, pts, 4, 12u);
-    return JJS_OK;
-}
-static int build_ext_vargen(const void* const* d, size_t n, void* status, void* tally, hipStream_t s, staged_call& C) {
-    if (n && !all_ok(d[0], d[1], d[2], d[3], d[4])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
-    pick_slot(n, s);
-    if (int rc = ensure_wire(n)) return rc;
-    out_ptrs o{(uint8_t*)status, (unsigned long long*)tally, nullptr, sl->workspace};
-    C = staged_call{};
-    C.P = params_vargen((const uint8_t*)d[0], wire_pts(0), wire_pts(1), wire_pts(2), (const uint8_t*)d[4], n, o);
-    const void* pts[] = {d[1], d[2], d[3]};                // R, PK, Gen
-    ext_common(C, pts, 3, 6u);
-    return JJS_OK;
-}
-
 // a resident call: device pointers d[], asynchronous on `stream`
-static int resident_call(call_builder build, const void* const* d, size_t n, void* status, void* tally, void* stream) {
+static int resident_call(const call_shape& S, const void* const* d, size_t n, void* status, void* tally, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -570,29 +540,9 @@ static int resident_call(call_builder build, const void* const* d, size_t n, voi
         return JJS_OK;
     }
     staged_call C;
-    if (int rc = build(d, n, status, tally, s, C)) return rc;
+    if (int rc = build_call(S, d, n, status, tally, s, C)) return rc;
     return launch_staged(C, s);
 }
-
-// The shape of every verification entry point: its builder and the columns of a host-buffer call in the order of the
-// entry point's arguments (width in bytes, and the group that decides when a large call uploads the column: host_calls.h).
-struct call_shape {
-    call_builder build;
-    size_t n_cols;
-    struct { size_t width; uint32_t group; } col[8];
-    int wire_points;              // R points per signature that a wire call decodes per item
-};
-static const call_shape SHAPES[3][3] = {       // [JJS_SCHEME_*][JJS_FORMAT_*]
-    {{build_affine_single, 4, {{32, COLS_LATE}, {64, COLS_REST}, {64, COLS_KEYS}, {32, COLS_REST}}, 0},
-     {build_ext_single, 4, {{32, COLS_LATE}, {96, COLS_REST}, {96, COLS_KEYS}, {32, COLS_REST}}, 0},
-     {build_wire_single, 3, {{64, COLS_REST}, {32, COLS_KEYS}, {32, COLS_REST}}, 1}},
-    {{build_affine_double, 6, {{32, COLS_LATE}, {64, COLS_REST}, {64, COLS_REST}, {64, COLS_KEYS}, {64, COLS_KEYS}, {32, COLS_REST}}, 0},
-     {build_ext_double, 6, {{32, COLS_LATE}, {96, COLS_REST}, {96, COLS_REST}, {96, COLS_KEYS}, {96, COLS_KEYS}, {32, COLS_REST}}, 0},
-     {build_wire_double, 3, {{96, COLS_REST}, {64, COLS_KEYS}, {32, COLS_REST}}, 2}},
-    {{build_affine_vargen, 5, {{32, COLS_LATE}, {64, COLS_REST}, {64, COLS_KEYS}, {64, COLS_KEYS}, {32, COLS_REST}}, 0},
-     {build_ext_vargen, 5, {{32, COLS_LATE}, {96, COLS_REST}, {96, COLS_KEYS}, {96, COLS_KEYS}, {32, COLS_REST}}, 0},
-     {build_wire_vargen, 3, {{64, COLS_REST}, {64, COLS_KEYS}, {32, COLS_REST}}, 1}},
-};
 
 #include "host_lanes.h"
 #include "keyset_calls.h"
@@ -613,8 +563,6 @@ static int host_call(int scheme, int format, const uint8_t* const* ptrs, size_t 
         return JJS_OK;
     }
     if (one_device && n <= LANE_MAX_ITEMS) return lane_call(scheme, format, ptrs, n, status, tally);
-    host_col cols[8];
-    for (size_t k = 0; k < S.n_cols; ++k) cols[k] = host_col{ptrs[k], S.col[k].width, S.col[k].group};
     if (one_device) {
         // A large call fills the device by itself: such calls run one at a time per device (host_mu; they share the device's
         // staging), but outside the engine's mutex, which they take only to pick their slot -- other threads' calls are queued
@@ -630,28 +578,28 @@ static int host_call(int scheme, int format, const uint8_t* const* ptrs, size_t 
             std::lock_guard<std::mutex> lock(L.mu);
             if (L.devs.empty() || check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine was shut down during the call");
         }
-        return no_throw([&] { return run_host(cols, S.n_cols, n, status, tally, S.build, S.wire_points, true); });
+        return no_throw([&] { return run_host(S, ptrs, n, status, tally, true); });
     }
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
-    return no_throw([&] { return run_host(cols, S.n_cols, n, status, tally, S.build, S.wire_points); });
+    return no_throw([&] { return run_host(S, ptrs, n, status, tally); });
 }
 
 // ---- affine inputs: device-buffer and host-buffer entry points ----------------------------------------------
 int jjs_verify_single_dev(const void* u, const void* R, const void* PK, const void* m, size_t n, void* status,
                           void* tally, void* stream) {
     const void* d[] = {u, R, PK, m};
-    return resident_call(build_affine_single, d, n, status, tally, stream);
+    return resident_call(SHAPES[JJS_SCHEME_SINGLE][JJS_FORMAT_AFFINE], d, n, status, tally, stream);
 }
 int jjs_verify_double_dev(const void* u, const void* R, const void* Rp, const void* PK, const void* PKp, const void* m,
                           size_t n, void* status, void* tally, void* stream) {
     const void* d[] = {u, R, Rp, PK, PKp, m};
-    return resident_call(build_affine_double, d, n, status, tally, stream);
+    return resident_call(SHAPES[JJS_SCHEME_DOUBLE][JJS_FORMAT_AFFINE], d, n, status, tally, stream);
 }
 int jjs_verify_vargen_dev(const void* u, const void* R, const void* PK, const void* Gen, const void* m, size_t n,
                           void* status, void* tally, void* stream) {
     const void* d[] = {u, R, PK, Gen, m};
-    return resident_call(build_affine_vargen, d, n, status, tally, stream);
+    return resident_call(SHAPES[JJS_SCHEME_VARGEN][JJS_FORMAT_AFFINE], d, n, status, tally, stream);
 }
 int jjs_verify_single(const uint8_t* u, const uint8_t* R, const uint8_t* PK, const uint8_t* m, size_t n,
                       uint8_t* status, uint64_t tally[4]) {
@@ -676,15 +624,15 @@ int jjs_verify_vargen(const uint8_t* u, const uint8_t* R, const uint8_t* PK, con
 // ---- wire formats: on-device decoding, then the same verify kernels -----------------------------------
 int jjs_verify_single_wire_dev(const void* sig, const void* pk, const void* m, size_t n, void* status, void* tally, void* stream) {
     const void* d[] = {sig, pk, m};
-    return resident_call(build_wire_single, d, n, status, tally, stream);
+    return resident_call(SHAPES[JJS_SCHEME_SINGLE][JJS_FORMAT_WIRE], d, n, status, tally, stream);
 }
 int jjs_verify_double_wire_dev(const void* sig, const void* pk, const void* m, size_t n, void* status, void* tally, void* stream) {
     const void* d[] = {sig, pk, m};
-    return resident_call(build_wire_double, d, n, status, tally, stream);
+    return resident_call(SHAPES[JJS_SCHEME_DOUBLE][JJS_FORMAT_WIRE], d, n, status, tally, stream);
 }
 int jjs_verify_vargen_wire_dev(const void* sig, const void* pk, const void* m, size_t n, void* status, void* tally, void* stream) {
     const void* d[] = {sig, pk, m};
-    return resident_call(build_wire_vargen, d, n, status, tally, stream);
+    return resident_call(SHAPES[JJS_SCHEME_VARGEN][JJS_FORMAT_WIRE], d, n, status, tally, stream);
 }
 int jjs_verify_single_wire(const uint8_t* sig, const uint8_t* pk, const uint8_t* m, size_t n, uint8_t* status, uint64_t tally[4]) {
     const uint8_t* p[] = {sig, pk, m};
@@ -703,17 +651,17 @@ int jjs_verify_vargen_wire(const uint8_t* sig, const uint8_t* pk, const uint8_t*
 int jjs_verify_single_ext_dev(const void* u, const void* R, const void* PK, const void* m, size_t n, void* status, void* tally,
                               void* stream) {
     const void* d[] = {u, R, PK, m};
-    return resident_call(build_ext_single, d, n, status, tally, stream);
+    return resident_call(SHAPES[JJS_SCHEME_SINGLE][JJS_FORMAT_EXT], d, n, status, tally, stream);
 }
 int jjs_verify_double_ext_dev(const void* u, const void* R, const void* Rp, const void* PK, const void* PKp, const void* m,
                               size_t n, void* status, void* tally, void* stream) {
     const void* d[] = {u, R, Rp, PK, PKp, m};
-    return resident_call(build_ext_double, d, n, status, tally, stream);
+    return resident_call(SHAPES[JJS_SCHEME_DOUBLE][JJS_FORMAT_EXT], d, n, status, tally, stream);
 }
 int jjs_verify_vargen_ext_dev(const void* u, const void* R, const void* PK, const void* Gen, const void* m, size_t n,
                               void* status, void* tally, void* stream) {
     const void* d[] = {u, R, PK, Gen, m};
-    return resident_call(build_ext_vargen, d, n, status, tally, stream);
+    return resident_call(SHAPES[JJS_SCHEME_VARGEN][JJS_FORMAT_EXT], d, n, status, tally, stream);
 }
 int jjs_verify_single_ext(const uint8_t* u, const uint8_t* R, const uint8_t* PK, const uint8_t* m, size_t n, uint8_t* status,
                           uint64_t tally[4]) {
@@ -764,7 +712,7 @@ int jjs_reserve(int scheme, int format, size_t n_items, int host_buffers) {
                 const void* in[8];
                 for (size_t k = 0; k < S.n_cols; ++k) in[k] = reinterpret_cast<const void*>(uintptr_t(4096));
                 staged_call C;
-                int rc = S.build(in, per, nullptr, nullptr, nullptr, C);
+                int rc = build_call(S, in, per, nullptr, nullptr, nullptr, C);
                 forced_slot = nullptr;
                 if (rc) return rc;
                 if (int r = reserve_for(C.P)) return r;
@@ -775,9 +723,7 @@ int jjs_reserve(int scheme, int format, size_t n_items, int host_buffers) {
                     for (host_lane& l : d->lanes)
                         if (int r = ensure_lane(l, Y.total)) return r;
                 } else {
-                    host_col cols[8];
-                    for (size_t k = 0; k < S.n_cols; ++k) cols[k] = host_col{nullptr, S.col[k].width, S.col[k].group};
-                    if (int r = reserve_host_block(cols, S.n_cols, per, S.wire_points)) return r;
+                    if (int r = reserve_host_block(S, per)) return r;
                 }
             }
         }
@@ -822,7 +768,7 @@ int jjs_memory_stats(uint64_t out[JJS_MEMORY_STATS]) {
     uint64_t pool = 0, slots = 0, lanes = 0;
     for (const call_slot& c : g->slots) {
         pool += c.key_pool_bytes + c.key_memo_bytes;
-        slots += c.pending_items * 8 + c.prep_items * 65 + c.wire_items * (4 * 64 + 16 + 2 * 48) + c.small_bytes + c.keys_bytes + c.verdict_bytes;
+        slots += c.pending_items * 8 + c.prep_items * 65 + c.wire_items * WIRE_ITEM_BYTES + c.small_bytes + c.keys_bytes + c.verdict_bytes;
     }
     for (const host_lane& l : g->lanes) lanes += l.dev_bytes + l.pinned_bytes;
     out[JJS_MEMORY_KEY_POOLS] = pool;
@@ -883,16 +829,34 @@ int jjs_compress_dev(const void* affine, size_t n, void* out, void* stream) {
 }
 
 // ---- multisig: batch verify_share / combine -------------------------------------------
-// the device's multisignature scratch (grow-only), for n shares in n_transcripts transcripts: tr_of, d_words, dpk, e_pt per
-// share; a_words, c_words, the offsets and the long tags per transcript
+// The device's multisignature scratch (g->msig, grow-only; sized for g->msig_items shares in g->msig_transcripts transcripts),
+// in words: tr_of (1), d_words (8), dpk and e_pt (EXT_WORDS each) per share, then a_words and c_words (8 each), the offsets
+// (1, and one more) and the long tags (18) per transcript.
+struct msig_scratch {
+    uint32_t *tr_of, *d_words, *dpk, *e_pt, *a_words, *c_words, *offsets, *long_tags;
+};
+static size_t msig_scratch_bytes(size_t items, size_t transcripts) { return items * 4 * (1 + 8 + 2 * EXT_WORDS) + transcripts * 4 * (16 + 1 + 18) + 64; }
+static msig_scratch msig_scratch_carve() {
+    msig_scratch W{};
+    uint32_t* w = (uint32_t*)g->msig;
+    W.tr_of = w; w += g->msig_items;
+    W.d_words = w; w += 8 * g->msig_items;
+    W.dpk = w; w += EXT_WORDS * g->msig_items;
+    W.e_pt = w; w += EXT_WORDS * g->msig_items;
+    W.a_words = w; w += 8 * g->msig_transcripts;
+    W.c_words = w; w += 8 * g->msig_transcripts;
+    W.offsets = w; w += g->msig_transcripts + 1;
+    W.long_tags = w;
+    return W;
+}
 static int ensure_msig_scratch(size_t n, size_t n_transcripts) {
     if (n <= g->msig_items && n_transcripts <= g->msig_transcripts) return JJS_OK;
     size_t ci = grown(n < 4096 ? 4096 : n), ct = grown(n_transcripts < 1024 ? 1024 : n_transcripts);
     if (ci < g->msig_items) ci = g->msig_items;
     if (ct < g->msig_transcripts) ct = g->msig_transcripts;
     uint8_t* fresh = nullptr;
-    HIP_TRY(hipMalloc(&fresh, ci * 4 * (1 + 8 + 2 * EXT_WORDS) + ct * 4 * (16 + 1 + 18) + 64));
-    retire(g->msig, false, g->msig_items * 4 * (1 + 8 + 2 * EXT_WORDS) + g->msig_transcripts * 4 * (16 + 1 + 18) + 64);
+    HIP_TRY(hipMalloc(&fresh, msig_scratch_bytes(ci, ct)));
+    retire(g->msig, false, msig_scratch_bytes(g->msig_items, g->msig_transcripts));
     g->msig = fresh;
     g->msig_items = ci; g->msig_transcripts = ct;
     return JJS_OK;
@@ -923,27 +887,20 @@ int jjs_multisig_combine_dev(const void* z, const void* PK, const void* R, const
     P.n_transcripts = (uint32_t)n_transcripts; P.n_total = n;
     P.share_status = (uint8_t*)share_status; P.agg_pk = (uint8_t*)agg_pk; P.sig_u = (uint8_t*)sig_u; P.sig_R = (uint8_t*)sig_R;
     P.transcript_status = (uint8_t*)transcript_status;
-    uint32_t* w = (uint32_t*)g->msig;
-    P.tr_of = w; w += g->msig_items;
-    P.d_words = w; w += 8 * g->msig_items;
-    P.dpk = w; w += EXT_WORDS * g->msig_items;
-    P.e_pt = w; w += EXT_WORDS * g->msig_items;
-    P.a_words = w; w += 8 * g->msig_transcripts;
-    P.c_words = w; w += 8 * g->msig_transcripts;
-    uint32_t* d_off = w; w += g->msig_transcripts + 1;
-    uint32_t* d_long = w;
-    P.offsets = d_off;
+    const msig_scratch W = msig_scratch_carve();
+    P.tr_of = W.tr_of; P.d_words = W.d_words; P.dpk = W.dpk; P.e_pt = W.e_pt;
+    P.a_words = W.a_words; P.c_words = W.c_words; P.offsets = W.offsets;
     P.tags = g->tags_long; P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
     P.max_table_participants = JJS_MSIG_MAX_PARTICIPANTS;
-    P.long_tags = d_long;
+    P.long_tags = W.long_tags;
     big_slot();
     if (int rc = begin_shared(s)) return rc;
     auto queue = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(d_off, offsets_host, (n_transcripts + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(W.offsets, offsets_host, (n_transcripts + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         for (int pass = 0; pass < 7; ++pass) {
             const size_t count = (pass == 0 || pass == 2 || pass == 4 || pass == 6) ? n_transcripts : n;
             // a pass with a hash chain and few items: eight lanes per item (multisig_core.h hash_lanes)
-            P.hash_lanes = ((pass == 1 || pass == 2 || pass == 4) && count <= MSIG_COOP_MAX_ITEMS) ? 8u : 1u;
+            P.hash_lanes = (pass == 1 || pass == 2 || pass == 4) ? msig_hash_lanes(count) : 1u;
             hipLaunchKernelGGL(msig_kernel, dim3(grid_for(g->grid_msig, count * P.hash_lanes)), dim3(BLOCK), 0, s, P, pass);
         }
         HIP_TRY(hipGetLastError());

@@ -1,17 +1,89 @@
 // Part of jjs_gpu.hip (included among the extern "C" entry points): registered key sets (keyset.h, include/jjs_gpu.h
 // jjs_keyset_*) -- building a set on every driven device, the registry, and the calls against a set.
 
-static keyset_entry* find_keyset(jjs_keyset h) {            // under L.mu
-    const uint32_t idx = (uint32_t)(h & 0xffffffffu), gen = (uint32_t)(h >> 32);
-    if (idx == 0 || idx > g_keysets.size()) return nullptr;
-    keyset_entry* k = g_keysets[idx - 1].get();
-    return k && k->generation == gen ? k : nullptr;
+extern "C++" {        // (templates below)
+// One jjs_*_create call, from its first section under L.mu to the published handle.  The object is built outside the engine's
+// mutex, on a stream of its own per device (other threads' calls go on meanwhile), and published in its registry under the
+// mutex once every copy is complete.  While it is being built the call counts among the blocking calls jjs_shutdown waits
+// for, so the devices it uses stay alive.  Nothing here throws.
+// The three steps are called in this order, each only after the one before returned JJS_OK (`e` is null until enter() has).
+template <class Entry>
+class registration {
+    std::vector<device_state*> devs;       // the devices the engine drove when the call came in
+    std::optional<blocking_call_leave> leave_on_every_way_out;
+    void free_copies() {                   // nothing has been published: no launch of anybody else reads these
+        device_restore restore;
+        for (auto& c : e->copies)
+            if (c.mem) { (void)hipSetDevice(c.dev->device); (void)hipFree(c.mem); c.mem = nullptr; }
+    }
+public:
+    std::unique_ptr<Entry> e;              // the entry, from enter() until it is published
+    // the first section under L.mu: the engine is ready, check() accepts the arguments; then the call is counted in
+    template <class Check>
+    int enter(Check check) {
+        std::lock_guard<std::mutex> lock(L.mu);
+        if (int rc = check_ready()) return rc;
+        if (int rc = check()) return rc;
+        if (int rc = no_throw([&] { devs = L.devs; e.reset(new Entry()); return JJS_OK; })) return rc;
+        ++g_blocking_calls;
+        leave_on_every_way_out.emplace();
+        return JJS_OK;
+    }
+    // build_copy(copy, stream) on every device in turn (g is that device), each on a non-blocking stream of its own
+    template <class BuildCopy>
+    int build(BuildCopy build_copy) {
+        device_restore restore;
+        const int rc = no_throw([&]() -> int {
+            for (device_state* d : devs) {
+                g = d;
+                HIP_TRY(hipSetDevice(d->device));
+                hipStream_t s = nullptr;
+                HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+                e->copies.emplace_back();
+                const int brc = build_copy(e->copies.back(), s);
+                (void)hipStreamDestroy(s);
+                if (brc) { e->copies.pop_back(); return brc; }
+            }
+            return JJS_OK;
+        });
+        if (rc) free_copies();
+        return rc;
+    }
+    // the second section under L.mu: the engine still drives the same devices; the entry goes into `reg`, its handle to *out
+    int publish(registry<Entry>& reg, const char* what, uint64_t* out) {
+        std::lock_guard<std::mutex> lock(L.mu);
+        int rc = L.devs != devs ? fail(JJS_ERR_NOT_INIT, "the engine's devices changed while the %s was built", what)
+                                : no_throw([&] { *out = reg.publish(e); return JJS_OK; });
+        if (rc) free_copies();
+        return rc;
+    }
+};
+// The frame of one device's copy `c` of an object (g is that device; `what`: the object, for the messages): the copy's own
+// allocation of `bytes`, a build area of `tmp_bytes` beside it, body(build area), which carves both and queues the build on
+// stream s; then the stream is drained and the build area freed -- and the copy with it when the body failed.
+template <class Body>
+static int build_device_copy(device_copy& c, size_t bytes, size_t tmp_bytes, const char* what, hipStream_t s, Body body) {
+    c.dev = g;
+    c.bytes = bytes;
+    if (hipMalloc(&c.mem, c.bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c.mem = nullptr;
+        return fail(JJS_ERR_HIP, "hipMalloc of a %s (%zu bytes) failed", what, c.bytes);
+    }
+    uint8_t* tmp = nullptr;
+    if (hipMalloc(&tmp, tmp_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(c.mem); c.mem = nullptr;
+        return fail(JJS_ERR_HIP, "hipMalloc of a %s's build area (%zu bytes) failed", what, tmp_bytes);
+    }
+    const int rc = body(tmp);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(tmp);
+    if (rc) { (void)hipFree(c.mem); c.mem = nullptr; }
+    return rc;
 }
-static const keyset_copy* keyset_copy_for(const keyset_entry& k, const device_state* d) {
-    for (const keyset_copy& c : k.copies)
-        if (c.dev == d) return &c;
-    return nullptr;
-}
+}  // extern "C++"
+
 static uint32_t keyset_cols(int scheme) { return scheme == JJS_SCHEME_SINGLE ? 1u : 2u; }
 
 // One device's copy of a set (g is that device): the keys uploaded and decoded / normalised into the copy, their flags, the
@@ -23,37 +95,24 @@ static int keyset_build_copy(keyset_entry& k, keyset_copy& c, int format, const 
     const int w = KEYSET_WINDOW;
     const size_t key_bytes = pad256((size_t)n * 64), flag_bytes = pad256(n);
     const size_t table_bytes = (size_t)n * kt_positions(w) * kt_table_words(w) * 4;
-    c.dev = g;
-    c.bytes = 256 + cols * (key_bytes + flag_bytes + pad256(table_bytes));
-    if (hipMalloc(&c.mem, c.bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        c.mem = nullptr;
-        return fail(JJS_ERR_HIP, "hipMalloc of a key set (%zu bytes) failed", c.bytes);
-    }
-    uint8_t* p = c.mem;
-    c.words = reinterpret_cast<uint32_t*>(p); p += 256;
-    for (uint32_t i = 0; i < cols; ++i) {
-        c.keys[i] = p; p += key_bytes;
-        c.flags[i] = p; p += flag_bytes;
-        c.tables[i] = reinterpret_cast<uint32_t*>(p); p += pad256(table_bytes);
-    }
     // the build area: the uploaded encodings, the chains of bases, key_item, the valid-key lists, the malformed flags
     const size_t in_width = format == JJS_FORMAT_EXT ? 96 : (format == JJS_FORMAT_WIRE ? 32 : 0);
     const size_t in_bytes = pad256((size_t)n * in_width * cols), base_bytes = pad256((size_t)n * kt_positions(w) * KT_BASE_WORDS * 4);
     const size_t item_bytes = pad256((size_t)n * 4), valid_bytes = pad256(((size_t)n + 1) * 4), scratch_bytes = pad256((size_t)n * 48);
     const size_t tmp_bytes = in_bytes + cols * (base_bytes + valid_bytes) + item_bytes + flag_bytes + scratch_bytes;
-    uint8_t* tmp = nullptr;
-    if (hipMalloc(&tmp, tmp_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(c.mem); c.mem = nullptr;
-        return fail(JJS_ERR_HIP, "hipMalloc of a key set's build area (%zu bytes) failed", tmp_bytes);
-    }
-    // host memory the queued copies read or write: it outlives every return path below (the stream is drained first)
+    // host memory the queued copies read or write: it outlives the frame, which drains the stream on every way out
     std::vector<uint32_t> host(64 > n ? 64 : n);
     for (uint32_t i = 0; i < n; ++i) host[i] = i;
     uint32_t words[64] = {n, n, (uint32_t)w};
     flags_out.assign((size_t)cols * n, 0);
-    int rc = [&]() -> int {
+    return build_device_copy(c, 256 + cols * (key_bytes + flag_bytes + pad256(table_bytes)), tmp_bytes, "key set", s, [&](uint8_t* tmp) -> int {
+        uint8_t* p = c.mem;
+        c.words = reinterpret_cast<uint32_t*>(p); p += 256;
+        for (uint32_t i = 0; i < cols; ++i) {
+            c.keys[i] = p; p += key_bytes;
+            c.flags[i] = p; p += flag_bytes;
+            c.tables[i] = reinterpret_cast<uint32_t*>(p); p += pad256(table_bytes);
+        }
         uint8_t* q = tmp;
         uint8_t* in = q; q += in_bytes;
         uint32_t* key_item = reinterpret_cast<uint32_t*>(q); q += item_bytes;
@@ -103,19 +162,7 @@ static int keyset_build_copy(keyset_entry& k, keyset_copy& c, int format, const 
             HIP_TRY(hipMemcpyAsync(flags_out.data() + (size_t)i * n, c.flags[i], n, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return JJS_OK;
-    }();
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(tmp);
-    if (rc) { (void)hipFree(c.mem); c.mem = nullptr; }
-    return rc;
-}
-
-// the scheme's verification descriptor over affine columns (Rp, PK2: the columns the scheme has)
-static verify_params scheme_params(int scheme, const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* PK, const uint8_t* PK2,
-                                   const uint8_t* m, size_t n, const out_ptrs& o) {
-    if (scheme == JJS_SCHEME_SINGLE) return params_single(u, R, PK, m, n, g->comb_g, o);
-    if (scheme == JJS_SCHEME_DOUBLE) return params_double(u, R, Rp, PK, PK2, m, n, g->tag, g->comb_g, g->comb_gn, o);
-    return params_vargen(u, R, PK, PK2, m, n, o);
+    });
 }
 
 // The front of a call against a set's copy `c` on stream s (g is c's device), shared by keyset_launch and
@@ -264,9 +311,9 @@ static int keyset_check_cols(int scheme, int format, const void* key_idx, const 
 
 // ---- blocking host calls on a device's key-set stream ------------------------------------------------------------------------
 // Such a call (jjs_keyset_create, jjs_keyset_verify, the verdict algorithm of jjs_verify_all_* and jjs_keyset_verify_all)
-// counts itself among g_keyset_host_calls in its first section under L.mu, so that jjs_shutdown does not free its device
-// before it has left, and leaves through keyset_host_call_leave (engine_state.h) on every way out.
-extern "C++" {        // (templates below)
+// counts itself among g_blocking_calls in its first section under L.mu, so that jjs_shutdown does not free its device
+// before it has left, and leaves through blocking_call_leave (engine_state.h) on every way out.
+extern "C++" {
 // The call's columns and outputs in dev's staging area (under dev->host_mu): column i of widths[i] bytes per item (0: not
 // used) copied from src[i] on the key-set stream s, then output areas of out_bytes[j] bytes, each part padded to 256 bytes.
 struct keyset_stage {
@@ -302,9 +349,9 @@ static int keyset_launch_locked(device_state* dev, const jjs_keyset* ks, Launch 
     keyset_entry* k = nullptr;
     const keyset_copy* c = nullptr;
     if (ks) {
-        k = find_keyset(*ks);
+        k = g_keysets.find(*ks);
         if (!k) return fail(JJS_ERR_ARG, "the key set was destroyed during the call");
-        c = keyset_copy_for(*k, dev);
+        c = copy_for(*k, dev);
         if (!c) return fail(JJS_ERR_ARG, "the key set has no copy on this device");
     }
     return launch(k, c);
@@ -313,84 +360,48 @@ static int keyset_launch_locked(device_state* dev, const jjs_keyset* ks, Launch 
 
 extern "C" {
 
-// The set is built outside the engine's mutex, on a stream of its own per device (other threads' calls go on meanwhile), and
-// published in the registry under the mutex once every copy is complete.  While it is being built the call counts among the
-// keyset calls jjs_shutdown waits for, so the devices it uses stay alive.
 int jjs_keyset_create(int scheme, int format, const uint8_t* keys, const uint8_t* keys2, size_t n_keys, uint8_t* key_status,
                       jjs_keyset* out) {
-    std::vector<device_state*> devs;
-    {
-        std::lock_guard<std::mutex> lock(L.mu);
-        if (int rc = check_ready()) return rc;
-        if (scheme < 0 || scheme > 2 || format < 0 || format > 2) return fail(JJS_ERR_ARG, "scheme / format out of range");
-        if (!out || !keys || n_keys == 0 || n_keys > KEYSET_MAX_KEYS) return fail(JJS_ERR_ARG, "a key set needs 1 .. 2^24 keys and an output handle");
-        if (keyset_cols(scheme) > 1 && format != JJS_FORMAT_WIRE && !keys2) return fail(JJS_ERR_ARG, "the second key column is missing");
-        devs = L.devs;
-        ++g_keyset_host_calls;
-    }
-    keyset_host_call_leave leave_on_every_way_out;
+    registration<keyset_entry> call;
+    if (int rc = call.enter([&] {
+            if (scheme < 0 || scheme > 2 || format < 0 || format > 2) return fail(JJS_ERR_ARG, "scheme / format out of range");
+            if (!out || !keys || n_keys == 0 || n_keys > KEYSET_MAX_KEYS) return fail(JJS_ERR_ARG, "a key set needs 1 .. 2^24 keys and an output handle");
+            if (keyset_cols(scheme) > 1 && format != JJS_FORMAT_WIRE && !keys2) return fail(JJS_ERR_ARG, "the second key column is missing");
+            return (int)JJS_OK;
+        }))
+        return rc;
+    keyset_entry& k = *call.e;
     const uint32_t cols = keyset_cols(scheme);
-    std::unique_ptr<keyset_entry> k(new keyset_entry());
-    k->scheme = scheme; k->n_keys = (uint32_t)n_keys; k->n_cols = cols;
-    device_restore restore;
-    auto free_copies = [&] {               // nothing has been published: no launch of anybody else reads these
-        for (keyset_copy& c : k->copies)
-            if (c.mem) { (void)hipSetDevice(c.dev->device); (void)hipFree(c.mem); c.mem = nullptr; }
-    };
-    std::vector<uint8_t> flags;
-    int rc = no_throw([&]() -> int {
-        for (device_state* d : devs) {
-            g = d;
-            HIP_TRY(hipSetDevice(d->device));
-            hipStream_t s = nullptr;
-            HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-            k->copies.emplace_back();
+    k.scheme = scheme; k.n_keys = (uint32_t)n_keys; k.n_cols = cols;
+    std::vector<uint8_t> flags;            // of the first copy: every device computes the same
+    if (int rc = call.build([&](keyset_copy& c, hipStream_t s) {
             std::vector<uint8_t> f;
-            const int brc = keyset_build_copy(*k, k->copies.back(), format, keys, keys2, f, s);
-            (void)hipStreamDestroy(s);
-            if (brc) { k->copies.pop_back(); return brc; }
-            if (flags.empty()) flags.swap(f);
-        }
-        return JJS_OK;
-    });
-    if (rc) { free_copies(); return rc; }
+            const int brc = keyset_build_copy(k, c, format, keys, keys2, f, s);
+            if (!brc && flags.empty()) flags.swap(f);
+            return brc;
+        }))
+        return rc;
     uint32_t valid = 0;
     for (size_t i = 0; i < n_keys; ++i) {
         const uint32_t st = ks_key_status(flags[i], cols > 1 ? flags[n_keys + i] : (uint32_t)KT_KEY_VALID);
         if (key_status) key_status[i] = (uint8_t)st;
         valid += st == ST_OK;
     }
-    k->valid = valid;
-    std::lock_guard<std::mutex> lock(L.mu);
-    if (L.devs != devs) { free_copies(); return fail(JJS_ERR_NOT_INIT, "the engine's devices changed while the key set was built"); }
-    rc = no_throw([&]() -> int {
-        size_t slot = 0;
-        while (slot < g_keysets.size() && g_keysets[slot]) ++slot;
-        if (slot == g_keysets.size()) g_keysets.emplace_back();
-        if (++g_keyset_generation == 0) ++g_keyset_generation;       // 0 is never a generation: no valid handle is 0
-        k->generation = g_keyset_generation;
-        *out = ((uint64_t)k->generation << 32) | (uint64_t)(slot + 1);
-        g_keysets[slot] = std::move(k);
-        return JJS_OK;
-    });
-    if (rc) free_copies();
-    return rc;
+    k.valid = valid;
+    return call.publish(g_keysets, "key set", out);
 }
 
 int jjs_keyset_destroy(jjs_keyset ks) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
-    keyset_entry* k = find_keyset(ks);
-    if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
-    retire_keyset(*k);         // launches already queued still read it: freed by jjs_trim / jjs_shutdown
-    g_keysets[(ks & 0xffffffffu) - 1].reset();
+    if (!g_keysets.destroy(ks)) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
     return JJS_OK;
 }
 
 int jjs_keyset_info(jjs_keyset ks, uint64_t out[JJS_KEYSET_INFO]) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
-    keyset_entry* k = find_keyset(ks);
+    keyset_entry* k = g_keysets.find(ks);
     if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
     if (!out) return fail(JJS_ERR_ARG, "null pointer");
     out[JJS_KEYSET_SCHEME] = (uint64_t)k->scheme;
@@ -407,7 +418,7 @@ int jjs_keyset_verify_dev(jjs_keyset ks, int format, const void* key_idx, const 
                           size_t n, void* status, void* tally, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
-    keyset_entry* k = find_keyset(ks);
+    keyset_entry* k = g_keysets.find(ks);
     if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
     hipStream_t s = (hipStream_t)stream;
     if (status && !aligned16(status)) return fail(JJS_ERR_ARG, "status must be 16-byte aligned");
@@ -417,7 +428,7 @@ int jjs_keyset_verify_dev(jjs_keyset ks, int format, const void* key_idx, const 
         return JJS_OK;
     }
     if (int rc = keyset_check_cols(k->scheme, format, key_idx, s0, s1, s2, m, true)) return rc;
-    const keyset_copy* c = keyset_copy_for(*k, g);
+    const keyset_copy* c = copy_for(*k, g);
     if (!c) return fail(JJS_ERR_ARG, "the key set has no copy on this device");
     const void* d[] = {key_idx, s0, s1, s2, m};
     return no_throw([&] { return keyset_launch(*k, *c, format, d, n, status, tally, s); });
@@ -434,7 +445,7 @@ int jjs_keyset_verify(jjs_keyset ks, int format, const uint32_t* key_idx, const 
     {
         std::lock_guard<std::mutex> lock(L.mu);
         if (int rc = check_ready()) return rc;
-        keyset_entry* k = find_keyset(ks);
+        keyset_entry* k = g_keysets.find(ks);
         if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
         if (format < 0 || format > 2) return fail(JJS_ERR_ARG, "format out of range");
         if (n == 0) {
@@ -444,9 +455,9 @@ int jjs_keyset_verify(jjs_keyset ks, int format, const uint32_t* key_idx, const 
         if (int rc = keyset_check_cols(k->scheme, format, key_idx, s0, s1, s2, m, false)) return rc;
         scheme = k->scheme;
         dev = g;
-        ++g_keyset_host_calls;           // jjs_shutdown does not free `dev` before this call has left (see below)
+        ++g_blocking_calls;              // jjs_shutdown does not free `dev` before this call has left (see below)
     }
-    keyset_host_call_leave leave_on_every_way_out;
+    blocking_call_leave leave_on_every_way_out;
     std::lock_guard<std::mutex> big(dev->host_mu);
     g = dev;
     return no_throw([&]() -> int {

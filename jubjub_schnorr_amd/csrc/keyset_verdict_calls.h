@@ -98,14 +98,14 @@ int jjs_keyset_verify_all_dev(jjs_keyset ks, int format, const void* key_idx, co
                               size_t n, void* verdict, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
-    keyset_entry* k = find_keyset(ks);
+    keyset_entry* k = g_keysets.find(ks);
     if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
     hipStream_t s = (hipStream_t)stream;
     if (format < 0 || format > 2) return fail(JJS_ERR_ARG, "format out of range");
     if (int rc = verdict_word_dev(verdict, n, s)) return rc;
     if (n == 0) return JJS_OK;
     if (int rc = keyset_check_cols(k->scheme, format, key_idx, s0, s1, s2, m, true)) return rc;
-    const keyset_copy* c = keyset_copy_for(*k, g);
+    const keyset_copy* c = copy_for(*k, g);
     if (!c) return fail(JJS_ERR_ARG, "the key set has no copy on this device");
     const void* d[] = {key_idx, s0, s1, s2, m};
     return no_throw([&] {
@@ -125,7 +125,7 @@ int jjs_keyset_verify_all(jjs_keyset ks, int format, const uint32_t* key_idx, co
     {
         std::lock_guard<std::mutex> lock(L.mu);
         if (int rc = check_ready()) return rc;
-        keyset_entry* k = find_keyset(ks);
+        keyset_entry* k = g_keysets.find(ks);
         if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
         if (format < 0 || format > 2) return fail(JJS_ERR_ARG, "format out of range");
         if (n == 0) { *verdict = 1; return JJS_OK; }
@@ -133,7 +133,7 @@ int jjs_keyset_verify_all(jjs_keyset ks, int format, const uint32_t* key_idx, co
         scheme = k->scheme;
         msm = keyset_verdict_route(scheme, format, n);
         dev = g;
-        if (msm) ++g_keyset_host_calls;       // jjs_shutdown does not free `dev` before this call has left
+        if (msm) ++g_blocking_calls;       // jjs_shutdown does not free `dev` before this call has left
     }
     uint64_t tally[4] = {};
     auto per_item = [&] { return jjs_keyset_verify(ks, format, key_idx, s0, s1, s2, m, n, status, tally); };

@@ -1,18 +1,6 @@
 // Part of jjs_gpu.hip (included among the extern "C" entry points): multisig signer groups (msig_group.h, include/jjs_gpu.h
 // jjs_msig_group_*) -- building a group on every driven device, the registry, and the call against a group.
 
-static msig_group_entry* find_msig_group(jjs_msig_group h) {            // under L.mu
-    const uint32_t idx = (uint32_t)(h & 0xffffffffu), gen = (uint32_t)(h >> 32);
-    if (idx == 0 || idx > g_msig_groups.size()) return nullptr;
-    msig_group_entry* k = g_msig_groups[idx - 1].get();
-    return k && k->generation == gen ? k : nullptr;
-}
-static const msig_group_copy* msig_group_copy_for(const msig_group_entry& k, const device_state* d) {
-    for (const msig_group_copy& c : k.copies)
-        if (c.dev == d) return &c;
-    return nullptr;
-}
-
 // A call has at least this many transcripts when its share pass runs a wave over the transcripts of ONE participant
 // (msig_group_params::by_participant): below, a wave would span several participants anyway.
 constexpr size_t MSIG_GROUP_BY_PARTICIPANT_FROM = 64;
@@ -23,31 +11,18 @@ static int msig_group_build_copy(msig_group_entry& k, msig_group_copy& c, const 
                                  hipStream_t s) {
     const uint32_t n = k.participants;
     const size_t d_bytes = pad256((size_t)n * 32), table_bytes = (size_t)n * MG_TABLE_WORDS_PER_KEY * 4;
-    c.dev = g;
-    c.bytes = 256 + d_bytes + pad256(table_bytes);
-    if (hipMalloc(&c.mem, c.bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        c.mem = nullptr;
-        return fail(JJS_ERR_HIP, "hipMalloc of a signer group (%zu bytes) failed", c.bytes);
-    }
-    c.agg_pk = c.mem;
-    c.tag_a = reinterpret_cast<uint32_t*>(c.mem + 64);
-    c.d_words = reinterpret_cast<uint32_t*>(c.mem + 256);
-    c.tables = reinterpret_cast<uint32_t*>(c.mem + 256 + d_bytes);
     // the build area: the keys, pass 1's participant map, offsets and D_j, the chains of bases, the lanes' workspaces
-    const uint32_t hash_lanes = n <= MSIG_COOP_MAX_ITEMS ? 8u : 1u;
+    const uint32_t hash_lanes = msig_hash_lanes(n);
     const int delin_grid = grid_for(g->grid_msig, (size_t)n * hash_lanes);
     const size_t pk_bytes = pad256((size_t)n * 64), map_bytes = pad256((size_t)n * 4), dpk_bytes = pad256((size_t)n * EXT_WORDS * 4);
     const size_t base_bytes = pad256((size_t)n * MG_BASE_WORDS_PER_KEY * 4), ws_bytes = (size_t)delin_grid * BLOCK * WS_WORDS_PER_LANE * 4;
     const size_t tmp_bytes = pk_bytes + map_bytes + 256 + dpk_bytes + base_bytes + ws_bytes;
-    uint8_t* tmp = nullptr;
-    if (hipMalloc(&tmp, tmp_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(c.mem); c.mem = nullptr;
-        return fail(JJS_ERR_HIP, "hipMalloc of a signer group's build area (%zu bytes) failed", tmp_bytes);
-    }
-    const uint32_t offsets[2] = {0, n};          // host memory the queued copies read: the stream is drained before it goes
-    int rc = [&]() -> int {
+    const uint32_t offsets[2] = {0, n};          // host memory the queued copies read: the frame drains the stream before it goes
+    return build_device_copy(c, 256 + d_bytes + pad256(table_bytes), tmp_bytes, "signer group", s, [&](uint8_t* tmp) -> int {
+        c.agg_pk = c.mem;
+        c.tag_a = reinterpret_cast<uint32_t*>(c.mem + 64);
+        c.d_words = reinterpret_cast<uint32_t*>(c.mem + 256);
+        c.tables = reinterpret_cast<uint32_t*>(c.mem + 256 + d_bytes);
         uint8_t* q = tmp;
         uint8_t* pk = q; q += pk_bytes;
         uint32_t* tr_of = reinterpret_cast<uint32_t*>(q); q += map_bytes;
@@ -73,95 +48,51 @@ static int msig_group_build_copy(msig_group_entry& k, msig_group_copy& c, const 
         HIP_TRY(hipMemcpyAsync(agg_out, c.agg_pk, 64, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return JJS_OK;
-    }();
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(tmp);
-    if (rc) { (void)hipFree(c.mem); c.mem = nullptr; }
-    return rc;
+    });
 }
 
 extern "C" {
 
-// Built outside the engine's mutex, on a stream of its own per device, and published under the mutex once every copy is
-// complete; while it is being built the call counts among the calls jjs_shutdown waits for (as jjs_keyset_create).
 int jjs_msig_group_create(const uint8_t* PK, size_t n, jjs_msig_group* out) {
-    std::vector<device_state*> devs;
-    {
-        std::lock_guard<std::mutex> lock(L.mu);
-        if (int rc = check_ready()) return rc;
-        if (!out || !PK || n == 0) return fail(JJS_ERR_ARG, "a signer group needs at least one key and an output handle");
-        if (n > JJS_MSIG_PARTICIPANTS_LIMIT) return fail(JJS_ERR_ARG, "%zu participants (at most %u)", n, (unsigned)JJS_MSIG_PARTICIPANTS_LIMIT);
-        devs = L.devs;
-        ++g_keyset_host_calls;
-    }
-    keyset_host_call_leave leave_on_every_way_out;
-    std::unique_ptr<msig_group_entry> k;
+    registration<msig_group_entry> call;
+    if (int rc = call.enter([&] {
+            if (!out || !PK || n == 0) return fail(JJS_ERR_ARG, "a signer group needs at least one key and an output handle");
+            if (n > JJS_MSIG_PARTICIPANTS_LIMIT) return fail(JJS_ERR_ARG, "%zu participants (at most %u)", n, (unsigned)JJS_MSIG_PARTICIPANTS_LIMIT);
+            return (int)JJS_OK;
+        }))
+        return rc;
+    msig_group_entry& k = *call.e;
     std::vector<u32x4> keys;                // the caller's bytes, aligned for the range test
-    uint32_t tags[2][9];
-    int rc = no_throw([&]() -> int {
-        k.reset(new msig_group_entry());
-        keys.resize(n * 4);
-        memcpy(keys.data(), PK, n * 64);
-        return JJS_OK;
-    });
-    if (rc) return rc;
+    if (int rc = no_throw([&]() -> int {
+            keys.resize(n * 4);
+            memcpy(keys.data(), PK, n * 64);
+            return JJS_OK;
+        }))
+        return rc;
     const uint8_t* pk = reinterpret_cast<const uint8_t*>(keys.data());
     if (!mg_keys_acceptable(pk, n)) return fail(JJS_ERR_ARG, "a coordinate of a key is not below q");
-    k->participants = (uint32_t)n;
+    k.participants = (uint32_t)n;
+    uint32_t tags[2][9];
     for (int which = 0; which < 2; ++which) {
         const uint32_t n_in = which ? 3u + 4u * (uint32_t)n : 2u + 2u * (uint32_t)n;
         if (n <= JJS_MSIG_MAX_PARTICIPANTS) memcpy(tags[which], JJS_SPONGE_TAG_LONG[n_in], sizeof(tags[which]));
         else safe_tag_limbs(n_in, JJS_Q_WORDS, tags[which]);
     }
-    device_restore restore;
-    auto free_copies = [&] {               // nothing has been published: no launch of anybody else reads these
-        for (msig_group_copy& c : k->copies)
-            if (c.mem) { (void)hipSetDevice(c.dev->device); (void)hipFree(c.mem); c.mem = nullptr; }
-    };
-    rc = no_throw([&]() -> int {
-        for (device_state* d : devs) {
-            g = d;
-            HIP_TRY(hipSetDevice(d->device));
-            hipStream_t s = nullptr;
-            HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-            k->copies.emplace_back();
-            const int brc = msig_group_build_copy(*k, k->copies.back(), pk, tags, k->agg_pk, s);
-            (void)hipStreamDestroy(s);
-            if (brc) { k->copies.pop_back(); return brc; }
-        }
-        return JJS_OK;
-    });
-    if (rc) { free_copies(); return rc; }
-    std::lock_guard<std::mutex> lock(L.mu);
-    if (L.devs != devs) { free_copies(); return fail(JJS_ERR_NOT_INIT, "the engine's devices changed while the signer group was built"); }
-    rc = no_throw([&]() -> int {
-        size_t slot = 0;
-        while (slot < g_msig_groups.size() && g_msig_groups[slot]) ++slot;
-        if (slot == g_msig_groups.size()) g_msig_groups.emplace_back();
-        if (++g_keyset_generation == 0) ++g_keyset_generation;       // 0 is never a generation: no valid handle is 0
-        k->generation = g_keyset_generation;
-        *out = ((uint64_t)k->generation << 32) | (uint64_t)(slot + 1);
-        g_msig_groups[slot] = std::move(k);
-        return JJS_OK;
-    });
-    if (rc) free_copies();
-    return rc;
+    if (int rc = call.build([&](msig_group_copy& c, hipStream_t s) { return msig_group_build_copy(k, c, pk, tags, k.agg_pk, s); })) return rc;
+    return call.publish(g_msig_groups, "signer group", out);
 }
 
 int jjs_msig_group_destroy(jjs_msig_group h) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
-    msig_group_entry* k = find_msig_group(h);
-    if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed signer group");
-    retire_msig_group(*k);     // launches already queued still read it: freed by jjs_trim / jjs_shutdown
-    g_msig_groups[(h & 0xffffffffu) - 1].reset();
+    if (!g_msig_groups.destroy(h)) return fail(JJS_ERR_ARG, "unknown or destroyed signer group");
     return JJS_OK;
 }
 
 int jjs_msig_group_info(jjs_msig_group h, uint64_t out[JJS_MSIG_GROUP_INFO]) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
-    msig_group_entry* k = find_msig_group(h);
+    msig_group_entry* k = g_msig_groups.find(h);
     if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed signer group");
     if (!out) return fail(JJS_ERR_ARG, "null pointer");
     out[JJS_MSIG_GROUP_PARTICIPANTS] = k->participants;
@@ -174,7 +105,7 @@ int jjs_msig_group_info(jjs_msig_group h, uint64_t out[JJS_MSIG_GROUP_INFO]) {
 int jjs_msig_group_aggregate_pk(jjs_msig_group h, uint8_t out[64]) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
-    msig_group_entry* k = find_msig_group(h);
+    msig_group_entry* k = g_msig_groups.find(h);
     if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed signer group");
     if (!out) return fail(JJS_ERR_ARG, "null pointer");
     memcpy(out, k->agg_pk, 64);
@@ -185,7 +116,7 @@ int jjs_msig_group_combine_dev(jjs_msig_group h, const void* z, const void* R, c
                                void* share_status, void* transcript_status, void* sig_u, void* sig_R, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
-    msig_group_entry* k = find_msig_group(h);
+    msig_group_entry* k = g_msig_groups.find(h);
     if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed signer group");
     if (n_transcripts == 0) return JJS_OK;
     const uint64_t per = k->participants;
@@ -193,7 +124,7 @@ int jjs_msig_group_combine_dev(jjs_msig_group h, const void* z, const void* R, c
         return fail(JJS_ERR_ARG, "%zu transcripts of %llu participants: the shares are indexed with 32 bits", n_transcripts, (unsigned long long)per);
     const size_t n = n_transcripts * per;
     if (!all_ok(z, R, S, m, sig_u, sig_R) || !share_status) return fail(JJS_ERR_ARG, "null or misaligned pointer");
-    const msig_group_copy* c = msig_group_copy_for(*k, g);
+    const msig_group_copy* c = copy_for(*k, g);
     if (!c) return fail(JJS_ERR_ARG, "the signer group has no copy on this device");
     hipStream_t s = (hipStream_t)stream;
     if (int rc = ensure_msig_scratch(n, n_transcripts)) return rc;
@@ -204,10 +135,8 @@ int jjs_msig_group_combine_dev(jjs_msig_group h, const void* z, const void* R, c
     P.share_status = (uint8_t*)share_status; P.sig_u = (uint8_t*)sig_u; P.sig_R = (uint8_t*)sig_R;
     P.transcript_status = (uint8_t*)transcript_status;
     P.agg_pk = c->agg_pk;                                            // read only: the group's
-    uint32_t* w = (uint32_t*)g->msig + (1 + 8 + EXT_WORDS) * g->msig_items;      // the layout of jjs_multisig_combine_dev
-    P.e_pt = w; w += EXT_WORDS * g->msig_items;
-    P.a_words = w; w += 8 * g->msig_transcripts;
-    P.c_words = w;
+    const msig_scratch W = msig_scratch_carve();
+    P.e_pt = W.e_pt; P.a_words = W.a_words; P.c_words = W.c_words;
     P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
     G.participants = (uint32_t)per;
     G.d_words = c->d_words; G.tables = c->tables; G.tag_a = c->tag_a + 9;
@@ -225,7 +154,7 @@ int jjs_msig_group_combine_dev(jjs_msig_group h, const void* z, const void* R, c
         }
         const size_t count = pass == 1 ? n : n_transcripts;
         // a pass with a hash chain and few items: eight lanes per item (multisig_core.h hash_lanes)
-        P.hash_lanes = ((pass == 0 || pass == 2) && count <= MSIG_COOP_MAX_ITEMS) ? 8u : 1u;
+        P.hash_lanes = (pass == 0 || pass == 2) ? msig_hash_lanes(count) : 1u;
         hipLaunchKernelGGL(msig_group_kernel, dim3(grid_for(g->grid_msig, count * P.hash_lanes)), dim3(BLOCK), 0, s, G, pass);
     }
     const hipError_t e = hipGetLastError();

@@ -138,7 +138,7 @@ static int verdict_launch_msm(int scheme, const void* const* d, size_t n, uint32
 // The per-item route on stream s (under L.mu): the resident call with its tally in the slot, then the verdict from the tally.
 static int verdict_launch_items(int scheme, const void* const* d, size_t n, uint32_t* verdict, hipStream_t s) {
     staged_call C;
-    if (int rc = SHAPES[scheme][JJS_FORMAT_AFFINE].build(d, n, nullptr, nullptr, s, C)) return rc;
+    if (int rc = build_call(SHAPES[scheme][JJS_FORMAT_AFFINE], d, n, nullptr, nullptr, s, C)) return rc;
     if (int rc = ensure_verdict(256)) return rc;
     unsigned long long* tally = reinterpret_cast<unsigned long long*>(sl->verdict);
     C.P.tally = tally;
@@ -170,7 +170,7 @@ static int verdict_dev(int scheme, const void* const* d, size_t n, void* verdict
     });
 }
 
-// The verdict algorithm's route of a blocking host call that has counted itself among g_keyset_host_calls: the columns go
+// The verdict algorithm's route of a blocking host call that has counted itself among g_blocking_calls: the columns go
 // whole to dev's key-set staging area (one such call at a time per device, host_mu), launch(k, c, d, verdict word, stream)
 // runs under L.mu, the verdict comes back.  Verdict 1: every status is 0; verdict 0: the statuses come from per_item().
 extern "C++" {
@@ -179,7 +179,7 @@ static int verdict_host_msm(device_state* dev, const jjs_keyset* ks, const size_
                             Launch launch, PerItem per_item, uint8_t* status, int* verdict) {
     int v = 0;
     {
-        keyset_host_call_leave leave_on_every_way_out;
+        blocking_call_leave leave_on_every_way_out;
         std::lock_guard<std::mutex> big(dev->host_mu);
         g = dev;
         int rc = no_throw([&]() -> int {
@@ -219,7 +219,7 @@ static int verdict_host(int scheme, const uint8_t* const* ptrs, size_t n, uint8_
         if (n == 0) { *verdict = 1; return JJS_OK; }
         msm = L.devs.size() == 1 && verdict_route(scheme, n);
         dev = g;
-        if (msm) ++g_keyset_host_calls;       // jjs_shutdown does not free `dev` before this call has left
+        if (msm) ++g_blocking_calls;       // jjs_shutdown does not free `dev` before this call has left
     }
     uint64_t tally[4] = {};
     auto per_item = [&] { return host_call(scheme, JJS_FORMAT_AFFINE, ptrs, n, status, tally); };

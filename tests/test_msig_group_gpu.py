@@ -265,6 +265,74 @@ def test_destroy_trim_and_stale_handles(eng):
     assert lib.jjs_trim() == 0
 
 
+def test_handles_of_one_kind_are_unknown_to_the_other(eng):
+    """Key sets and signer groups share one registry type and one generation counter: a live handle of either kind is an
+    unknown handle to every entry point of the other (JJS_ERR_ARG, nothing destroyed, nothing launched), also after one
+    kind's index has been freed and the other kind has registered again.  Two keys, two participants, one item, one transcript."""
+    import torch
+    from jubjub_schnorr_amd import _ffi
+    lib = _ffi.lib()
+    b = make_batch("single", 2, seed=77, n_keys=2, mix=False)
+    ks = eng.keyset("single", b["PK"])
+    assert ks.key_status.tolist() == [0, 0]
+    gc = gcs.group_transcripts(2, 1, seed=230, threads=THREADS)
+    rc, grp = create(lib, gc.PK)
+    assert rc == 0 and grp and ks.handle and grp != ks.handle
+    kd = [dev(x) for x in (np.zeros(1, np.int32), b["u"][:1], b["R"][:1], b["m"][:1])]           # key_idx, u, R, m
+    gd = [dev(x) for x in gc.call_args()]
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    info = (ctypes.c_uint64 * 8)()
+    out64 = np.zeros(64, np.uint8)
+
+    def keyset_calls(h):
+        """rc of jjs_keyset_info, _verify_dev, _verify_all_dev on handle h, and what the two calls wrote (prefilled 0xA5)."""
+        st = torch.full((16,), 0xA5, dtype=torch.uint8, device="cuda")
+        tally = torch.full((4,), -1, dtype=torch.int64, device="cuda")
+        verdict = torch.full((1,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+        rcs = [lib.jjs_keyset_info(h, info),
+               lib.jjs_keyset_verify_dev(h, 0, _ptr(kd[0]), _ptr(kd[1]), _ptr(kd[2]), None, _ptr(kd[3]), 1, _ptr(st), _ptr(tally), stream),
+               lib.jjs_keyset_verify_all_dev(h, 0, _ptr(kd[0]), _ptr(kd[1]), _ptr(kd[2]), None, _ptr(kd[3]), 1, _ptr(verdict), stream)]
+        torch.cuda.synchronize()
+        return rcs, (st.cpu().numpy().tobytes(), tally.cpu().numpy().tobytes(), verdict.cpu().numpy().tobytes())
+
+    def group_calls(h):
+        """rc of jjs_msig_group_info, _aggregate_pk, _combine_dev on handle h, and what they wrote (prefilled 0xA5)."""
+        out64[:] = 0xA5
+        rcs = [lib.jjs_msig_group_info(h, info), lib.jjs_msig_group_aggregate_pk(h, out64.ctypes.data_as(ctypes.c_void_p))]
+        rc, outs = abi_call(lib, h, gc, ins=gd)
+        return rcs + [rc], (out64.tobytes(),) + tuple(x.tobytes() for x in host(outs))
+
+    untouched_k = (b"\xa5" * 16, b"\xff" * 32, b"\x5a" * 4)
+    untouched_g = (b"\xa5" * 64, b"\xa5" * 2, b"\xa5" * 32, b"\xa5" * 64, b"\xa5")
+    rcs, first_k = keyset_calls(ks.handle)
+    assert rcs == [0, 0, 0]
+    assert first_k[0][0] == oracle_verify("single", b, threads=THREADS)[0] == 0
+    assert first_k[1] == np.array([1, 0, 0, 0], np.int64).tobytes() and first_k[2] == np.array([1], np.int32).tobytes()
+    got = run_and_check(eng, lib, gc, "one transcript of two", h=grp)
+    rcs, first_g = group_calls(grp)
+    assert rcs == [0, 0, 0] and first_g == (aggregate(lib, grp).tobytes(),) + tuple(x.tobytes() for x in got)
+
+    # the live key set is no signer group, the live signer group is no key set
+    assert group_calls(ks.handle) == ([-1, -1, -1], untouched_g) and lib.jjs_msig_group_destroy(ks.handle) == -1
+    assert keyset_calls(grp) == ([-1, -1, -1], untouched_k) and lib.jjs_keyset_destroy(grp) == -1
+    assert b"key set" in lib.jjs_last_error()
+    assert keyset_calls(ks.handle) == ([0, 0, 0], first_k) and group_calls(grp) == ([0, 0, 0], first_g)
+
+    # the key set's index is free again; the next signer group takes an index of its own registry and a new generation
+    old = ks.handle
+    assert lib.jjs_keyset_destroy(old) == 0
+    ks.handle = 0
+    rc, grp2 = create(lib, gc.PK)
+    assert rc == 0 and grp2 and grp2 not in (old, grp)
+    assert keyset_calls(old) == ([-1, -1, -1], untouched_k) and lib.jjs_keyset_destroy(old) == -1
+    assert group_calls(old) == ([-1, -1, -1], untouched_g) and lib.jjs_msig_group_destroy(old) == -1
+    assert keyset_calls(grp2) == ([-1, -1, -1], untouched_k) and lib.jjs_keyset_destroy(grp2) == -1
+    assert group_calls(grp) == ([0, 0, 0], first_g) and group_calls(grp2) == ([0, 0, 0], first_g)
+    assert lib.jjs_trim() == 0
+    assert group_calls(grp) == ([0, 0, 0], first_g) and group_calls(grp2) == ([0, 0, 0], first_g)
+    assert lib.jjs_msig_group_destroy(grp) == 0 and lib.jjs_msig_group_destroy(grp2) == 0
+
+
 def test_state_across_shutdown_in_a_fresh_process():
     p = subprocess.run([sys.executable, os.path.join(HERE, "msig_group_state_child.py")], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and p.stdout.strip().endswith("ok"), p.stdout[-3000:] + p.stderr[-3000:]
