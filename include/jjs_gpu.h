@@ -439,6 +439,9 @@ int jjs_debug_half_scalars_dev(const void* c, size_t n, void* a_out, void* b_out
  * jjs_debug_comb_table_bytes() */
 size_t jjs_debug_comb_table_bytes(void);
 int jjs_debug_comb_table(int which, void* host_out);
+/* copies the square-root tables of the current device (csrc/decode.h) to host memory: 7 x 256 x 9 uint32 of powers of the
+ * root of unity in Montgomery form, and the 65536-byte table of the logarithms in the order-256 subgroup */
+int jjs_debug_dlog_tables(void* pow_host_out, void* hash_host_out);
 /* Loads RCCL, forms a one-rank clique on the current device and all-reduces a known 4 x u64 vector on the
  * engine stream: the call sequence of the multi-device tally reduction, runnable with a single GPU. */
 int jjs_debug_rccl_selftest(void);

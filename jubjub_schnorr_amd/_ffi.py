@@ -62,6 +62,7 @@ SIGNATURES = {
     "jjs_debug_half_scalars_dev": [_P, _Z, _P, _P, _P, _P],
     "jjs_debug_comb_table_bytes": [],
     "jjs_debug_comb_table": [_I, _P],
+    "jjs_debug_dlog_tables": [_P, _P],
     "jjs_debug_rccl_selftest": [],
     "jjs_debug_msig_resident_lanes": [],
     "jjs_public_keys_dev": [_P, _Z, _P, _P, _P, _P],

@@ -363,6 +363,13 @@ class Engine:
         bits = 16 if nbytes == 16 * 65536 * 112 else 8          # digits of the fixed-base comb (csrc/verify_core.h)
         return out.reshape(256 // bits, 1 << bits, 28)
 
+    def debug_dlog_tables(self):
+        """The engine's square-root tables (csrc/decode.h): powers (7, 256, 9) uint32 in Montgomery form, logarithms (65536,) uint8."""
+        pw, hs = np.empty((7, 256, 9), np.uint32), np.empty(65536, np.uint8)
+        _ffi.check(self._lib.jjs_debug_dlog_tables(pw.ctypes.data_as(ctypes.c_void_p), hs.ctypes.data_as(ctypes.c_void_p)),
+                   "jjs_debug_dlog_tables")
+        return pw, hs
+
     def sync(self):
         _ffi.check(self._lib.jjs_stream_sync(self._stream()), "jjs_stream_sync")
 

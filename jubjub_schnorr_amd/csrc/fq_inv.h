@@ -136,6 +136,7 @@ JJS_HD s30 s30_from_limbs29(const fe_c& a) {
         const int bit = 30 * i, lo = bit / 29, sh = bit % 29;
         uint64_t w = (uint64_t)a.l[lo] >> sh;
         if (lo + 1 < 9) w |= (uint64_t)a.l[lo + 1] << (29 - sh);
+        // (never taken with nine limbs: sh = 30 i mod 29 = i <= 8, so two 29-bit limbs always cover a 30-bit one; it folds away)
         if (lo + 2 < 9 && 58 - sh < 30) w |= (uint64_t)a.l[lo + 2] << (58 - sh);
         r.v[i] = (int32_t)((uint32_t)w & 0x3fffffffu);
     }

@@ -1144,6 +1144,14 @@ int jjs_debug_comb_table(int which, void* host_out) {
     HIP_TRY(hipMemcpy(host_out, which ? g->comb_gn : g->comb_g, COMB_TABLE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return JJS_OK;
 }
+int jjs_debug_dlog_tables(void* pow_host_out, void* hash_host_out) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    if (!pow_host_out || !hash_host_out) return fail(JJS_ERR_ARG, "null pointer");
+    HIP_TRY(hipMemcpy(pow_host_out, g->dlog_pow, DLOG_POW_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hash_host_out, g->dlog_hash, 65536, hipMemcpyDeviceToHost));
+    return JJS_OK;
+}
 int jjs_debug_msig_resident_lanes(void) { std::lock_guard<std::mutex> lock(L.mu); if (int rc = check_ready()) return rc; return g->grid_msig * BLOCK; }
 
 }  // extern "C"

@@ -108,6 +108,31 @@ def torsion_generator():
         v += 1
 
 
+def wire_point_cases(rng, n_random=64):
+    """Compressed encodings covering every decode branch, with the oracle's answer."""
+    enc = []
+    for _ in range(n_random):
+        p = o.mul(o.G, int.from_bytes(rng.bytes(31), "little") + 1)
+        enc.append(o.compress(p))
+    t8 = torsion_generator()
+    enc += [o.compress(o.mul(t8, k)) for k in range(8)]              # small-order points decode fine
+    enc += [o.compress(o.IDENTITY), o.compress(o.ORDER2)]
+    ident_bad = bytearray(o.compress(o.IDENTITY)); ident_bad[31] |= 0x80   # u = 0, sign bit set
+    o2_bad = bytearray(o.compress(o.ORDER2)); o2_bad[31] |= 0x80
+    enc += [bytes(ident_bad), bytes(o2_bad)]
+    enc.append(o.le32(o.Q))                                              # v = q (non canonical)
+    enc.append(bytes([0xFF] * 31 + [0x7F]))                              # v = 2^255 - 1
+    v = 2
+    while len(enc) < n_random + 24:                                      # v with no square root
+        b = o.le32(v)
+        if o.decompress(b) is None:
+            enc.append(b)
+        v += 1
+    for i in range(n_random // 2):                                      # sign bit flipped -> the negated point
+        b = bytearray(enc[i]); b[31] ^= 0x80; enc.append(bytes(b))
+    return enc
+
+
 def make_batch(scheme: str, n: int, seed: int = SEED, n_keys: int = 64, mix: bool = True):
     """Deterministic synthetic batch: K distinct keys, item i uses key i mod K,
     uniform messages, oracle signatures, then a fixed mix of corruptions.  Returns a dict of

@@ -15,6 +15,7 @@
 #include "jjs_sponge_tags_long.inc"
 #include "safe_tag.h"
 #include "../../jubjub_schnorr_amd/tools/scalar_stages.h"
+#include "../../jubjub_schnorr_amd/tools/ingest_stages.h"
 
 using namespace jjs;
 
@@ -181,8 +182,75 @@ struct host_records {
     }
 };
 
+// the square-root tables of the CPU build: every entry by dlog_table_entry after a cleared hash, as the device fills them
+static dlog_tables host_dlog() {
+    static std::vector<uint32_t> pw;
+    static std::vector<uint8_t> hs;
+    if (pw.empty()) {
+        pw.resize(DLOG_POW_WORDS); hs.assign(ig::DLOG_HASH_BYTES, 0);
+        for (int i = 0; i < 7; ++i) for (int j = 0; j < 256; ++j) dlog_table_entry(pw.data(), hs.data(), i, j);
+    }
+    return dlog_tables{pw.data(), hs.data()};
+}
+
+// tools/ingest_stages.h on this thread: items and lanes one after the other
+struct host_ingest {
+    const uint32_t* in;
+    size_t in_words, pos = 0;
+    int records = 0;
+    std::vector<uint32_t> out;
+    ig::ctx C;
+    template <typename S>
+    int step(uint32_t n) {
+        if (!ig::record_fits<S>(in_words, pos, n)) return 1;
+        uint32_t res[S::OUT];
+        for (uint32_t i = 0; i < n; ++i) {
+            memset(res, 0xff, sizeof(res));
+            S::run(C, in + pos + (size_t)S::IN * i, res);
+            out.insert(out.end(), res, res + S::OUT);
+        }
+        pos += (size_t)S::IN * n;
+        return 0;
+    }
+    int normalize(uint32_t n_src, uint32_t rows) {
+        ig::norm_header H;
+        if (!ig::norm_fits(in_words, pos, n_src, rows, in, H)) return 1;
+        const size_t iw = ig::norm_in_words(n_src, rows), ew = iw - ig::NORM_HEADER, ow = ig::norm_out_words(n_src, rows);
+        std::vector<uint32_t> ext(ew + 4), res(ow + 4), scratch(ig::norm_scratch_words(rows));
+        uint32_t* ep = (uint32_t*)(((uintptr_t)ext.data() + 15) & ~(uintptr_t)15);
+        uint32_t* rp = (uint32_t*)(((uintptr_t)res.data() + 15) & ~(uintptr_t)15);
+        memcpy(ep, in + pos + ig::NORM_HEADER, 4 * ew);
+        ig::norm_prefill(H, rp);
+        const normalize_params P = ig::norm_params(H, ep, rp, scratch.data());
+        for (uint32_t lane = 0; lane < H.lanes; ++lane) normalize_lane(P, lane, H.lanes);
+        out.insert(out.end(), rp, rp + ow);
+        pos += iw;
+        return 0;
+    }
+    int tables(uint32_t n) {
+        if (n != 1) return 1;
+        out.insert(out.end(), C.T.pow, C.T.pow + DLOG_POW_WORDS);
+        const size_t at = out.size();
+        out.resize(at + ig::DLOG_HASH_BYTES / 4);
+        memcpy(out.data() + at, C.T.hash, ig::DLOG_HASH_BYTES);
+        return 0;
+    }
+};
+
 extern "C" {
 
+// the records of tools/ingest_stages.h (inversion, inverse square roots, decoding, normalisation, the square-root tables);
+// returns 0 and the number of output words, or the failing record's code
+int jjs_host_ingest_records(const uint32_t* in, size_t in_words, uint32_t* out, size_t out_cap, size_t* out_words) {
+    host_ingest x{in, in_words};
+    x.C = ig::ctx{host_dlog()};
+    const int rc = ig::run_records(x);
+    if (rc) return rc;
+    if (x.out.size() > out_cap) return 4;
+    memcpy(out, x.out.data(), 4 * x.out.size());
+    *out_words = x.out.size();
+    return 0;
+}
 // the records of tools/scalar_stages.h (the product's scalar multiplications with caller-chosen scalars); returns 0 and the
 // number of output words, or the failing record's code
 int jjs_host_scalar_records(const uint32_t* in, size_t in_words, uint32_t* out, size_t out_cap, size_t* out_words) {
@@ -338,13 +406,7 @@ int jjs_host_half_size(const uint8_t* c, size_t n, uint8_t* out) {
 }
 // compressed (n x 32) -> affine (n x 64) + ok byte
 int jjs_host_decompress(const uint8_t* in, size_t n, uint8_t* out, uint8_t* ok) {
-    static std::vector<uint32_t> pw;
-    static std::vector<uint8_t> hs;
-    if (pw.empty()) {
-        pw.resize(DLOG_POW_WORDS); hs.assign(65536, 0);
-        for (int i = 0; i < 7; ++i) for (int j = 0; j < 256; ++j) dlog_table_entry(pw.data(), hs.data(), i, j);
-    }
-    const dlog_tables T{pw.data(), hs.data()};
+    const dlog_tables T = host_dlog();
     for (size_t i = 0; i < n; ++i) {
         words8 w;
         memcpy(w.w, in + 32 * i, 32);

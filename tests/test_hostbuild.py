@@ -7,7 +7,7 @@ import hostlib as hl
 import jjs_oracle as o
 import jjs_oracle_c as oc
 from helpers import (edge_cases, edge_limb_vectors, fe_arr, fe_bytes, limbs_val, make_batch, oracle_verify, pt_arr, rand_mod,
-                     to_int, torsion_generator, torsion_grid)
+                     to_int, torsion_generator, torsion_grid, wire_point_cases)
 
 
 def special_fq(rng, n):
@@ -172,31 +172,6 @@ def test_half_size_scalars():
     assert n_special >= 15 and len(c) >= 3000
     out = hl.half_size(c)
     check_half_size(c, out[:, :16], out[:, 16:32], out[:, 32])
-
-
-def wire_point_cases(rng, n_random=64):
-    """Compressed encodings covering every decode branch, with the oracle's answer."""
-    enc = []
-    for _ in range(n_random):
-        p = o.mul(o.G, int.from_bytes(rng.bytes(31), "little") + 1)
-        enc.append(o.compress(p))
-    t8 = torsion_generator()
-    enc += [o.compress(o.mul(t8, k)) for k in range(8)]              # small-order points decode fine
-    enc += [o.compress(o.IDENTITY), o.compress(o.ORDER2)]
-    ident_bad = bytearray(o.compress(o.IDENTITY)); ident_bad[31] |= 0x80   # u = 0, sign bit set
-    o2_bad = bytearray(o.compress(o.ORDER2)); o2_bad[31] |= 0x80
-    enc += [bytes(ident_bad), bytes(o2_bad)]
-    enc.append(o.le32(o.Q))                                              # v = q (non canonical)
-    enc.append(bytes([0xFF] * 31 + [0x7F]))                              # v = 2^255 - 1
-    v = 2
-    while len(enc) < n_random + 24:                                      # v with no square root
-        b = o.le32(v)
-        if o.decompress(b) is None:
-            enc.append(b)
-        v += 1
-    for i in range(n_random // 2):                                      # sign bit flipped -> the negated point
-        b = bytearray(enc[i]); b[31] ^= 0x80; enc.append(bytes(b))
-    return enc
 
 
 def test_decompress_matches_oracle():
