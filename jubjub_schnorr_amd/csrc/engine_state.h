@@ -1,6 +1,7 @@
 // Part of jjs_gpu.hip (included inside its anonymous namespace): what the library owns between jjs_init and jjs_shutdown --
 // per-device state, call slots, the staging threads of the host-buffer calls, the RCCL handle -- and the helpers every
-// launch uses (errors, grids, slot ordering, grow-only buffers, the latency path's launch).
+// launch uses (errors, grids, slot ordering, the retired list, the latency path's launch).  Memory, streams and events are held by
+// the owner types of device_owners.h.
 #pragma once
 // ---------------------------------------------------------------------------------------------
 // Per-device state: everything a launch on that device needs (tables, per-lane workspace, scratch).
@@ -79,34 +80,36 @@ public:
 struct key_feedback {
     uint32_t counters[16];
 };
+#ifndef JJS_SMALL_SLOTS
+#define JJS_SMALL_SLOTS 6
+#endif
+constexpr int N_SMALL_SLOTS = JJS_SMALL_SLOTS;   // six since round 4: host threads with a few signatures per call keep more than three in flight
+constexpr size_t SMALL_SLOT_ITEMS = 16384;
+// A slot's wire area (wire and ext entry points, calls against a key set), per item: four point columns of 64 bytes, 16 bytes
+// of flags (the first: the encoding was rejected) and the prefix products of the normalisation (normalize.h) -- one area for
+// the key columns and one for the others, whose launches may overlap in a host-buffer call.
+constexpr size_t WIRE_FLAGS_AT = 4 * 64, WIRE_SCRATCH_AT = 4 * 64 + 16, WIRE_SCRATCH_BYTES = 48, WIRE_ITEM_BYTES = WIRE_SCRATCH_AT + 2 * WIRE_SCRATCH_BYTES;
 struct call_slot {
-    uint32_t* workspace = nullptr;    // WS_WORDS_PER_LANE words per lane of the verify grid
+    device_mem<uint32_t> workspace;   // WS_WORDS_PER_LANE words per lane of the verify grid
     int grid_verify = 0;              // blocks of verify_kernel that fit this workspace
-    uint64_t* pending = nullptr;      // queue of the resolve pass: [0] = count, then one entry per queued item
-    size_t pending_items = 0;
-    uint8_t* prep = nullptr;          // prepare_kernel -> verify_kernel records, 65 bytes per item (grow-only)
-    size_t prep_items = 0;
-    uint8_t* wire = nullptr;          // decoded / normalised points (4 x n x 64), flags, scratch: wire and ext entry points
-    size_t wire_items = 0;
-    uint8_t* small = nullptr;         // latency path: window tables of the chain lanes + per-point verdicts (grow-only)
-    size_t small_bytes = 0;
-    uint8_t* verdict = nullptr;       // batch verdict (verdict_calls.h): MSM terms, sort, buckets, or the per-item route's tally (grow-only)
-    size_t verdict_bytes = 0;
+    // The grow-only buffers, each with its rule: the least capacity, the bytes of a unit, the slack behind the units.
+    grow_only<uint64_t> pending{{SMALL_SLOT_ITEMS, sizeof(uint64_t), 2 * sizeof(uint64_t)}};   // queue of the resolve pass: [0] = count, then one entry per queued item
+    grow_only<uint8_t> prep{{SMALL_SLOT_ITEMS, 65, 64}};      // prepare_kernel -> verify_kernel records, 65 bytes per item
+    grow_only<uint8_t> wire{{4096, WIRE_ITEM_BYTES, 0}};      // decoded / normalised points (4 x n x 64), flags, scratch: wire and ext entry points
+    grow_only<uint8_t> small;         // latency path: window tables of the chain lanes + per-point verdicts (bytes)
+    grow_only<uint8_t> verdict;       // batch verdict (verdict_calls.h): MSM terms, sort, buckets, or the per-item route's tally (bytes)
     // key-table path (big and medium slots).  Two arenas, both grow-only: the index (hash tables, key ids, item order:
     // sized by the batch) and the pool of per-key bases and window tables, which is sized by the number of distinct keys
     // the slot's calls have carried -- KEY_POOL_INITIAL_BYTES to begin with, more once a call has shown that it needs more.
-    uint8_t* keys = nullptr;
-    size_t keys_bytes = 0;
-    uint8_t* key_pool = nullptr;
-    size_t key_pool_bytes = 0;
+    grow_only<uint8_t> keys;
+    device_mem<uint8_t> key_pool;
     size_t key_pool_want = 0;         // what the last call that found the pool too small would have needed
     size_t key_pool_refused = 0;      // a size hipMalloc turned down (not asked for again)
     // The memo of the slot's last key-table call (key_tables.h step 5): device memory beside the pool, replaced and freed with it.
     // Only the slot's own kernels touch it, in the order of the slot's calls (last_use), which is also the order in which they
     // write the pool: a queued call reads the tables its own match step found claimed, and no later call of the slot -- the only
     // other writer of this pool -- starts before that call has ended.  Another slot has another pool and another memo.
-    uint8_t* key_memo = nullptr;
-    size_t key_memo_bytes = 0;
+    device_mem<uint8_t> key_memo;
     uint32_t memo_cap = 0;            // pool indices per column its arrays hold
     uint64_t memo_seed = 0;           // of its hash: drawn once, with the slot's first key-table call
     bool memo_seeded = false;
@@ -114,23 +117,18 @@ struct call_slot {
     uint32_t memo_cols = 0;           // key columns of that call: another number is another pool layout
     bool memo_flush = true;           // the next call must not trust the memo: the pool is new, or a call was abandoned half-way
     bool memo_dirty = false;          // ... and the memory is fresh from hipMalloc: the next call clears it on its key stream
-    key_feedback* seen = nullptr;     // pinned host memory
+    pinned_mem<key_feedback> seen;    // zero-filled at creation; only in slots that have a key stream
     bool seen_pending = false;        // `seen` is being written by a call that may still run (its end: last_use)
     bool keys_repeated = true;        // the slot's last key-table attempt that has ended built tables (launch_staged)
     uint64_t seen_n = 0;              // ... whose batch had this many items in
     uint32_t seen_cols = 0;           // ... this many key columns
-    hipStream_t key_stream = nullptr; // the per-key kernels of the slot's call run here, beside the challenge hashes
-    hipEvent_t key_fork = nullptr, key_mid = nullptr, key_join = nullptr, key_ahead = nullptr, key_chains = nullptr, key_cleared = nullptr;
-    hipStream_t table_stream = nullptr;   // key_table_kernel runs here, at the lowest priority: see job_keys
-    hipEvent_t last_use = nullptr;    // end of the last launch that used this slot
-    hipStream_t last_stream = nullptr;// ... and the stream it was issued on
+    stream_owner key_stream;          // the per-key kernels of the slot's call run here, beside the challenge hashes
+    event_owner key_fork, key_mid, key_join, key_ahead, key_chains, key_cleared;
+    stream_owner table_stream;        // key_table_kernel runs here, at the lowest priority: see job_keys
+    event_owner last_use;             // end of the last launch that used this slot
+    hipStream_t last_stream = nullptr;// ... and the stream it was issued on (the caller's: not owned)
     bool host_owned = false;          // a large host-buffer call is feeding this slot right now, outside the engine's mutex (run_host)
 };
-#ifndef JJS_SMALL_SLOTS
-#define JJS_SMALL_SLOTS 6
-#endif
-constexpr int N_SMALL_SLOTS = JJS_SMALL_SLOTS;   // six since round 4: host threads with a few signatures per call keep more than three in flight
-constexpr size_t SMALL_SLOT_ITEMS = 16384;
 // Calls of up to MEDIUM_SLOT_ITEMS items take one of N_MEDIUM_SLOTS medium slots in turn: such a call is a few waves
 // per SIMD at most and is bound by the latency of one signature (~1.7 ms), so calls on different streams overlap almost
 // freely.  A medium slot has everything the big one has (workspace, key arena) for its size.
@@ -166,12 +164,10 @@ constexpr size_t SMALL_PATH_MAX_ITEMS_VARGEN = 16384, SMALL_PATH_FINE_ITEMS_VARG
 // different shapes, and calls too large to combine, run side by side.  Every caller gets its own statuses and its own tally
 // (counted on the host from its statuses).
 struct host_lane {
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;        // end of the launch in progress on the lane
-    uint8_t* dev = nullptr;           // device area: the columns of the launch, its statuses (grow-only)
-    size_t dev_bytes = 0;
-    uint8_t* pinned = nullptr;        // pinned host area, same layout (grow-only)
-    size_t pinned_bytes = 0;
+    stream_owner stream;
+    event_owner done;                 // end of the launch in progress on the lane
+    grow_only<uint8_t> dev{{size_t(1) << 20}};            // device area: the columns of the launch, its statuses (bytes)
+    grow_only<uint8_t, true> pinned{{size_t(1) << 20}};   // pinned host area, same layout
     // the launch that is being put together / runs on the lane
     enum : int { FREE = 0, OPEN = 1, LAUNCHED = 2, DONE = 3 };
     int state = FREE;
@@ -241,20 +237,20 @@ struct device_state {
     int device = -1;               // HIP device ordinal
     call_slot slots[N_SLOTS];          // [0] big, then the small ones, then the medium ones, then the second big one
     unsigned next_small = 0, next_medium = 0, next_big = 0;
-    hipStream_t stream = nullptr;  // used by the host-buffer entry points
-    hipStream_t side[HOST_SIDE_STREAMS] = {};   // ... whose ranges go to `stream` and these in turn (run_host_block)
-    hipStream_t ingest[2] = {};                 // ... and whose extended points are normalised here, ahead of the hashes (priority)
-    hipEvent_t host_begin = nullptr;
-    uint32_t* comb_g = nullptr;
-    uint32_t* comb_gn = nullptr;
-    uint8_t* tag = nullptr;
-    unsigned long long* tally = nullptr;
+    stream_owner stream;           // used by the host-buffer entry points
+    stream_owner side[HOST_SIDE_STREAMS];       // ... whose ranges go to `stream` and these in turn (run_host_block)
+    stream_owner ingest[2];                     // ... and whose extended points are normalised here, ahead of the hashes (priority)
+    event_owner host_begin;
+    device_mem<uint32_t> comb_g;
+    device_mem<uint32_t> comb_gn;
+    device_mem<uint8_t> tag;
+    device_mem<unsigned long long> tally;
     int grid_sign = 0, grid_resolve = 0, grid_prepare = 0, grid_key_verify = 0;
-    hipEvent_t last_use = nullptr;  // host-buffer calls: end of the last use of the staging arena and the counters
-    uint32_t* dlog_pow = nullptr;  // square-root tables (decode.h)
-    uint8_t* dlog_hash = nullptr;
-    uint32_t* tags_long = nullptr; // SAFE tags for long transcripts (multisig)
-    uint8_t* msig = nullptr;       // multisig scratch
+    event_owner last_use;          // host-buffer calls: end of the last use of the staging arena and the counters
+    device_mem<uint32_t> dlog_pow; // square-root tables (decode.h)
+    device_mem<uint8_t> dlog_hash;
+    device_mem<uint32_t> tags_long;// SAFE tags for long transcripts (multisig)
+    device_mem<uint8_t> msig;      // multisig scratch: grows in two dimensions (ensure_msig_scratch)
     size_t msig_items = 0, msig_transcripts = 0;
     int grid_msig = 0;
     int key_priority = 0;                // stream priority of the slots' key streams
@@ -263,14 +259,12 @@ struct device_state {
     std::atomic<uint64_t> memo_stats[2] = {};           // keys the key-table calls found in their slot's memo / built (note_key_feedback)
     std::mutex host_mu;                  // large host-buffer calls: one at a time per device (they share the staging below)
     std::mutex retired_mu;               // guards `retired`
-    hipStream_t copy_stream = nullptr;   // host-buffer calls: uploads and status downloads, beside `stream`
-    hipEvent_t side_join = nullptr, ingest_done = nullptr;
-    staging_pool* stagers = nullptr;     // host-buffer calls: the threads that copy pageable -> pinned with the caller's
-    uint8_t* stage = nullptr;            // host-buffer calls: device copies of the inputs + statuses (grow-only)
-    size_t stage_bytes = 0;
-    uint8_t* pinned = nullptr;           // host-buffer calls: pinned host staging (two input slots + statuses, grow-only)
-    size_t pinned_bytes = 0;
-    hipEvent_t chunk_up[HOST_MAX_PIECES] = {}, chunk_done[HOST_MAX_PIECES] = {};   // per piece of a host-buffer call: uploaded, converted
+    stream_owner copy_stream;            // host-buffer calls: uploads and status downloads, beside `stream`
+    event_owner side_join, ingest_done;
+    grow_only<uint8_t> stage;            // host-buffer calls: device copies of the inputs + statuses (bytes)
+    grow_only<uint8_t, true> pinned;     // host-buffer calls: pinned host staging (two input slots + statuses)
+    std::unique_ptr<staging_pool> stagers;   // host-buffer calls: the threads that copy pageable -> pinned with the caller's
+    event_owner chunk_up[HOST_MAX_PIECES], chunk_done[HOST_MAX_PIECES];   // per piece of a host-buffer call: uploaded, converted
     host_lane lanes[N_HOST_LANES];       // small and medium host-buffer calls: one lane per launch in flight or filling
     std::atomic<uint64_t> lane_epoch{0}; // bumped (under the engine's mutex) whenever a lane changes state: what lane leaders and callers without a lane poll
     std::atomic<int> lane_spinners{0};   // threads polling for a lane right now (at most LANE_MAX_SPINNERS; the others sleep)
@@ -279,9 +273,8 @@ struct device_state {
     std::chrono::steady_clock::time_point lane_last_done[3][3] = {};   // come back, and the next lane waits for them (COMBINE_WINDOW_US)
     std::vector<retired_buffer> retired; // replaced buffers, freed by jjs_trim / jjs_shutdown
     size_t retired_bytes = 0;
-    hipStream_t ks_stream = nullptr;     // host-buffer calls on a registered key set (jjs_keyset_verify): uploads, launch, statuses
-    uint8_t* ks_stage = nullptr;         // ... their device copies of the inputs and outputs (grow-only; under host_mu)
-    size_t ks_stage_bytes = 0;
+    stream_owner ks_stream;              // host-buffer calls on a registered key set (jjs_keyset_verify): uploads, launch, statuses
+    grow_only<uint8_t> ks_stage;         // ... their device copies of the inputs and outputs (bytes; under host_mu)
 };
 
 // RCCL is needed only when one process drives several devices, so it is loaded on demand.
@@ -399,14 +392,7 @@ int end_shared(hipStream_t s) {
     return JJS_OK;
 }
 
-// Grow-only buffers: the replacement is allocated first, the old buffer is retired (launches in flight may still use it; it
-// is freed by jjs_trim / jjs_shutdown).  No call waits for the device here.
-size_t grown(size_t want) {              // the smallest of 2^k, 1.5 * 2^k that holds `want`: what is retired stays below what is live
-    size_t cap = 4096;
-    while (cap < want) cap <<= 1;
-    const size_t mid = cap / 4 * 3;
-    return mid >= want ? mid : cap;
-}
+// What a grow-only buffer or a destroyed object leaves behind (device_owners.h) is filed here, under the device it belongs to.
 void retire(void* p, bool host, size_t bytes) {
     if (!p) return;
     std::lock_guard<std::mutex> lock(g->retired_mu);
@@ -426,16 +412,6 @@ void free_retired(device_state& d) {      // the caller has made sure that the d
     d.retired.clear();
     d.retired_bytes = 0;
 }
-template <typename T>
-int regrow(T*& buf, size_t& have, size_t old_bytes, size_t want_units, size_t bytes) {
-    T* fresh = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&fresh), bytes));
-    retire(buf, false, old_bytes);
-    buf = fresh;
-    have = want_units;
-    return JJS_OK;
-}
-
 // Registered objects: key sets (keyset.h; jjs_keyset_*) and multisig signer groups (msig_group.h; jjs_msig_group_*).  An object
 // is immutable once built and has one copy per driven device.  Handles are (generation << 32) | (registry index + 1): a
 // destroyed object's index may be reused, its generation never is, so a stale handle finds nothing (JJS_ERR_ARG) and never
@@ -444,8 +420,7 @@ int regrow(T*& buf, size_t& have, size_t old_bytes, size_t want_units, size_t by
 // that launches already queued on a stream still read valid tables, and freed by jjs_trim / jjs_shutdown.
 struct device_copy {
     device_state* dev = nullptr;
-    uint8_t* mem = nullptr;                // one allocation: the regions its owner carves from it
-    size_t bytes = 0;
+    device_mem<uint8_t> mem;               // one allocation: the regions its owner carves from it
 };
 template <class Copy>
 struct registered {
@@ -473,7 +448,7 @@ struct registry {                          // every member: under L.mu
     }
     static void retire_copies(Entry& e) {             // the devices of its copies are alive
         device_state* const keep = g;
-        for (auto& c : e.copies) { g = c.dev; retire(c.mem, false, c.bytes); c.mem = nullptr; }
+        for (auto& c : e.copies) { g = c.dev; c.mem.release(); }
         g = keep;
     }
     bool destroy(uint64_t h) {             // launches already queued still read it: freed by jjs_trim / jjs_shutdown
@@ -520,8 +495,10 @@ struct msig_group_entry : registered<msig_group_copy> {
     uint8_t agg_pk[64] = {};
     uint64_t calls = 0;
 };
-registry<keyset_entry> g_keysets;
-registry<msig_group_entry> g_msig_groups;
+// (never destroyed: objects that are still registered when the process ends are left to it, like the devices of L.devs -- no
+// destructor frees device memory behind the runtime's own exit)
+registry<keyset_entry>& g_keysets = *new registry<keyset_entry>;
+registry<msig_group_entry>& g_msig_groups = *new registry<msig_group_entry>;
 // Blocking calls that hold a device pointer outside L.mu, between their first and last use of the mutex (the create calls, the
 // host-buffer calls against a key set, the verdict algorithm's host route): jjs_shutdown waits for them before it frees a
 // device.  Counted in under L.mu ...
@@ -533,24 +510,6 @@ struct blocking_call_leave {               // ... and out here, on every path
         L.lane_cv.notify_all();
     }
 };
-
-int ensure_pending(size_t n) {
-    if (n <= sl->pending_items) return JJS_OK;
-    const size_t cap = grown(n < SMALL_SLOT_ITEMS ? SMALL_SLOT_ITEMS : n);
-    return regrow(sl->pending, sl->pending_items, (sl->pending_items + 2) * sizeof(uint64_t), cap, (cap + 2) * sizeof(uint64_t));
-}
-
-int ensure_prep(size_t n) {
-    if (n <= sl->prep_items) return JJS_OK;
-    const size_t cap = grown(n < SMALL_SLOT_ITEMS ? SMALL_SLOT_ITEMS : n);
-    return regrow(sl->prep, sl->prep_items, sl->prep_items * 65 + 64, cap, cap * 65 + 64);
-}
-
-int ensure_small(size_t bytes) {
-    if (bytes <= sl->small_bytes) return JJS_OK;
-    const size_t cap = grown(bytes);
-    return regrow(sl->small, sl->small_bytes, sl->small_bytes, cap, cap);
-}
 
 // Latency path (small_batch.h): two launches, every signature spread over 11 (single) or 21 (double) lanes.
 // A call that is alone on the device spreads every signature over as many lanes as shorten its critical path: 8 pieces per
@@ -603,11 +562,11 @@ int launch_small(verify_params P, hipStream_t s) {
     const unsigned others = small_calls_in_flight();
     const uint32_t positions = small_positions(P, others);
     const size_t table_bytes = small_table_bytes(P, positions);
-    if (int rc = ensure_small((positions > 8 ? small_table_bytes(P, positions) : small_table_bytes_max(P)) + 4 * P.n + 64)) return rc;
+    if (int rc = sl->small.ensure((positions > 8 ? small_table_bytes(P, positions) : small_table_bytes_max(P)) + 4 * P.n + 64)) return rc;
     small_params S{};
     P.small_mode = 1;
     S.V = P;
-    S.tables = reinterpret_cast<uint32_t*>(sl->small);
+    S.tables = reinterpret_cast<uint32_t*>(sl->small.get());
     S.point_ok = sl->small + table_bytes;
     S.positions = positions;
     S.windows = vargen ? 64 : 32;

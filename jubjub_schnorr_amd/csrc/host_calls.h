@@ -51,22 +51,6 @@ constexpr size_t HOST_SLOTS = 3;
 constexpr unsigned HOST_STAGING_THREADS_MAX = JJS_HOST_STAGING_THREADS;
 constexpr size_t HOST_STAGING_MIN_BYTES = size_t(4) << 20;     // below this a piece is copied by the calling thread alone
 
-int ensure_stage(size_t bytes) {
-    if (bytes <= g->stage_bytes) return JJS_OK;
-    const size_t cap = grown(bytes);
-    return regrow(g->stage, g->stage_bytes, g->stage_bytes, cap, cap);
-}
-int ensure_pinned(size_t bytes) {
-    if (bytes <= g->pinned_bytes) return JJS_OK;
-    const size_t cap = grown(bytes);
-    uint8_t* fresh = nullptr;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&fresh), cap, hipHostMallocDefault));
-    retire(g->pinned, true, g->pinned_bytes);
-    g->pinned = fresh;
-    g->pinned_bytes = cap;
-    return JJS_OK;
-}
-
 // nothing may leave an extern "C" entry point by exception: the host-buffer calls allocate (block and piece lists)
 template <typename F>
 int no_throw(F&& f) {
@@ -250,16 +234,16 @@ int run_host_block(device_state* dev, const call_shape& S, const host_col* cols,
     size_t bytes = 0;
     for (size_t k = 0; k < n_cols; ++k) bytes += pad256(nl * cols[k].width);
     bytes += pad256(nl);
-    if (int rc = ensure_stage(bytes)) return rc;
+    if (int rc = g->stage.ensure(bytes)) return rc;
     const void* in[8];
     uint8_t* col_dev[8];
     uint8_t* p = g->stage;
     for (size_t k = 0; k < n_cols; ++k) { in[k] = col_dev[k] = p; p += pad256(nl * cols[k].width); }
     uint8_t* st = p;
-    if (int rc = ensure_pinned(HOST_SLOTS * slot_bytes + pad256(nl) + 256)) return rc;
+    if (int rc = g->pinned.ensure(HOST_SLOTS * slot_bytes + pad256(nl) + 256)) return rc;
     uint8_t* const pst = g->pinned + HOST_SLOTS * slot_bytes;
     unsigned long long* const ptally = reinterpret_cast<unsigned long long*>(pst + pad256(nl));
-    if (!g->stagers && b.staging_threads > 1) g->stagers = new (std::nothrow) staging_pool(b.staging_threads - 1);
+    if (!g->stagers && b.staging_threads > 1) g->stagers.reset(new (std::nothrow) staging_pool(b.staging_threads - 1));
     // The call of this block (the builder picks its slot), and with it the upload order: the columns nothing reads before
     // the equations (u) travel last when the call will hash with the head launch of prepare_kernel, which does not touch
     // them -- i.e. when it tries the key tables (and is not a wire call, whose u sits inside the signature column).
@@ -285,7 +269,7 @@ int run_host_block(device_state* dev, const call_shape& S, const host_col* cols,
         bool active = false;
         ~in_flight() { if (active && pool) pool->join(); }
     } staging;
-    staging.pool = g->stagers;
+    staging.pool = g->stagers.get();
     auto stage_begin = [&](size_t i) -> int {
         const host_piece& pc = b.pieces[i];
         if (i >= HOST_SLOTS) HIP_TRY(hipEventSynchronize(g->chunk_up[i - HOST_SLOTS]));      // the slot's previous upload has left it
@@ -454,8 +438,8 @@ int reserve_host_block(const call_shape& S, size_t nl) {
     for (size_t k = 0; k < S.n_cols; ++k) bytes += pad256(nl * S.col[k].width);
     std::vector<host_piece> plans[2];
     plan_block(S, nl, plans, largest);
-    if (int rc = ensure_stage(bytes + pad256(nl))) return rc;
-    return ensure_pinned(HOST_SLOTS * pad256(largest) + pad256(nl) + 256);
+    if (int rc = g->stage.ensure(bytes + pad256(nl))) return rc;
+    return g->pinned.ensure(HOST_SLOTS * pad256(largest) + pad256(nl) + 256);
 }
 
 // `unlocked`: the caller does NOT hold the engine's mutex (one driven device: the call holds that device's host_mu instead, so

@@ -29,21 +29,10 @@ static size_t lane_cap_for(const device_state* dev, int scheme, int format, size
     return cap < COMBINE_CAP_ITEMS ? cap : COMBINE_CAP_ITEMS;
 }
 static int ensure_lane(host_lane& lane, size_t bytes) {
-    if (!lane.stream) HIP_TRY(hipStreamCreateWithFlags(&lane.stream, hipStreamNonBlocking));
-    if (!lane.done) HIP_TRY(hipEventCreateWithFlags(&lane.done, hipEventDisableTiming));
-    if (bytes > lane.dev_bytes) {
-        const size_t cap = grown(bytes < (size_t(1) << 20) ? (size_t(1) << 20) : bytes);
-        if (int rc = regrow(lane.dev, lane.dev_bytes, lane.dev_bytes, cap, cap)) return rc;
-    }
-    if (bytes > lane.pinned_bytes) {
-        const size_t cap = grown(bytes < (size_t(1) << 20) ? (size_t(1) << 20) : bytes);
-        uint8_t* fresh = nullptr;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&fresh), cap, hipHostMallocDefault));
-        retire(lane.pinned, true, lane.pinned_bytes);
-        lane.pinned = fresh;
-        lane.pinned_bytes = cap;
-    }
-    return JJS_OK;
+    if (!lane.stream) HIP_TRY(lane.stream.create(hipStreamNonBlocking));
+    if (!lane.done) HIP_TRY(lane.done.create(hipEventDisableTiming));
+    if (int rc = lane.dev.ensure(bytes)) return rc;
+    return lane.pinned.ensure(bytes);
 }
 // The end of a lane launch: small calls last half a millisecond, and a thread that sleeps on the stream pays the wake-up on
 // top (tens to hundreds of microseconds on an idle core), so it polls the launch's event for LANE_SPIN_US first.

@@ -15,7 +15,8 @@
 //
 // This translation unit in parts (textual includes inside one anonymous namespace, in this order):
 //   device_kernels.h   every __global__ entry
-//   engine_state.h     device state, call slots, staging threads, errors, slot ordering, grow-only buffers
+//   device_owners.h    the owners of device and pinned memory, grow-only buffers, streams and events; when one may free
+//   engine_state.h     device state, call slots, staging threads, errors, slot ordering, the retired list
 //   verify_job.h       the arenas of the key-table path; a verification call in stages (begin, ingest, keys, hash, finish)
 //   (here)             device set-up and tear-down, the RCCL clique
 //   host_calls.h       the large blocking host-buffer calls: upload plan, staging copies, the pipeline
@@ -71,6 +72,7 @@ namespace {
 #include "device_kernels.h"
 #include "verdict_kernels.h"
 #include "keyset_verdict_kernels.h"
+#include "device_owners.h"
 #include "engine_state.h"
 #include "verify_job.h"
 
@@ -95,24 +97,24 @@ int init_device(device_state& d, int ordinal) {
     HIP_TRY(hipSetDevice(ordinal));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, ordinal));
-    HIP_TRY(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
-    for (hipStream_t& side : d.side) HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&d.host_begin, hipEventDisableTiming));
-    HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&d.ks_stream, hipStreamNonBlocking));
+    HIP_TRY(d.stream.create(hipStreamNonBlocking));
+    for (stream_owner& side : d.side) HIP_TRY(side.create(hipStreamNonBlocking));
+    HIP_TRY(d.host_begin.create(hipEventDisableTiming));
+    HIP_TRY(d.copy_stream.create(hipStreamNonBlocking));
+    HIP_TRY(d.ks_stream.create(hipStreamNonBlocking));
     {   // the per-key kernels are few, long waves that must finish before the challenge hashes do: dispatch them first
         int lo = 0, hi = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
         d.key_priority = hi;
         d.table_priority = lo;
     }
-    HIP_TRY(hipEventCreateWithFlags(&d.side_join, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&d.ingest_done, hipEventDisableTiming));
+    HIP_TRY(d.side_join.create(hipEventDisableTiming));
+    HIP_TRY(d.ingest_done.create(hipEventDisableTiming));
     for (size_t i = 0; i < HOST_MAX_PIECES; ++i) {
-        HIP_TRY(hipEventCreateWithFlags(&d.chunk_up[i], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&d.chunk_done[i], hipEventDisableTiming));
+        HIP_TRY(d.chunk_up[i].create(hipEventDisableTiming));
+        HIP_TRY(d.chunk_done[i].create(hipEventDisableTiming));
     }
-    HIP_TRY(hipEventCreateWithFlags(&d.last_use, hipEventDisableTiming));
+    HIP_TRY(d.last_use.create(hipEventDisableTiming));
     HIP_TRY(hipEventRecord(d.last_use, d.stream));
     int per_cu_v = 0, per_cu_s = 0, per_cu_m = 0, per_cu_r = 0;
     int per_cu_p = 0;
@@ -143,18 +145,18 @@ int init_device(device_state& d, int ordinal) {
         c.grid_verify = big ? d.slots[0].grid_verify : (int)(slot_items / BLOCK);
         // slot 0 also serves the signer and the multisig kernels, whose grids may be larger than the verify grid
         const size_t lanes = i == 0 ? (size_t)lanes_blocks * BLOCK : (big ? (size_t)c.grid_verify * BLOCK : slot_items);
-        HIP_TRY(hipMalloc(&c.workspace, lanes * WS_WORDS_PER_LANE * sizeof(uint32_t)));
-        HIP_TRY(hipEventCreateWithFlags(&c.last_use, hipEventDisableTiming));
+        HIP_TRY(c.workspace.alloc(lanes * WS_WORDS_PER_LANE * sizeof(uint32_t)));
+        HIP_TRY(c.last_use.create(hipEventDisableTiming));
         HIP_TRY(hipEventRecord(c.last_use, d.stream));
         if (i == 0 || i > N_SMALL_SLOTS) {       // slots whose calls can be large enough for the key tables: a key stream each
-            HIP_TRY(hipEventCreateWithFlags(&c.key_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&c.key_mid, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&c.key_join, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&c.key_ahead, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&c.key_chains, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&c.key_cleared, hipEventDisableTiming));
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c.seen), sizeof(key_feedback), hipHostMallocDefault));
-            memset(c.seen, 0, sizeof(key_feedback));
+            HIP_TRY(c.key_fork.create(hipEventDisableTiming));
+            HIP_TRY(c.key_mid.create(hipEventDisableTiming));
+            HIP_TRY(c.key_join.create(hipEventDisableTiming));
+            HIP_TRY(c.key_ahead.create(hipEventDisableTiming));
+            HIP_TRY(c.key_chains.create(hipEventDisableTiming));
+            HIP_TRY(c.key_cleared.create(hipEventDisableTiming));
+            HIP_TRY(c.seen.alloc(sizeof(key_feedback)));
+            memset(c.seen.get(), 0, sizeof(key_feedback));
         }
     }
     // The priority streams, in the order of their importance: the runtime hands its high-priority hardware queues out in
@@ -167,22 +169,22 @@ int init_device(device_state& d, int ordinal) {
     // single call 12.1-12.3 -> 11.6-11.8 ms, profiles/r04_host_ext_ab.jsonl).
     {
         static_assert(N_MEDIUM_SLOTS == 3 && N_BIG_SLOTS == 2, "one entry per slot that has a key stream");
-        for (int i : {0, SECOND_BIG_SLOT}) HIP_TRY(hipStreamCreateWithPriority(&d.slots[i].key_stream, hipStreamNonBlocking, d.key_priority));
-        for (hipStream_t& is : d.ingest) HIP_TRY(hipStreamCreateWithPriority(&is, hipStreamNonBlocking, d.key_priority));
+        for (int i : {0, SECOND_BIG_SLOT}) HIP_TRY(d.slots[i].key_stream.create(hipStreamNonBlocking, d.key_priority));
+        for (stream_owner& is : d.ingest) HIP_TRY(is.create(hipStreamNonBlocking, d.key_priority));
         for (int i : {1 + N_SMALL_SLOTS, 2 + N_SMALL_SLOTS, 3 + N_SMALL_SLOTS})
-            HIP_TRY(hipStreamCreateWithPriority(&d.slots[i].key_stream, hipStreamNonBlocking, d.key_priority));
+            HIP_TRY(d.slots[i].key_stream.create(hipStreamNonBlocking, d.key_priority));
     }
     for (call_slot& c : d.slots)
-        if (c.key_stream) HIP_TRY(hipStreamCreateWithPriority(&c.table_stream, hipStreamNonBlocking, d.table_priority));
-    HIP_TRY(hipMalloc(&d.comb_g, COMB_TABLE_WORDS * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&d.comb_gn, COMB_TABLE_WORDS * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&d.tag, 32));
-    HIP_TRY(hipMalloc(&d.tally, 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&d.dlog_pow, DLOG_POW_WORDS * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&d.dlog_hash, 65536));
+        if (c.key_stream) HIP_TRY(c.table_stream.create(hipStreamNonBlocking, d.table_priority));
+    HIP_TRY(d.comb_g.alloc(COMB_TABLE_WORDS * sizeof(uint32_t)));
+    HIP_TRY(d.comb_gn.alloc(COMB_TABLE_WORDS * sizeof(uint32_t)));
+    HIP_TRY(d.tag.alloc(32));
+    HIP_TRY(d.tally.alloc(4 * sizeof(unsigned long long)));
+    HIP_TRY(d.dlog_pow.alloc(DLOG_POW_WORDS * sizeof(uint32_t)));
+    HIP_TRY(d.dlog_hash.alloc(65536));
     HIP_TRY(hipMemsetAsync(d.dlog_hash, 0, 65536, d.stream));
     hipLaunchKernelGGL(dlog_table_kernel, dim3(7), dim3(BLOCK), 0, d.stream, d.dlog_pow, d.dlog_hash);
-    HIP_TRY(hipMalloc(&d.tags_long, sizeof(JJS_SPONGE_TAG_LONG)));
+    HIP_TRY(d.tags_long.alloc(sizeof(JJS_SPONGE_TAG_LONG)));
     HIP_TRY(hipMemcpyAsync(d.tags_long, JJS_SPONGE_TAG_LONG, sizeof(JJS_SPONGE_TAG_LONG), hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipMemcpyAsync(d.tag, JJS_DOUBLE_TAG_WORDS, 32, hipMemcpyHostToDevice, d.stream));
     const int blocks = (COMB_WINDOWS * COMB_ENTRIES + BLOCK - 1) / BLOCK;
@@ -193,50 +195,18 @@ int init_device(device_state& d, int ordinal) {
     return JJS_OK;
 }
 
-void free_device(device_state& d) {
-    if (d.device < 0) return;
-    (void)hipSetDevice(d.device);
-    if (d.stream) (void)hipStreamSynchronize(d.stream);
-    if (d.ks_stream) { (void)hipStreamSynchronize(d.ks_stream); (void)hipStreamDestroy(d.ks_stream); }
-    void* bufs[] = {d.comb_g, d.comb_gn, d.tag, d.tally, d.msig, d.tags_long, d.dlog_pow, d.dlog_hash, d.stage, d.ks_stage};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (call_slot& c : d.slots) {
-        if (c.key_stream) { (void)hipStreamSynchronize(c.key_stream); (void)hipStreamDestroy(c.key_stream); }
-        if (c.table_stream) { (void)hipStreamSynchronize(c.table_stream); (void)hipStreamDestroy(c.table_stream); }
-        void* sb[] = {c.workspace, c.pending, c.prep, c.wire, c.small, c.keys, c.key_pool, c.key_memo, c.verdict};
-        for (void* b : sb)
-            if (b) (void)hipFree(b);
-        if (c.seen) (void)hipHostFree(c.seen);
-        hipEvent_t evs[] = {c.last_use, c.key_fork, c.key_mid, c.key_join, c.key_ahead, c.key_chains, c.key_cleared};
-        for (hipEvent_t e : evs)
-            if (e) (void)hipEventDestroy(e);
+// The end of a device's state, whole or half set up (the way out of a failed jjs_init): nobody queues work any more.  The device
+// is drained, so what growth and destroyed objects retired can be freed; the staging threads end before the pinned memory they
+// copy into goes; then the members let go of what they own (device_owners.h) -- on a drained device, in whatever order they
+// are declared.
+void free_device(device_state* d) {
+    if (d->device >= 0) {
+        (void)hipSetDevice(d->device);
+        (void)hipDeviceSynchronize();
+        free_retired(*d);
+        d->stagers.reset();
     }
-    if (d.pinned) (void)hipHostFree(d.pinned);
-    for (host_lane& l : d.lanes) {
-        if (l.stream) { (void)hipStreamSynchronize(l.stream); (void)hipStreamDestroy(l.stream); }
-        if (l.done) (void)hipEventDestroy(l.done);
-        if (l.dev) (void)hipFree(l.dev);
-        if (l.pinned) (void)hipHostFree(l.pinned);
-    }
-    (void)hipDeviceSynchronize();
-    free_retired(d);
-    if (d.last_use) (void)hipEventDestroy(d.last_use);
-    for (size_t i = 0; i < HOST_MAX_PIECES; ++i) {
-        if (d.chunk_up[i]) (void)hipEventDestroy(d.chunk_up[i]);
-        if (d.chunk_done[i]) (void)hipEventDestroy(d.chunk_done[i]);
-    }
-    if (d.copy_stream) { (void)hipStreamSynchronize(d.copy_stream); (void)hipStreamDestroy(d.copy_stream); }
-    for (hipStream_t side : d.side)
-        if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
-    for (hipStream_t is : d.ingest)
-        if (is) { (void)hipStreamSynchronize(is); (void)hipStreamDestroy(is); }
-    if (d.host_begin) (void)hipEventDestroy(d.host_begin);
-    if (d.side_join) (void)hipEventDestroy(d.side_join);
-    if (d.ingest_done) (void)hipEventDestroy(d.ingest_done);
-    delete d.stagers;
-    if (d.stream) (void)hipStreamDestroy(d.stream);
-    d.device = -1;
+    delete d;
 }
 
 int load_rccl() {
@@ -297,7 +267,7 @@ void shutdown_locked() {
         for (size_t i = 0; i < L.devs.size(); ++i) (void)L.rccl.CommDestroy(L.comms[i]);
         L.comms_up = false;
     }
-    for (device_state* d : L.devs) { free_device(*d); delete d; }
+    for (device_state* d : L.devs) free_device(d);
     L.devs.clear();
     L.virtual_devices = false;
     g = nullptr;
@@ -344,18 +314,10 @@ const call_shape SHAPES[3][3] = {       // [JJS_SCHEME_*][JJS_FORMAT_*]
      {JJS_SCHEME_VARGEN, JJS_FORMAT_WIRE, 3, {{64, COLS_REST, COL_SIG_WIRE}, {64, COLS_KEYS, COL_KEYS_WIRE}, {32, COLS_REST, COL_MESSAGE}}, 1}},
 };
 
-// A slot's wire area (wire and ext entry points, calls against a key set), per item: four point columns of 64 bytes, 16 bytes
-// of flags (the first: the encoding was rejected) and the prefix products of the normalisation (normalize.h) -- one area for
-// the key columns and one for the others, whose launches may overlap in a host-buffer call.
-constexpr size_t WIRE_FLAGS_AT = 4 * 64, WIRE_SCRATCH_AT = 4 * 64 + 16, WIRE_SCRATCH_BYTES = 48, WIRE_ITEM_BYTES = WIRE_SCRATCH_AT + 2 * WIRE_SCRATCH_BYTES;
-int ensure_wire(size_t n) {
-    if (n <= sl->wire_items) return JJS_OK;
-    const size_t cap = grown(n < 4096 ? 4096 : n);
-    return regrow(sl->wire, sl->wire_items, sl->wire_items * WIRE_ITEM_BYTES, cap, cap * WIRE_ITEM_BYTES);
-}
-uint8_t* wire_pts(int k) { return sl->wire + (size_t)k * sl->wire_items * 64; }
-uint8_t* wire_bad() { return sl->wire + sl->wire_items * WIRE_FLAGS_AT; }
-uint32_t* wire_scratch(int k) { return reinterpret_cast<uint32_t*>(sl->wire + sl->wire_items * (WIRE_SCRATCH_AT + WIRE_SCRATCH_BYTES * k)); }
+// A slot's wire area (call_slot::wire; WIRE_ITEM_BYTES per item of its capacity): where its parts begin.
+uint8_t* wire_pts(int k) { return sl->wire + (size_t)k * sl->wire.capacity() * 64; }
+uint8_t* wire_bad() { return sl->wire + sl->wire.capacity() * WIRE_FLAGS_AT; }
+uint32_t* wire_scratch(int k) { return reinterpret_cast<uint32_t*>(sl->wire + sl->wire.capacity() * (WIRE_SCRATCH_AT + WIRE_SCRATCH_BYTES * k)); }
 
 // the scheme's verification descriptor over affine columns (Rp, PK2: the columns the scheme has; PK2 of a var-gen call: the generator)
 verify_params scheme_params(int scheme, const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* PK, const uint8_t* PK2,
@@ -377,7 +339,7 @@ int build_call(const call_shape& S, const void* const* d, size_t n, void* status
     pick_slot(n, s);
     const bool affine = S.format == JJS_FORMAT_AFFINE;
     if (!affine)
-        if (int rc = ensure_wire(n)) return rc;
+        if (int rc = sl->wire.ensure(n)) return rc;
     C = staged_call{};
     const uint8_t *u = nullptr, *m = nullptr, *R[2] = {}, *PK[2] = {};
     uint32_t n_r = 0, n_pk = 0, sig_width = 0;
@@ -752,11 +714,10 @@ int jjs_trim(void) {
         free_retired(*d);
         for (call_slot& c : d->slots) {
             if (!c.key_pool) continue;
-            HIP_TRY(hipFree(c.key_pool));
-            if (c.key_pool_bytes > c.key_pool_want) c.key_pool_want = c.key_pool_bytes;
-            c.key_pool = nullptr; c.key_pool_bytes = 0;
-            if (c.key_memo) HIP_TRY(hipFree(c.key_memo));      // the memo goes with the tables it describes
-            c.key_memo = nullptr; c.key_memo_bytes = 0; c.memo_cap = 0; c.memo_flush = true;
+            if (c.key_pool.bytes() > c.key_pool_want) c.key_pool_want = c.key_pool.bytes();
+            HIP_TRY(c.key_pool.free());
+            HIP_TRY(c.key_memo.free());                        // the memo goes with the tables it describes
+            c.memo_cap = 0; c.memo_flush = true;
         }
     }
     return JJS_OK;
@@ -767,13 +728,14 @@ int jjs_memory_stats(uint64_t out[JJS_MEMORY_STATS]) {
     if (!out) return fail(JJS_ERR_ARG, "null pointer");
     uint64_t pool = 0, slots = 0, lanes = 0;
     for (const call_slot& c : g->slots) {
-        pool += c.key_pool_bytes + c.key_memo_bytes;
-        slots += c.pending_items * 8 + c.prep_items * 65 + c.wire_items * WIRE_ITEM_BYTES + c.small_bytes + c.keys_bytes + c.verdict_bytes;
+        pool += c.key_pool.bytes() + c.key_memo.bytes();
+        slots += c.pending.reported_bytes() + c.prep.reported_bytes() + c.wire.reported_bytes() + c.small.reported_bytes() + c.keys.reported_bytes() +
+                 c.verdict.reported_bytes();
     }
-    for (const host_lane& l : g->lanes) lanes += l.dev_bytes + l.pinned_bytes;
+    for (const host_lane& l : g->lanes) lanes += l.dev.reported_bytes() + l.pinned.reported_bytes();
     out[JJS_MEMORY_KEY_POOLS] = pool;
     out[JJS_MEMORY_SLOT_BUFFERS] = slots;
-    out[JJS_MEMORY_HOST_STAGING] = lanes + g->stage_bytes + g->pinned_bytes;
+    out[JJS_MEMORY_HOST_STAGING] = lanes + g->stage.reported_bytes() + g->pinned.reported_bytes();
     out[JJS_MEMORY_RETIRED] = g->retired_bytes;
     return JJS_OK;
 }
@@ -789,7 +751,7 @@ int jjs_path_stats(uint64_t out[JJS_PATH_STATS]) {
     for (call_slot& c : g->slots) {
         sl = &c;
         if (c.key_stream && !c.host_owned) note_key_feedback();     // (a slot a large host-buffer call is feeding: counted by that call's successor)
-        pool += c.key_pool_bytes;
+        pool += c.key_pool.bytes();
     }
     for (int i = 0; i < JJS_PATH_STATS; ++i) out[i] = g->stats[i];
     out[JJS_PATH_KEY_POOL_BYTES] = pool;
@@ -838,7 +800,7 @@ struct msig_scratch {
 static size_t msig_scratch_bytes(size_t items, size_t transcripts) { return items * 4 * (1 + 8 + 2 * EXT_WORDS) + transcripts * 4 * (16 + 1 + 18) + 64; }
 static msig_scratch msig_scratch_carve() {
     msig_scratch W{};
-    uint32_t* w = (uint32_t*)g->msig;
+    uint32_t* w = reinterpret_cast<uint32_t*>(g->msig.get());
     W.tr_of = w; w += g->msig_items;
     W.d_words = w; w += 8 * g->msig_items;
     W.dpk = w; w += EXT_WORDS * g->msig_items;
@@ -854,10 +816,9 @@ static int ensure_msig_scratch(size_t n, size_t n_transcripts) {
     size_t ci = grown(n < 4096 ? 4096 : n), ct = grown(n_transcripts < 1024 ? 1024 : n_transcripts);
     if (ci < g->msig_items) ci = g->msig_items;
     if (ct < g->msig_transcripts) ct = g->msig_transcripts;
-    uint8_t* fresh = nullptr;
-    HIP_TRY(hipMalloc(&fresh, msig_scratch_bytes(ci, ct)));
-    retire(g->msig, false, msig_scratch_bytes(g->msig_items, g->msig_transcripts));
-    g->msig = fresh;
+    device_mem<uint8_t> fresh;
+    HIP_TRY(fresh.alloc(msig_scratch_bytes(ci, ct)));
+    g->msig.replace(std::move(fresh));
     g->msig_items = ci; g->msig_transcripts = ct;
     return JJS_OK;
 }

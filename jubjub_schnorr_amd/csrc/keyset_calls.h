@@ -11,11 +11,7 @@ template <class Entry>
 class registration {
     std::vector<device_state*> devs;       // the devices the engine drove when the call came in
     std::optional<blocking_call_leave> leave_on_every_way_out;
-    void free_copies() {                   // nothing has been published: no launch of anybody else reads these
-        device_restore restore;
-        for (auto& c : e->copies)
-            if (c.mem) { (void)hipSetDevice(c.dev->device); (void)hipFree(c.mem); c.mem = nullptr; }
-    }
+    void free_copies() { e->copies.clear(); }     // nothing has been published, and each copy's build stream was drained: freed, not retired
 public:
     std::unique_ptr<Entry> e;              // the entry, from enter() until it is published
     // the first section under L.mu: the engine is ready, check() accepts the arguments; then the call is counted in
@@ -37,12 +33,10 @@ public:
             for (device_state* d : devs) {
                 g = d;
                 HIP_TRY(hipSetDevice(d->device));
-                hipStream_t s = nullptr;
-                HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+                stream_owner s;
+                HIP_TRY(s.create(hipStreamNonBlocking));
                 e->copies.emplace_back();
-                const int brc = build_copy(e->copies.back(), s);
-                (void)hipStreamDestroy(s);
-                if (brc) { e->copies.pop_back(); return brc; }
+                if (int brc = build_copy(e->copies.back(), s)) { e->copies.pop_back(); return brc; }
             }
             return JJS_OK;
         });
@@ -64,22 +58,19 @@ public:
 template <class Body>
 static int build_device_copy(device_copy& c, size_t bytes, size_t tmp_bytes, const char* what, hipStream_t s, Body body) {
     c.dev = g;
-    c.bytes = bytes;
-    if (hipMalloc(&c.mem, c.bytes) != hipSuccess) {
+    if (c.mem.alloc(bytes) != hipSuccess) {
         (void)hipGetLastError();
-        c.mem = nullptr;
-        return fail(JJS_ERR_HIP, "hipMalloc of a %s (%zu bytes) failed", what, c.bytes);
+        return fail(JJS_ERR_HIP, "hipMalloc of a %s (%zu bytes) failed", what, bytes);
     }
-    uint8_t* tmp = nullptr;
-    if (hipMalloc(&tmp, tmp_bytes) != hipSuccess) {
+    device_mem<uint8_t> tmp;
+    if (tmp.alloc(tmp_bytes) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(c.mem); c.mem = nullptr;
+        (void)c.mem.free();
         return fail(JJS_ERR_HIP, "hipMalloc of a %s's build area (%zu bytes) failed", what, tmp_bytes);
     }
-    const int rc = body(tmp);
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(tmp);
-    if (rc) { (void)hipFree(c.mem); c.mem = nullptr; }
+    const int rc = body(tmp.get());
+    (void)hipStreamSynchronize(s);        // ... so that the build area may go, and the copy with it when the body failed
+    if (rc) (void)c.mem.free();
     return rc;
 }
 }  // extern "C++"
@@ -176,10 +167,10 @@ struct keyset_front {
 };
 static int keyset_front_end(const keyset_entry& k, const keyset_copy& c, const void* key_idx, size_t n, bool sort, hipStream_t s, keyset_front& F) {
     pick_slot(n, s);
-    if (int rc = ensure_wire(n)) return rc;
+    if (int rc = sl->wire.ensure(n)) return rc;
     F.cursor_words = (size_t)k.n_keys + 1 > (size_t)CURSOR_DENSE_FROM * CURSOR_STRIDE ? (size_t)k.n_keys + 1
                                                                                       : (size_t)CURSOR_DENSE_FROM * CURSOR_STRIDE;
-    if (int rc = ensure_key_index(2 * pad256(n * 4) + pad256(F.cursor_words * 4))) return rc;
+    if (int rc = sl->keys.ensure(2 * pad256(n * 4) + pad256(F.cursor_words * 4))) return rc;
     key_params& K = F.K;
     K = key_params{};
     K.n_cols = k.n_cols; K.max_keys = k.n_keys; K.max_keys_wide = k.n_keys; K.n = n; K.counters = c.words;
@@ -225,10 +216,10 @@ static int keyset_launch(keyset_entry& k, const keyset_copy& c, int format, cons
     keyset_front F;
     if (int rc = keyset_front_end(k, c, d[0], n, !small, s, F)) return rc;
     const key_params& K = F.K;
-    if (int rc = ensure_prep(n)) return rc;
-    if (int rc = ensure_pending(n)) return rc;
+    if (int rc = sl->prep.ensure(n)) return rc;
+    if (int rc = sl->pending.ensure(n)) return rc;
     if (small)
-        if (int rc = ensure_small(2 * n + 64)) return rc;      // the subgroup tests of the R points (keyset_hash_kernel)
+        if (int rc = sl->small.ensure(2 * n + 64)) return rc;      // the subgroup tests of the R points (keyset_hash_kernel)
     // the verification descriptor: R (R') as the format gives them, the keys gathered per item into wire_pts(2) (3)
     const uint8_t *R = (const uint8_t*)d[2], *Rp = (const uint8_t*)d[3];
     const uint32_t n_r = scheme == JJS_SCHEME_DOUBLE ? 2u : 1u;
@@ -238,7 +229,7 @@ static int keyset_launch(keyset_entry& k, const keyset_copy& c, int format, cons
     const uint32_t sig_stride = scheme == JJS_SCHEME_DOUBLE ? 96u : 64u;
     if (format == JJS_FORMAT_WIRE) { P.u = fe_src{(const uint8_t*)d[1], sig_stride, 0}; P.decoded_points = 1; }
     P.prep = sl->prep;
-    P.pending_count = reinterpret_cast<unsigned long long*>(sl->pending);
+    P.pending_count = reinterpret_cast<unsigned long long*>(sl->pending.get());
     P.pending = sl->pending + 2;
 
     if (int rc = begin_shared(s)) return rc;
@@ -326,10 +317,7 @@ static int keyset_stage_in(device_state* dev, const size_t* widths, const void* 
     size_t off[8], total = 0;
     for (size_t i = 0; i < cols; ++i) { off[i] = total; total += pad256(widths[i] * n); }
     for (size_t j = 0; j < outs; ++j) { off[cols + j] = total; total += pad256(out_bytes[j]); }
-    if (total > dev->ks_stage_bytes) {
-        const size_t cap = grown(total);
-        if (int rc = regrow(dev->ks_stage, dev->ks_stage_bytes, dev->ks_stage_bytes, cap, cap)) return rc;
-    }
+    if (int rc = dev->ks_stage.ensure(total)) return rc;
     HIP_TRY(hipSetDevice(dev->device));
     S.s = dev->ks_stream;
     for (size_t i = 0; i < cols; ++i) {
@@ -408,7 +396,7 @@ int jjs_keyset_info(jjs_keyset ks, uint64_t out[JJS_KEYSET_INFO]) {
     out[JJS_KEYSET_KEYS] = k->n_keys;
     out[JJS_KEYSET_VALID_KEYS] = k->valid;
     out[JJS_KEYSET_WINDOW_BITS] = (uint64_t)KEYSET_WINDOW;
-    out[JJS_KEYSET_DEVICE_BYTES] = k->copies.empty() ? 0 : k->copies[0].bytes;
+    out[JJS_KEYSET_DEVICE_BYTES] = k->copies.empty() ? 0 : k->copies[0].mem.bytes();
     out[JJS_KEYSET_SMALL_CALLS] = k->small_calls;
     out[JJS_KEYSET_LARGE_CALLS] = k->large_calls;
     return JJS_OK;

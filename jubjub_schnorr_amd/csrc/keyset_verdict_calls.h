@@ -76,8 +76,8 @@ static int keyset_verdict_launch_msm(keyset_entry& k, const keyset_copy& c, cons
 static int keyset_verdict_launch_items(keyset_entry& k, const keyset_copy& c, int format, const void* const* d, size_t n, uint32_t* verdict,
                                        hipStream_t s) {
     pick_slot(n, s);
-    if (int rc = ensure_verdict(256)) return rc;
-    unsigned long long* tally = reinterpret_cast<unsigned long long*>(sl->verdict);
+    if (int rc = sl->verdict.ensure(256)) return rc;
+    unsigned long long* tally = reinterpret_cast<unsigned long long*>(sl->verdict.get());
     {
         struct keep_slot {                      // keyset_launch picks its slot itself: the one that holds the tally
             call_slot* before = forced_slot;

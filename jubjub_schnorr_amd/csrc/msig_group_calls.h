@@ -97,7 +97,7 @@ int jjs_msig_group_info(jjs_msig_group h, uint64_t out[JJS_MSIG_GROUP_INFO]) {
     if (!out) return fail(JJS_ERR_ARG, "null pointer");
     out[JJS_MSIG_GROUP_PARTICIPANTS] = k->participants;
     out[JJS_MSIG_GROUP_WINDOW_BITS] = (uint64_t)MG_WINDOW;
-    out[JJS_MSIG_GROUP_DEVICE_BYTES] = k->copies.empty() ? 0 : k->copies[0].bytes;
+    out[JJS_MSIG_GROUP_DEVICE_BYTES] = k->copies.empty() ? 0 : k->copies[0].mem.bytes();
     out[JJS_MSIG_GROUP_CALLS] = k->calls;
     return JJS_OK;
 }

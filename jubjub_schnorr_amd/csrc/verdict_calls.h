@@ -41,11 +41,6 @@ static int batch_seed(uint32_t seed[8]) {
     return JJS_OK;
 }
 
-static int ensure_verdict(size_t bytes) {
-    if (bytes <= sl->verdict_bytes) return JJS_OK;
-    const size_t cap = grown(bytes);
-    return regrow(sl->verdict, sl->verdict_bytes, sl->verdict_bytes, cap, cap);
-}
 static verify_params verdict_params(int scheme, const void* const* d, size_t n) {
     const uint8_t* const* p = reinterpret_cast<const uint8_t* const*>(d);
     const out_ptrs o{nullptr, nullptr, nullptr, nullptr};
@@ -77,7 +72,7 @@ static int verdict_scratch(P& B, msm_params& M, uint32_t blocks, const size_t* e
     size_t total = 0;
     for (size_t x : sz) total += pad256(x);
     for (int i = 0; i < n_extra; ++i) total += pad256(extra[i]);
-    if (int rc = ensure_verdict(total)) return rc;
+    if (int rc = sl->verdict.ensure(total)) return rc;
     uint8_t* p = sl->verdict;
     uint8_t* q[MSM_PARTS];
     for (int i = 0; i < MSM_PARTS; ++i) { q[i] = p; p += pad256(sz[i]); }
@@ -139,8 +134,8 @@ static int verdict_launch_msm(int scheme, const void* const* d, size_t n, uint32
 static int verdict_launch_items(int scheme, const void* const* d, size_t n, uint32_t* verdict, hipStream_t s) {
     staged_call C;
     if (int rc = build_call(SHAPES[scheme][JJS_FORMAT_AFFINE], d, n, nullptr, nullptr, s, C)) return rc;
-    if (int rc = ensure_verdict(256)) return rc;
-    unsigned long long* tally = reinterpret_cast<unsigned long long*>(sl->verdict);
+    if (int rc = sl->verdict.ensure(256)) return rc;
+    unsigned long long* tally = reinterpret_cast<unsigned long long*>(sl->verdict.get());
     C.P.tally = tally;
     if (int rc = launch_staged(C, s)) return rc;
     hipLaunchKernelGGL(tally_verdict_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long*)tally, (uint64_t)n, verdict);

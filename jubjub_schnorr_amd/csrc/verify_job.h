@@ -88,11 +88,6 @@ memo_layout key_memo_layout(uint32_t cap) {
     M.col_bytes = 256 + M.hash_bytes + M.key_bytes + 4 * M.word_bytes + M.flag_bytes;      // stamp, pool_of, todo, hit
     return M;
 }
-int ensure_key_index(size_t bytes) {
-    if (bytes <= sl->keys_bytes) return JJS_OK;
-    const size_t cap = grown(bytes);
-    return regrow(sl->keys, sl->keys_bytes, sl->keys_bytes, cap, cap);
-}
 // key columns of a scheme: PK of every equation, and the generator where it is per-item data
 uint32_t key_columns(const verify_params& P, fe_src cols[2]) {
     uint32_t n_cols = 0;
@@ -119,25 +114,20 @@ int ensure_key_pool(const verify_params& P) {
     if (first > KEY_POOL_INITIAL_BYTES) first = KEY_POOL_INITIAL_BYTES;
     size_t want = sl->key_pool_want > first ? sl->key_pool_want : first;
     const bool refused = sl->key_pool_refused && want >= sl->key_pool_refused;     // hipMalloc has said no to this much before
-    if (sl->key_pool && (want <= sl->key_pool_bytes || refused)) return JJS_OK;
+    if (sl->key_pool && (want <= sl->key_pool.bytes() || refused)) return JJS_OK;
     if (!sl->key_pool && refused) want = first < sl->key_pool_refused ? first : sl->key_pool_refused / 2;
-    uint8_t *fresh = nullptr, *memo = nullptr;
+    device_mem<uint8_t> fresh, memo;        // both, or neither: what was allocated goes when this returns early
     // the memo holds as many pool indices per column as one column has when it owns the whole pool, for either of two columns
     const uint32_t memo_cap = key_pool_layout(want & ~size_t(255)).cap_narrow;
     const size_t memo_bytes = 2 * key_memo_layout(memo_cap).col_bytes;
-    if (hipMalloc(&fresh, want) != hipSuccess || hipMalloc(&memo, memo_bytes) != hipSuccess) {
+    if (fresh.alloc(want) != hipSuccess || memo.alloc(memo_bytes) != hipSuccess) {
         (void)hipGetLastError();
-        if (fresh) (void)hipFree(fresh);
         sl->key_pool_refused = want;
         ++g->stats[JJS_PATH_KEYS_NO_MEMORY];
         return sl->key_pool ? JJS_OK : fail(JJS_ERR_HIP, "hipMalloc of the key-table pool (%zu bytes) failed", want);
     }
-    retire(sl->key_pool, false, sl->key_pool_bytes);        // earlier launches may still read the old pool
-    sl->key_pool = fresh;
-    sl->key_pool_bytes = want;
-    retire(sl->key_memo, false, sl->key_memo_bytes);
-    sl->key_memo = memo;
-    sl->key_memo_bytes = memo_bytes;
+    sl->key_pool.replace(std::move(fresh));                 // earlier launches may still read the old pool
+    sl->key_memo.replace(std::move(memo));
     sl->memo_cap = memo_cap;
     sl->memo_flush = sl->memo_dirty = true;
     return JJS_OK;
@@ -178,7 +168,7 @@ int carve_keys(const verify_params& P, key_params& K, uint8_t** cleared, size_t*
     const uint32_t n_cols = key_columns(P, cols);
     K.n_cols = n_cols;
     if (int rc = ensure_key_pool(P)) return rc;
-    const size_t col_bytes = (sl->key_pool_bytes / n_cols) & ~size_t(255);
+    const size_t col_bytes = (sl->key_pool.bytes() / n_cols) & ~size_t(255);
     const pool_layout L = key_pool_layout(col_bytes);
     const uint64_t most = P.n / KT_MIN_MULTIPLICITY;            // more keys than this never take the path
     K.max_keys = (uint32_t)(L.cap_narrow < most ? L.cap_narrow : most);
@@ -190,7 +180,7 @@ int carve_keys(const verify_params& P, key_params& K, uint8_t** cleared, size_t*
     const size_t cursor_words = (size_t)K.max_keys + 1 > (size_t)CURSOR_DENSE_FROM * CURSOR_STRIDE ? (size_t)K.max_keys + 1 : (size_t)CURSOR_DENSE_FROM * CURSOR_STRIDE;
     const size_t order_bytes = pad256(P.n * 4) + pad256(cursor_words * 4);
     const size_t valid_bytes = pad256(((size_t)K.max_keys + 1) * 4);
-    if (int rc = ensure_key_index(256 + order_bytes + n_cols * (per_col + valid_bytes))) return rc;
+    if (int rc = sl->keys.ensure(256 + order_bytes + n_cols * (per_col + valid_bytes))) return rc;
     uint8_t* p = sl->keys;
     // what every call finds cleared comes first and side by side (one memset, one launch: the dozen small dependent launches at
     // the head of a call are a third of a 2^16-item batch)
@@ -256,7 +246,7 @@ int setup_keys(const verify_params& P, key_params& K, hipStream_t s) {
 #if defined(JJS_PROFILING)
     if (g_force_path || g_force_window || g_keep_order) K.memo_mode = KT_MEMO_FLUSH;      // A/B runs measure a call that builds its tables
 #endif
-    if (sl->memo_dirty) HIP_TRY(hipMemsetAsync(sl->key_memo, 0, sl->key_memo_bytes, s));
+    if (sl->memo_dirty) HIP_TRY(hipMemsetAsync(sl->key_memo, 0, sl->key_memo.bytes(), s));
     sl->memo_dirty = sl->memo_flush = false;
     sl->memo_cols = K.n_cols;
     return JJS_OK;
@@ -277,9 +267,9 @@ bool small_path_applies(const verify_params& P) {
 
 // jjs_reserve: the slot buffers a call with this descriptor would allocate (the slot is `sl`), allocated now
 int reserve_for(const verify_params& P) {
-    if (int rc = ensure_prep(P.n)) return rc;
-    if (small_path_applies(P)) return ensure_small(small_table_bytes_max(P) + 4 * P.n + 64);
-    if (int rc = ensure_pending(P.n)) return rc;
+    if (int rc = sl->prep.ensure(P.n)) return rc;
+    if (small_path_applies(P)) return sl->small.ensure(small_table_bytes_max(P) + 4 * P.n + 64);
+    if (int rc = sl->pending.ensure(P.n)) return rc;
     if (key_path_applies(P)) {
         key_params K{};
         uint8_t* cleared = nullptr;
@@ -366,7 +356,7 @@ int job_begin(verify_job& J, hipStream_t s) {
 #if defined(JJS_PROFILING)
     P.skip_phases = g_skip_phases;
 #endif
-    if (int rc = ensure_prep(P.n)) return rc;
+    if (int rc = sl->prep.ensure(P.n)) return rc;
     P.prep = sl->prep;
     P.workspace = sl->workspace;
     if (int rc = begin_shared(s)) return rc;
@@ -376,8 +366,8 @@ int job_begin(verify_job& J, hipStream_t s) {
     Z.p[1] = const_cast<uint8_t*>(P.pre_malformed); Z.bytes[1] = P.pre_malformed ? P.n : 0;
     J.small = small_path_applies(P);
     if (!J.small) {
-        if (int rc = ensure_pending(P.n)) return rc;
-        P.pending_count = reinterpret_cast<unsigned long long*>(sl->pending);
+        if (int rc = sl->pending.ensure(P.n)) return rc;
+        P.pending_count = reinterpret_cast<unsigned long long*>(sl->pending.get());
         P.pending = sl->pending + 2;
         Z.p[2] = sl->pending; Z.bytes[2] = sizeof(uint64_t);
     }
