@@ -398,6 +398,39 @@ int jjs_msig_group_combine_dev(jjs_msig_group g, const void* z, const void* R, c
                                size_t n_transcripts, void* share_status, void* transcript_status, void* sig_u, void* sig_R,
                                void* stream);
 
+/* ---- multisignature from extended coordinates, and from host buffers ------------------------------------------
+ * The reference's verify_share / combine receive &[PublicKey], &[JubJubExtended], &[JubJubExtended] (src/multisig.rs:284-291,
+ * 332-338): the *_ext calls take PK, R and S as N x 96 = U || V || Z, three canonical field elements per point (the group call:
+ * R and S; jjs_msig_group_create_ext: the n keys), and normalise them on the device with one inversion shared by many rows
+ * (msig_normalize_kernel in front of the first pass, on the caller's stream), so that a host shim inverts nothing.  Everything
+ * else -- arguments, checks, n_transcripts == 0, the 2^32 limit of the group call, return codes, outputs (agg_pk and sig_R stay
+ * 64-byte affine) -- is that of the affine call of the same shape.
+ * Contract of the extended form: a point is UNUSABLE when U, V or Z is >= q or Z = 0 (the Rust type cannot hold such a value;
+ * the rule makes the ABI total).  The outputs of an _ext call are, byte for byte, the outputs of the affine call of the same
+ * shape on derived columns in which every usable point is the canonical (U/Z, V/Z) and every unusable point is 64 bytes of
+ * 0xFF.  A share with an unusable point therefore gets status 3 from the range test of its coordinates and its transcript
+ * gets no signature; whatever the affine call does with the rest of such a transcript, the extended call does too.  Z = 0
+ * gives status 3 here, NOT InvalidPoint (2) as in jjs_verify_*_ext: the multisignature calls validate no points and have no
+ * such status.  jjs_msig_group_create_ext refuses a set with an unusable key with -1, as jjs_msig_group_create refuses a
+ * coordinate >= q; a group registered from extended keys is the group registered from their affine forms (the same
+ * aggregate_pk, the same bytes out of every call).
+ * jjs_multisig_combine / jjs_msig_group_combine: the same two calls from HOST buffers, blocking; format = JJS_FORMAT_AFFINE or
+ * JJS_FORMAT_EXT (JJS_FORMAT_WIRE: -1).  No alignment is asked of the pointers; transcript_status may be NULL.  The columns are
+ * uploaded whole into a grow-only staging area of the calling thread's current device (reported under JJS_MEMORY_HOST_STAGING;
+ * jjs_trim frees it) and the call runs on a stream of the engine, one such call at a time per device. */
+int jjs_multisig_combine_ext_dev(const void* z, const void* PK_ext, const void* R_ext, const void* S_ext, const void* m,
+                                 const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
+                                 void* agg_pk, void* sig_u, void* sig_R, void* stream);
+int jjs_msig_group_create_ext(const uint8_t* PK_ext, size_t n, jjs_msig_group* out);
+int jjs_msig_group_combine_ext_dev(jjs_msig_group g, const void* z, const void* R_ext, const void* S_ext, const void* m,
+                                   size_t n_transcripts, void* share_status, void* transcript_status, void* sig_u, void* sig_R,
+                                   void* stream);
+int jjs_multisig_combine(int format, const uint8_t* z, const uint8_t* PK, const uint8_t* R, const uint8_t* S, const uint8_t* m,
+                         const uint32_t* offsets, size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status,
+                         uint8_t* agg_pk, uint8_t* sig_u, uint8_t* sig_R);
+int jjs_msig_group_combine(jjs_msig_group g, int format, const uint8_t* z, const uint8_t* R, const uint8_t* S, const uint8_t* m,
+                           size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status, uint8_t* sig_u, uint8_t* sig_R);
+
 /* ---- transcript parity (debug export): c_out = n x 32 bytes, the 250-bit challenge per item ---- */
 int jjs_challenge_single_dev(const void* R, const void* PK, const void* m, size_t n, void* c_out, void* stream);
 int jjs_challenge_double_dev(const void* R, const void* R_prime, const void* PK, const void* PK_prime, const void* m,

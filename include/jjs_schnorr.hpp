@@ -410,6 +410,42 @@ class KeySet {
 // delinearisation coefficients, aggregate key and window tables stay on the device.  Move-only; the destructor destroys the
 // group (calls already queued on a stream still complete).
 namespace multisig {
+// reference src/error.rs: what `combine` answers instead of a signature.  InvalidMultisigShare carries the participant index of
+// the first failing share (derived on the host from share_status, status 4).  BytesError is the engine's own third kind, with the same
+// index: the first failing share has status 3, an encoding the Rust types cannot hold (z >= r, a coordinate >= q, Z = 0, or m >= q) --
+// the reference's `combine` cannot be handed such a value and has no variant for it; it is not InvalidMultisigShare.
+struct CombineError {
+    enum Kind { InvalidMultisigTranscript, InvalidMultisigShare, BytesError } kind;
+    size_t participant_index;     // of the first failing share; 0 for InvalidMultisigTranscript
+};
+struct CombineResult {
+    std::optional<Signature> signature;      // present exactly when `error` is not
+    std::optional<CombineError> error;
+    explicit operator bool() const { return signature.has_value(); }
+};
+// `combine` (reference src/multisig.rs:326-360) of ONE transcript from the types the Rust side holds -- extended points pass
+// through as get_u / get_v / get_z bytes, nothing is inverted on the host -- through the blocking host form
+// jjs_multisig_combine.  An empty transcript, or vectors of unequal length: InvalidMultisigTranscript, without a call.
+inline CombineResult combine(const std::vector<JubJubScalar>& z_vec, const std::vector<ExtendedPoint>& pk_vec, const std::vector<ExtendedPoint>& R_vec,
+                             const std::vector<ExtendedPoint>& S_vec, const BlsScalar& msg) {
+    const size_t n = pk_vec.size();
+    if (n == 0 || z_vec.size() != n || R_vec.size() != n || S_vec.size() != n || n > 0xFFFFFFFFull)
+        return CombineResult{std::nullopt, CombineError{CombineError::InvalidMultisigTranscript, 0}};
+    const uint32_t offsets[2] = {0, (uint32_t)n};
+    std::vector<uint8_t> status(n);
+    uint8_t tstatus = 0;
+    AffinePoint agg{}, R{};
+    Scalar u{};
+    // (std::array rows are contiguous: a vector of them is the n x 32 / n x 96 column the call takes)
+    const int rc = jjs_multisig_combine(JJS_FORMAT_EXT, z_vec[0].data(), pk_vec[0].data(), R_vec[0].data(), S_vec[0].data(), msg.data(), offsets, 1,
+                                        status.data(), &tstatus, agg.data(), u.data(), R.data());
+    if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_combine");
+    for (size_t i = 0; i < n; ++i)
+        if (status[i])
+            return CombineResult{std::nullopt, CombineError{status[i] == JJS_STATUS_INVALID_SHARE ? CombineError::InvalidMultisigShare : CombineError::BytesError, i}};
+    return CombineResult{Signature{u, R}, std::nullopt};
+}
+
 class SignerGroup {
   public:
     // PK: host, n x 64 affine, the ordered pk_vec
@@ -420,6 +456,13 @@ class SignerGroup {
         if (rc != JJS_OK) { reset(); throw EngineError(rc, "jjs_msig_group_aggregate_pk"); }
     }
     explicit SignerGroup(const std::vector<AffinePoint>& keys) : SignerGroup(flat(keys).data(), keys.size()) {}
+    // the ordered pk_vec as the Rust side holds it (jjs_msig_group_create_ext): the same group as from the affine forms
+    explicit SignerGroup(const std::vector<ExtendedPoint>& keys) : participants_(keys.size()) {
+        int rc = jjs_msig_group_create_ext(keys.empty() ? nullptr : keys[0].data(), keys.size(), &handle_);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_create_ext");
+        rc = jjs_msig_group_aggregate_pk(handle_, aggregate_pk_.data());
+        if (rc != JJS_OK) { reset(); throw EngineError(rc, "jjs_msig_group_aggregate_pk"); }
+    }
     SignerGroup(SignerGroup&& o) noexcept : handle_(o.handle_), participants_(o.participants_), aggregate_pk_(o.aggregate_pk_) { o.handle_ = 0; }
     SignerGroup& operator=(SignerGroup&& o) noexcept {
         if (this != &o) { reset(); handle_ = o.handle_; participants_ = o.participants_; aggregate_pk_ = o.aggregate_pk_; o.handle_ = 0; }
@@ -445,6 +488,18 @@ class SignerGroup {
                      void* transcript_status, void* sig_u, void* sig_R, void* stream = nullptr) const {
         int rc = jjs_msig_group_combine_dev(handle_, z, R, S, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, stream);
         if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_combine_dev");
+    }
+    // the same with R and S as B n x 96 extended points (jjs_msig_group_combine_ext_dev)
+    void combine_ext_dev(const void* z, const void* R_ext, const void* S_ext, const void* m, size_t n_transcripts, void* share_status,
+                         void* transcript_status, void* sig_u, void* sig_R, void* stream = nullptr) const {
+        int rc = jjs_msig_group_combine_ext_dev(handle_, z, R_ext, S_ext, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, stream);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_combine_ext_dev");
+    }
+    // host buffers, blocking (jjs_msig_group_combine): format JJS_FORMAT_AFFINE (R, S: B n x 64) or JJS_FORMAT_EXT (B n x 96)
+    void combine(int format, const uint8_t* z, const uint8_t* R, const uint8_t* S, const uint8_t* m, size_t n_transcripts, uint8_t* share_status,
+                 uint8_t* transcript_status, uint8_t* sig_u, uint8_t* sig_R) const {
+        int rc = jjs_msig_group_combine(handle_, format, z, R, S, m, n_transcripts, share_status, transcript_status, sig_u, sig_R);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_combine");
     }
 
   private:

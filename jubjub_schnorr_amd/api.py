@@ -242,30 +242,53 @@ class Engine:
                    "jjs_compress_dev")
         return out
 
-    def multisig_combine(self, z, PK, R, S, m, offsets):
+    _MSIG_POINT_WIDTH = {"affine": 64, "ext": 96}
+
+    @classmethod
+    def _msig_width(cls, fmt: str) -> int:
+        if fmt not in cls._MSIG_POINT_WIDTH:
+            raise ValueError(f"the multisignature calls take fmt 'affine' or 'ext', not {fmt!r}")
+        return cls._MSIG_POINT_WIDTH[fmt]
+
+    def multisig_combine(self, z, PK, R, S, m, offsets, fmt: str = "affine"):
         """Batch `verify_share` + `combine` + `aggregate_pk` over many transcripts (reference src/multisig.rs).
-        z (N, 32), PK / R / S (N, 64), m (B, 32): torch CUDA uint8; offsets: B + 1 ints (host).  Returns
+        z (N, 32), PK / R / S (N, 64) -- or (N, 96) = U || V || Z with fmt="ext", normalised on the device -- m (B, 32);
+        offsets: B + 1 ints (host).  torch CUDA uint8 tensors run asynchronously on the current stream
+        (jjs_multisig_combine[_ext]_dev), numpy arrays block (jjs_multisig_combine).  Returns
         (share_status (N,), agg_pk (B, 64), sig_u (B, 32), sig_R (B, 64), transcript_status (B,)); statuses 0 ok / 3 / 4;
         sig_u / sig_R are zero for a transcript whose status is not 0 (`combine` returns an error, not a signature)."""
-        import torch
+        w = self._msig_width(fmt)
         offs = np.ascontiguousarray(offsets, dtype=np.uint32)
         B, N = len(offs) - 1, z.shape[0]
+        if not _is_torch(z):
+            hz, hpk, hr, hs, hm = self._host(z, 32), self._host(PK, w), self._host(R, w), self._host(S, w), self._host(m, 32)
+            if any(h.shape[0] != N for h in (hpk, hr, hs)) or hm.shape[0] != B or (B and int(offs[-1]) != N):
+                raise ValueError("the columns do not have the rows the offsets ask for")
+            status, tstatus = np.zeros(N, np.uint8), np.zeros(B, np.uint8)
+            agg, su, sr = np.zeros((B, 64), np.uint8), np.zeros((B, 32), np.uint8), np.zeros((B, 64), np.uint8)
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+            _ffi.check(self._lib.jjs_multisig_combine(self._FORMAT_IDS[fmt], p(hz), p(hpk), p(hr), p(hs), p(hm), p(offs), B, p(status),
+                                                      p(tstatus), p(agg), p(su), p(sr)), "jjs_multisig_combine")
+            return status, agg, su, sr, tstatus
+        import torch
         dev_ = z.device
         new = lambda rows, w: torch.empty((max(rows, 1), w), dtype=torch.uint8, device=dev_)[:rows]  # noqa: E731
         status = torch.empty(max(N, 1), dtype=torch.uint8, device=dev_)[:N]
         tstatus = torch.empty(max(B, 1), dtype=torch.uint8, device=dev_)[:B]
         agg, su, sr = new(B, 64), new(B, 32), new(B, 64)
         o = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        _ffi.check(self._lib.jjs_multisig_combine_dev(self._dev_ptr(z, 32, N), self._dev_ptr(PK, 64, N), self._dev_ptr(R, 64, N),
-                                                      self._dev_ptr(S, 64, N), self._dev_ptr(m, 32, B),
-                                                      offs.ctypes.data_as(ctypes.c_void_p), B, o(status), o(tstatus), o(agg), o(su),
-                                                      o(sr), self._stream()), "jjs_multisig_combine_dev")
+        name = "jjs_multisig_combine_ext_dev" if fmt == "ext" else "jjs_multisig_combine_dev"
+        _ffi.check(getattr(self._lib, name)(self._dev_ptr(z, 32, N), self._dev_ptr(PK, w, N), self._dev_ptr(R, w, N),
+                                            self._dev_ptr(S, w, N), self._dev_ptr(m, 32, B),
+                                            offs.ctypes.data_as(ctypes.c_void_p), B, o(status), o(tstatus), o(agg), o(su),
+                                            o(sr), self._stream()), name)
         return status, agg, su, sr, tstatus
 
-    def multisig_group(self, PK) -> "SignerGroup":
-        """Register the ordered key vector of a committee once (jjs_msig_group_create): its delinearisation coefficients, its
-        aggregate key and the window tables of its keys are built on every driven device and kept until `close()`."""
-        return SignerGroup(self, PK)
+    def multisig_group(self, PK, fmt: str = "affine") -> "SignerGroup":
+        """Register the ordered key vector of a committee once (jjs_msig_group_create; fmt="ext": (n, 96) extended keys,
+        jjs_msig_group_create_ext): its delinearisation coefficients, its aggregate key and the window tables of its keys are
+        built on every driven device and kept until `close()`."""
+        return SignerGroup(self, PK, fmt)
 
     def challenge(self, scheme: str, *arrays):
         """250-bit challenge per item (torch CUDA tensors): single (R, PK, m); double (R, R', PK, PK', m);
@@ -701,25 +724,38 @@ class SignerGroup:
     `close()` destroys the group (queued device calls still complete)."""
     INFO_NAMES = ("participants", "window_bits", "device_bytes", "calls")
 
-    def __init__(self, eng: Engine, PK):
+    def __init__(self, eng: Engine, PK, fmt: str = "affine"):
         self._eng, self._lib = eng, eng._lib
-        pk = eng._host(PK, 64)
+        pk = eng._host(PK, Engine._msig_width(fmt))
         h = ctypes.c_uint64(0)
-        _ffi.check(self._lib.jjs_msig_group_create(pk.ctypes.data_as(ctypes.c_void_p) if len(pk) else None, len(pk), ctypes.byref(h)),
-                   "jjs_msig_group_create")
+        name = "jjs_msig_group_create_ext" if fmt == "ext" else "jjs_msig_group_create"
+        _ffi.check(getattr(self._lib, name)(pk.ctypes.data_as(ctypes.c_void_p) if len(pk) else None, len(pk), ctypes.byref(h)), name)
         self.handle = h.value
         self.participants = len(pk)
         self.aggregate_pk = np.zeros(64, np.uint8)
         _ffi.check(self._lib.jjs_msig_group_aggregate_pk(self.handle, self.aggregate_pk.ctypes.data_as(ctypes.c_void_p)),
                    "jjs_msig_group_aggregate_pk")
 
-    def combine(self, z, R, S, m):
-        """Batch `verify_share` + `combine` over B transcripts of the group's n participants: z (B n, 32), R / S (B n, 64),
-        m (B, 32), torch CUDA uint8, share (t, i) at row t n + i.  Returns (share_status (B n,), sig_u (B, 32), sig_R (B, 64),
-        transcript_status (B,)): the tuple of `Engine.multisig_combine` without agg_pk, byte for byte."""
-        import torch
+    def combine(self, z, R, S, m, fmt: str = "affine"):
+        """Batch `verify_share` + `combine` over B transcripts of the group's n participants: z (B n, 32), R / S (B n, 64) -- or
+        (B n, 96) = U || V || Z with fmt="ext" -- m (B, 32), share (t, i) at row t n + i.  torch CUDA uint8 tensors run
+        asynchronously on the current stream, numpy arrays block (jjs_msig_group_combine).  Returns (share_status (B n,),
+        sig_u (B, 32), sig_R (B, 64), transcript_status (B,)): the tuple of `Engine.multisig_combine` without agg_pk, byte for byte."""
+        w = Engine._msig_width(fmt)
         B = m.shape[0]
         N = B * self.participants
+        if not _is_torch(z):
+            h = self._eng._host
+            hz, hr, hs, hm = h(z, 32), h(R, w), h(S, w), h(m, 32)
+            if any(x.shape[0] != N for x in (hz, hr, hs)):
+                raise ValueError(f"expected {N} rows: {B} transcripts of {self.participants} participants")
+            status, tstatus = np.zeros(N, np.uint8), np.zeros(B, np.uint8)
+            su, sr = np.zeros((B, 32), np.uint8), np.zeros((B, 64), np.uint8)
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+            _ffi.check(self._lib.jjs_msig_group_combine(self.handle, Engine._FORMAT_IDS[fmt], p(hz), p(hr), p(hs), p(hm), B, p(status),
+                                                        p(tstatus), p(su), p(sr)), "jjs_msig_group_combine")
+            return status, su, sr, tstatus
+        import torch
         dev_ = z.device
         new = lambda rows, w: torch.empty((max(rows, 1), w), dtype=torch.uint8, device=dev_)[:rows]  # noqa: E731
         status = torch.empty(max(N, 1), dtype=torch.uint8, device=dev_)[:N]
@@ -727,8 +763,9 @@ class SignerGroup:
         su, sr = new(B, 32), new(B, 64)
         o = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         d = Engine._dev_ptr
-        _ffi.check(self._lib.jjs_msig_group_combine_dev(self.handle, d(z, 32, N), d(R, 64, N), d(S, 64, N), d(m, 32, B), B, o(status),
-                                                        o(tstatus), o(su), o(sr), Engine._stream()), "jjs_msig_group_combine_dev")
+        name = "jjs_msig_group_combine_ext_dev" if fmt == "ext" else "jjs_msig_group_combine_dev"
+        _ffi.check(getattr(self._lib, name)(self.handle, d(z, 32, N), d(R, w, N), d(S, w, N), d(m, 32, B), B, o(status),
+                                            o(tstatus), o(su), o(sr), Engine._stream()), name)
         return status, su, sr, tstatus
 
     def info(self) -> dict:

@@ -570,6 +570,12 @@ __global__ __launch_bounds__(BLOCK) void normalize_kernel(normalize_params P) {
     __builtin_amdgcn_s_setprio(3);            // few waves, a long dependent chain, and the hashes of their items wait for them
     normalize_lane(P, (uint64_t)blockIdx.x * BLOCK + threadIdx.x, (uint64_t)gridDim.x * BLOCK);
 }
+// The same for the multisignature calls, in poison mode: an unusable point comes out as 64 bytes of 0xFF, which the range test
+// of the share pass turns into status 3 (normalize.h).  A kernel of its own: normalize_kernel keeps its code and its registers.
+__global__ __launch_bounds__(BLOCK) void msig_normalize_kernel(normalize_params P) {
+    __builtin_amdgcn_s_setprio(3);            // as above: every pass of the call waits for these few waves
+    normalize_lane<true>(P, (uint64_t)blockIdx.x * BLOCK + threadIdx.x, (uint64_t)gridDim.x * BLOCK);
+}
 __global__ __launch_bounds__(BLOCK) void compress_kernel(const uint8_t* affine, uint64_t n, uint8_t* out) {
     uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;

@@ -84,6 +84,11 @@ class grow_only {
 public:
     explicit grow_only(growth_rule rule = {}) : rule_(rule) {}
     int ensure(size_t want) { return want <= cap_ ? JJS_OK : grow(want); }
+    hipError_t free() {                                               // on a drained device only (see above): jjs_trim
+        const hipError_t e = mem_.free();
+        if (e == hipSuccess) cap_ = 0;
+        return e;
+    }
     size_t capacity() const { return cap_; }                          // in units
     size_t reported_bytes() const { return cap_ * rule_.unit_bytes; } // what jjs_memory_stats counts: the units, not the slack
     T* get() const { return mem_.get(); }

@@ -252,6 +252,7 @@ struct device_state {
     device_mem<uint32_t> tags_long;// SAFE tags for long transcripts (multisig)
     device_mem<uint8_t> msig;      // multisig scratch: grows in two dimensions (ensure_msig_scratch)
     size_t msig_items = 0, msig_transcripts = 0;
+    size_t msig_ext_rows = 0;      // ... and a third: rows whose extended points an *_ext call normalises into it (0 until one asks)
     int grid_msig = 0;
     int key_priority = 0;                // stream priority of the slots' key streams
     int table_priority = 0;              // ... and of their table streams (the lowest)
@@ -275,6 +276,9 @@ struct device_state {
     size_t retired_bytes = 0;
     stream_owner ks_stream;              // host-buffer calls on a registered key set (jjs_keyset_verify): uploads, launch, statuses
     grow_only<uint8_t> ks_stage;         // ... their device copies of the inputs and outputs (bytes; under host_mu)
+    grow_only<uint8_t> msig_stage;       // host-buffer multisig calls (jjs_multisig_combine, jjs_msig_group_combine): their columns and
+                                         // outputs (bytes), on ks_stream under host_mu; it grows under the engine's mutex as well, which
+                                         // jjs_memory_stats reads it under; jjs_trim frees it
 };
 
 // RCCL is needed only when one process drives several devices, so it is loaded on demand.

@@ -20,6 +20,7 @@
 //   verify_job.h       the arenas of the key-table path; a verification call in stages (begin, ingest, keys, hash, finish)
 //   (here)             device set-up and tear-down, the RCCL clique
 //   host_calls.h       the large blocking host-buffer calls: upload plan, staging copies, the pipeline
+//   msig_host_calls.h  the blocking host-buffer forms of the multisignature calls
 //   host_lanes.h       the small ones (included among the entry points, behind the table of call shapes): staging lanes
 //                      outside the engine's mutex, calls of several threads in one launch
 //   (here)             the table of call shapes and the staged_call builder it drives; the extern "C" entry points
@@ -712,6 +713,7 @@ int jjs_trim(void) {
         HIP_TRY(hipSetDevice(d->device));
         HIP_TRY(hipDeviceSynchronize());
         free_retired(*d);
+        HIP_TRY(d->msig_stage.free());                         // the staging of the host-buffer multisig calls (host_mu is held)
         for (call_slot& c : d->slots) {
             if (!c.key_pool) continue;
             if (c.key_pool.bytes() > c.key_pool_want) c.key_pool_want = c.key_pool.bytes();
@@ -735,7 +737,7 @@ int jjs_memory_stats(uint64_t out[JJS_MEMORY_STATS]) {
     for (const host_lane& l : g->lanes) lanes += l.dev.reported_bytes() + l.pinned.reported_bytes();
     out[JJS_MEMORY_KEY_POOLS] = pool;
     out[JJS_MEMORY_SLOT_BUFFERS] = slots;
-    out[JJS_MEMORY_HOST_STAGING] = lanes + g->stage.reported_bytes() + g->pinned.reported_bytes();
+    out[JJS_MEMORY_HOST_STAGING] = lanes + g->stage.reported_bytes() + g->pinned.reported_bytes() + g->msig_stage.reported_bytes();
     out[JJS_MEMORY_RETIRED] = g->retired_bytes;
     return JJS_OK;
 }
@@ -793,11 +795,18 @@ int jjs_compress_dev(const void* affine, size_t n, void* out, void* stream) {
 // ---- multisig: batch verify_share / combine -------------------------------------------
 // The device's multisignature scratch (g->msig, grow-only; sized for g->msig_items shares in g->msig_transcripts transcripts),
 // in words: tr_of (1), d_words (8), dpk and e_pt (EXT_WORDS each) per share, then a_words and c_words (8 each), the offsets
-// (1, and one more) and the long tags (18) per transcript.
+// (1, and one more) and the long tags (18) per transcript.  Behind them, once an *_ext call has asked for it (g->msig_ext_rows
+// rows; affine callers never pay for it): three columns of normalised points (64 bytes per row each) and the 9 words of prefix
+// product per row that normalize_lane keeps.
 struct msig_scratch {
     uint32_t *tr_of, *d_words, *dpk, *e_pt, *a_words, *c_words, *offsets, *long_tags;
+    uint8_t* norm[3];
+    uint32_t* prefix;
 };
-static size_t msig_scratch_bytes(size_t items, size_t transcripts) { return items * 4 * (1 + 8 + 2 * EXT_WORDS) + transcripts * 4 * (16 + 1 + 18) + 64; }
+constexpr size_t MSIG_EXT_ROW_BYTES = 3 * 64 + 9 * 4;
+static size_t msig_scratch_bytes(size_t items, size_t transcripts, size_t ext_rows) {
+    return items * 4 * (1 + 8 + 2 * EXT_WORDS) + transcripts * 4 * (16 + 1 + 18) + 64 + (ext_rows ? ext_rows * MSIG_EXT_ROW_BYTES + 64 : 0);
+}
 static msig_scratch msig_scratch_carve() {
     msig_scratch W{};
     uint32_t* w = reinterpret_cast<uint32_t*>(g->msig.get());
@@ -808,26 +817,41 @@ static msig_scratch msig_scratch_carve() {
     W.a_words = w; w += 8 * g->msig_transcripts;
     W.c_words = w; w += 8 * g->msig_transcripts;
     W.offsets = w; w += g->msig_transcripts + 1;
-    W.long_tags = w;
+    W.long_tags = w; w += 18 * g->msig_transcripts;
+    if (g->msig_ext_rows) {
+        uint8_t* q = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(w) + 63) & ~uintptr_t(63));
+        for (int k = 0; k < 3; ++k) { W.norm[k] = q; q += 64 * g->msig_ext_rows; }
+        W.prefix = reinterpret_cast<uint32_t*>(q);
+    }
     return W;
 }
-static int ensure_msig_scratch(size_t n, size_t n_transcripts) {
-    if (n <= g->msig_items && n_transcripts <= g->msig_transcripts) return JJS_OK;
+static int ensure_msig_scratch(size_t n, size_t n_transcripts, size_t ext_rows = 0) {
+    if (n <= g->msig_items && n_transcripts <= g->msig_transcripts && ext_rows <= g->msig_ext_rows) return JJS_OK;
     size_t ci = grown(n < 4096 ? 4096 : n), ct = grown(n_transcripts < 1024 ? 1024 : n_transcripts);
+    size_t ce = ext_rows ? grown(ext_rows < 4096 ? 4096 : ext_rows) : 0;
     if (ci < g->msig_items) ci = g->msig_items;
     if (ct < g->msig_transcripts) ct = g->msig_transcripts;
+    if (ce < g->msig_ext_rows) ce = g->msig_ext_rows;
     device_mem<uint8_t> fresh;
-    HIP_TRY(fresh.alloc(msig_scratch_bytes(ci, ct)));
+    HIP_TRY(fresh.alloc(msig_scratch_bytes(ci, ct, ce)));
     g->msig.replace(std::move(fresh));
-    g->msig_items = ci; g->msig_transcripts = ct;
+    g->msig_items = ci; g->msig_transcripts = ct; g->msig_ext_rows = ce;
     return JJS_OK;
 }
-int jjs_multisig_combine_dev(const void* z, const void* PK, const void* R, const void* S, const void* m,
-                             const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
-                             void* agg_pk, void* sig_u, void* sig_R, void* stream) {
-    std::lock_guard<std::mutex> lock(L.mu);
-    if (int rc = check_ready()) return rc;
-    if (n_transcripts == 0) return JJS_OK;
+// The normalisation in front of the passes of an extended call: `cols` columns of n rows (96 bytes a point) into the scratch's
+// normalised columns, one item per row, in poison mode; col[] is re-aimed at the normalised columns.
+static int msig_normalize(const msig_scratch& W, const uint8_t** col, uint32_t cols, size_t n, hipStream_t s) {
+    normalize_params N{};
+    N.n_src = cols; N.poison = 1; N.scratch = W.prefix;
+    for (uint32_t k = 0; k < cols; ++k) {
+        N.src[k] = fe_src{col[k], 96, 0};
+        N.out[k] = W.norm[k];
+        col[k] = W.norm[k];
+    }
+    return launch_normalize(N, 0, n, n, s);
+}
+// n = the shares of a call whose host offsets are acceptable
+static int msig_check_offsets(const uint32_t* offsets_host, size_t n_transcripts, size_t& n) {
     if (!offsets_host || offsets_host[0] != 0) return fail(JJS_ERR_ARG, "offsets must start at 0");
     // A transcript takes any number of participants: none is the reference's InvalidMultisigTranscript (status 5 for that
     // transcript, the others are not affected), and beyond the JJS_MSIG_MAX_PARTICIPANTS the tag table covers the two
@@ -839,16 +863,24 @@ int jjs_multisig_combine_dev(const void* z, const void* PK, const void* R, const
             return fail(JJS_ERR_ARG, "transcript %zu: %llu participants (the hash transcripts are indexed with 32 bits: at most %u)", t,
                         (unsigned long long)cnt, (unsigned)JJS_MSIG_PARTICIPANTS_LIMIT);
     }
-    const size_t n = offsets_host[n_transcripts];
+    n = offsets_host[n_transcripts];
+    return JJS_OK;
+}
+// The call on device columns, queued on s (under the engine's mutex, g the device; n_transcripts > 0).  ext: PK, R, S are N x 96.
+static int msig_combine_locked(bool ext, const void* z, const void* PK, const void* R, const void* S, const void* m,
+                               const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
+                               void* agg_pk, void* sig_u, void* sig_R, hipStream_t s) {
+    size_t n = 0;
+    if (int rc = msig_check_offsets(offsets_host, n_transcripts, n)) return rc;
     if ((n && !all_ok(z, PK, R, S)) || !all_ok(m, agg_pk, sig_u, sig_R) || (n && !share_status)) return fail(JJS_ERR_ARG, "null or misaligned pointer");
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = ensure_msig_scratch(n, n_transcripts)) return rc;
+    if (int rc = ensure_msig_scratch(n, n_transcripts, ext ? n : 0)) return rc;
+    const msig_scratch W = msig_scratch_carve();
+    const uint8_t* pts[3] = {(const uint8_t*)PK, (const uint8_t*)R, (const uint8_t*)S};
     msig_params P{};
-    P.z = (const uint8_t*)z; P.PK = (const uint8_t*)PK; P.R = (const uint8_t*)R; P.S = (const uint8_t*)S; P.m = (const uint8_t*)m;
+    P.z = (const uint8_t*)z; P.m = (const uint8_t*)m;
     P.n_transcripts = (uint32_t)n_transcripts; P.n_total = n;
     P.share_status = (uint8_t*)share_status; P.agg_pk = (uint8_t*)agg_pk; P.sig_u = (uint8_t*)sig_u; P.sig_R = (uint8_t*)sig_R;
     P.transcript_status = (uint8_t*)transcript_status;
-    const msig_scratch W = msig_scratch_carve();
     P.tr_of = W.tr_of; P.d_words = W.d_words; P.dpk = W.dpk; P.e_pt = W.e_pt;
     P.a_words = W.a_words; P.c_words = W.c_words; P.offsets = W.offsets;
     P.tags = g->tags_long; P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
@@ -858,6 +890,9 @@ int jjs_multisig_combine_dev(const void* z, const void* PK, const void* R, const
     if (int rc = begin_shared(s)) return rc;
     auto queue = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(W.offsets, offsets_host, (n_transcripts + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (ext)
+            if (int rc = msig_normalize(W, pts, 3, n, s)) return rc;
+        P.PK = pts[0]; P.R = pts[1]; P.S = pts[2];
         for (int pass = 0; pass < 7; ++pass) {
             const size_t count = (pass == 0 || pass == 2 || pass == 4 || pass == 6) ? n_transcripts : n;
             // a pass with a hash chain and few items: eight lanes per item (multisig_core.h hash_lanes)
@@ -871,8 +906,27 @@ int jjs_multisig_combine_dev(const void* z, const void* PK, const void* R, const
     const int rc2 = end_shared(s);              // the slot's event covers whatever was queued, also when a step failed
     return rc ? rc : rc2;
 }
+int jjs_multisig_combine_dev(const void* z, const void* PK, const void* R, const void* S, const void* m,
+                             const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
+                             void* agg_pk, void* sig_u, void* sig_R, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    if (n_transcripts == 0) return JJS_OK;
+    return msig_combine_locked(false, z, PK, R, S, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk, sig_u, sig_R,
+                               (hipStream_t)stream);
+}
+int jjs_multisig_combine_ext_dev(const void* z, const void* PK_ext, const void* R_ext, const void* S_ext, const void* m,
+                                 const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
+                                 void* agg_pk, void* sig_u, void* sig_R, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    if (n_transcripts == 0) return JJS_OK;
+    return msig_combine_locked(true, z, PK_ext, R_ext, S_ext, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk, sig_u,
+                               sig_R, (hipStream_t)stream);
+}
 
 #include "msig_group_calls.h"
+#include "msig_host_calls.h"
 
 // ---- challenge export ---------------------------------------------------------------------------
 static int launch_challenge(challenge_params P, void* stream) {

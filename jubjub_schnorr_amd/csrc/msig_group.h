@@ -53,6 +53,19 @@ JJS_HD bool mg_keys_acceptable(const uint8_t* PK, uint64_t n) {
     for (uint64_t i = 0; i < n; ++i) ok = ok && words_lt(load_words(pk, i), JJS_Q_WORDS) && words_lt(load_words(pk, i, 32), JJS_Q_WORDS);
     return ok;
 }
+// the same for keys in extended coordinates (n x 96): every key usable -- U, V, Z < q and Z != 0 (normalize.h, poison mode)
+JJS_HD bool mg_ext_keys_usable(const uint8_t* PK_ext, uint64_t n) {
+    if (!PK_ext || n == 0) return false;
+    const fe_src pk{PK_ext, 96, 0};
+    bool ok = true;
+    for (uint64_t i = 0; i < n; ++i) {
+        const words8 z = load_words(pk, i, 64);
+        uint32_t any = 0;
+        for (int k = 0; k < 8; ++k) any |= z.w[k];
+        ok = ok && any != 0 && words_lt(z, JJS_Q_WORDS) && words_lt(load_words(pk, i), JJS_Q_WORDS) && words_lt(load_words(pk, i, 32), JJS_Q_WORDS);
+    }
+    return ok;
+}
 
 // ---- registration ------------------------------------------------------------------------------------------------------------
 // (d_j and D_j = d_j * PK_j: msig_delin_item on a one-transcript msig_params; agg_pk: sum_points_affine over the D_j)

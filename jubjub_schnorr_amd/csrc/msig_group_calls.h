@@ -7,7 +7,8 @@ constexpr size_t MSIG_GROUP_BY_PARTICIPANT_FROM = 64;
 
 // One device's copy of a group (g is that device), on stream s: d_j and D_j = d_j * PK_j by the inline call's own pass 1 over a
 // one-transcript descriptor, their sum, and the chains and window tables of the keys.  `tags`: the two SAFE tags, from the host.
-static int msig_group_build_copy(msig_group_entry& k, msig_group_copy& c, const uint8_t* PK, const uint32_t (*tags)[9], uint8_t* agg_out,
+// ext: PK holds n x 96 extended keys (every one usable: the caller has looked), normalised here in front of everything else.
+static int msig_group_build_copy(msig_group_entry& k, msig_group_copy& c, const uint8_t* PK, bool ext, const uint32_t (*tags)[9], uint8_t* agg_out,
                                  hipStream_t s) {
     const uint32_t n = k.participants;
     const size_t d_bytes = pad256((size_t)n * 32), table_bytes = (size_t)n * MG_TABLE_WORDS_PER_KEY * 4;
@@ -16,7 +17,8 @@ static int msig_group_build_copy(msig_group_entry& k, msig_group_copy& c, const 
     const int delin_grid = grid_for(g->grid_msig, (size_t)n * hash_lanes);
     const size_t pk_bytes = pad256((size_t)n * 64), map_bytes = pad256((size_t)n * 4), dpk_bytes = pad256((size_t)n * EXT_WORDS * 4);
     const size_t base_bytes = pad256((size_t)n * MG_BASE_WORDS_PER_KEY * 4), ws_bytes = (size_t)delin_grid * BLOCK * WS_WORDS_PER_LANE * 4;
-    const size_t tmp_bytes = pk_bytes + map_bytes + 256 + dpk_bytes + base_bytes + ws_bytes;
+    const size_t ext_bytes = ext ? pad256((size_t)n * 96) : 0, prefix_bytes = ext ? pad256((size_t)n * 36) : 0;
+    const size_t tmp_bytes = pk_bytes + map_bytes + 256 + dpk_bytes + base_bytes + ext_bytes + prefix_bytes + ws_bytes;
     const uint32_t offsets[2] = {0, n};          // host memory the queued copies read: the frame drains the stream before it goes
     return build_device_copy(c, 256 + d_bytes + pad256(table_bytes), tmp_bytes, "signer group", s, [&](uint8_t* tmp) -> int {
         c.agg_pk = c.mem;
@@ -29,8 +31,18 @@ static int msig_group_build_copy(msig_group_entry& k, msig_group_copy& c, const 
         uint32_t* d_off = reinterpret_cast<uint32_t*>(q); q += 256;
         uint32_t* dpk = reinterpret_cast<uint32_t*>(q); q += dpk_bytes;
         uint32_t* bases = reinterpret_cast<uint32_t*>(q); q += base_bytes;
+        uint8_t* pk_ext = q; q += ext_bytes;
+        uint32_t* prefix = reinterpret_cast<uint32_t*>(q); q += prefix_bytes;
         uint32_t* ws = reinterpret_cast<uint32_t*>(q);
-        HIP_TRY(hipMemcpyAsync(pk, PK, (size_t)n * 64, hipMemcpyHostToDevice, s));
+        if (ext) {
+            HIP_TRY(hipMemcpyAsync(pk_ext, PK, (size_t)n * 96, hipMemcpyHostToDevice, s));
+            normalize_params N{};
+            N.n_src = 1; N.poison = 1; N.scratch = prefix;
+            N.src[0] = fe_src{pk_ext, 96, 0}; N.out[0] = pk;
+            if (int rc = launch_normalize(N, 0, n, n, s)) return rc;
+        } else {
+            HIP_TRY(hipMemcpyAsync(pk, PK, (size_t)n * 64, hipMemcpyHostToDevice, s));
+        }
         HIP_TRY(hipMemcpyAsync(c.tag_a, tags, 2 * 9 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(offsets), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(tr_of, 0, (size_t)n * 4, s));
@@ -51,9 +63,8 @@ static int msig_group_build_copy(msig_group_entry& k, msig_group_copy& c, const 
     });
 }
 
-extern "C" {
-
-int jjs_msig_group_create(const uint8_t* PK, size_t n, jjs_msig_group* out) {
+// jjs_msig_group_create / _ext: PK is n x 64 affine, or n x 96 extended
+static int msig_group_create(const uint8_t* PK, bool ext, size_t n, jjs_msig_group* out) {
     registration<msig_group_entry> call;
     if (int rc = call.enter([&] {
             if (!out || !PK || n == 0) return fail(JJS_ERR_ARG, "a signer group needs at least one key and an output handle");
@@ -62,15 +73,17 @@ int jjs_msig_group_create(const uint8_t* PK, size_t n, jjs_msig_group* out) {
         }))
         return rc;
     msig_group_entry& k = *call.e;
+    const size_t width = ext ? 96 : 64;
     std::vector<u32x4> keys;                // the caller's bytes, aligned for the range test
     if (int rc = no_throw([&]() -> int {
-            keys.resize(n * 4);
-            memcpy(keys.data(), PK, n * 64);
+            keys.resize(n * width / 16);
+            memcpy(keys.data(), PK, n * width);
             return JJS_OK;
         }))
         return rc;
     const uint8_t* pk = reinterpret_cast<const uint8_t*>(keys.data());
-    if (!mg_keys_acceptable(pk, n)) return fail(JJS_ERR_ARG, "a coordinate of a key is not below q");
+    if (ext ? !mg_ext_keys_usable(pk, n) : !mg_keys_acceptable(pk, n))
+        return fail(JJS_ERR_ARG, ext ? "a key is unusable: a coordinate is not below q, or Z is zero" : "a coordinate of a key is not below q");
     k.participants = (uint32_t)n;
     uint32_t tags[2][9];
     for (int which = 0; which < 2; ++which) {
@@ -78,9 +91,14 @@ int jjs_msig_group_create(const uint8_t* PK, size_t n, jjs_msig_group* out) {
         if (n <= JJS_MSIG_MAX_PARTICIPANTS) memcpy(tags[which], JJS_SPONGE_TAG_LONG[n_in], sizeof(tags[which]));
         else safe_tag_limbs(n_in, JJS_Q_WORDS, tags[which]);
     }
-    if (int rc = call.build([&](msig_group_copy& c, hipStream_t s) { return msig_group_build_copy(k, c, pk, tags, k.agg_pk, s); })) return rc;
+    if (int rc = call.build([&](msig_group_copy& c, hipStream_t s) { return msig_group_build_copy(k, c, pk, ext, tags, k.agg_pk, s); })) return rc;
     return call.publish(g_msig_groups, "signer group", out);
 }
+
+extern "C" {
+
+int jjs_msig_group_create(const uint8_t* PK, size_t n, jjs_msig_group* out) { return msig_group_create(PK, false, n, out); }
+int jjs_msig_group_create_ext(const uint8_t* PK_ext, size_t n, jjs_msig_group* out) { return msig_group_create(PK_ext, true, n, out); }
 
 int jjs_msig_group_destroy(jjs_msig_group h) {
     std::lock_guard<std::mutex> lock(L.mu);
@@ -112,10 +130,9 @@ int jjs_msig_group_aggregate_pk(jjs_msig_group h, uint8_t out[64]) {
     return JJS_OK;
 }
 
-int jjs_msig_group_combine_dev(jjs_msig_group h, const void* z, const void* R, const void* S, const void* m, size_t n_transcripts,
-                               void* share_status, void* transcript_status, void* sig_u, void* sig_R, void* stream) {
-    std::lock_guard<std::mutex> lock(L.mu);
-    if (int rc = check_ready()) return rc;
+// The call against group h on device columns, queued on s (under the engine's mutex, g the device).  ext: R, S are B n x 96.
+static int msig_group_combine_locked(jjs_msig_group h, bool ext, const void* z, const void* R, const void* S, const void* m, size_t n_transcripts,
+                                     void* share_status, void* transcript_status, void* sig_u, void* sig_R, hipStream_t s) {
     msig_group_entry* k = g_msig_groups.find(h);
     if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed signer group");
     if (n_transcripts == 0) return JJS_OK;
@@ -126,11 +143,11 @@ int jjs_msig_group_combine_dev(jjs_msig_group h, const void* z, const void* R, c
     if (!all_ok(z, R, S, m, sig_u, sig_R) || !share_status) return fail(JJS_ERR_ARG, "null or misaligned pointer");
     const msig_group_copy* c = copy_for(*k, g);
     if (!c) return fail(JJS_ERR_ARG, "the signer group has no copy on this device");
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = ensure_msig_scratch(n, n_transcripts)) return rc;
+    if (int rc = ensure_msig_scratch(n, n_transcripts, ext ? n : 0)) return rc;
+    const uint8_t* pts[2] = {(const uint8_t*)R, (const uint8_t*)S};
     msig_group_params G{};
     msig_params& P = G.M;
-    P.z = (const uint8_t*)z; P.R = (const uint8_t*)R; P.S = (const uint8_t*)S; P.m = (const uint8_t*)m;
+    P.z = (const uint8_t*)z; P.m = (const uint8_t*)m;
     P.n_transcripts = (uint32_t)n_transcripts; P.n_total = n;
     P.share_status = (uint8_t*)share_status; P.sig_u = (uint8_t*)sig_u; P.sig_R = (uint8_t*)sig_R;
     P.transcript_status = (uint8_t*)transcript_status;
@@ -147,7 +164,10 @@ int jjs_msig_group_combine_dev(jjs_msig_group h, const void* z, const void* R, c
     ++k->calls;
     big_slot();
     if (int rc = begin_shared(s)) return rc;
-    for (int pass = 0; pass < 5; ++pass) {
+    int rc_norm = JJS_OK;
+    if (ext) rc_norm = msig_normalize(W, pts, 2, n, s);
+    P.R = pts[0]; P.S = pts[1];
+    for (int pass = 0; pass < 5 && !rc_norm; ++pass) {
         if (pass == 3) {
             hipLaunchKernelGGL(msig_group_share_kernel, dim3(grid_for(g->grid_msig, n)), dim3(BLOCK), 0, s, G);
             continue;
@@ -159,8 +179,22 @@ int jjs_msig_group_combine_dev(jjs_msig_group h, const void* z, const void* R, c
     }
     const hipError_t e = hipGetLastError();
     const int rc2 = end_shared(s);              // the slot's event covers whatever was queued, also when a step failed
+    if (rc_norm) return rc_norm;
     if (e != hipSuccess) return fail(JJS_ERR_HIP, "launching the signer-group passes: %s", hipGetErrorString(e));
     return rc2;
+}
+
+int jjs_msig_group_combine_dev(jjs_msig_group h, const void* z, const void* R, const void* S, const void* m, size_t n_transcripts,
+                               void* share_status, void* transcript_status, void* sig_u, void* sig_R, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    return msig_group_combine_locked(h, false, z, R, S, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, (hipStream_t)stream);
+}
+int jjs_msig_group_combine_ext_dev(jjs_msig_group h, const void* z, const void* R_ext, const void* S_ext, const void* m, size_t n_transcripts,
+                                   void* share_status, void* transcript_status, void* sig_u, void* sig_R, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    return msig_group_combine_locked(h, true, z, R_ext, S_ext, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -333,7 +333,8 @@ int launch_normalize(normalize_params N, uint64_t first, uint64_t count, uint64_
         if (blocks > 512) blocks = 512;
     }
     if (blocks < by_share) blocks = by_share;
-    hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, s, N);
+    if (N.poison) hipLaunchKernelGGL(msig_normalize_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, s, N);      // the multisignature calls
+    else hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, s, N);
     HIP_TRY(hipGetLastError());
     return JJS_OK;
 }
