@@ -431,6 +431,43 @@ int jjs_multisig_combine(int format, const uint8_t* z, const uint8_t* PK, const 
 int jjs_msig_group_combine(jjs_msig_group g, int format, const uint8_t* z, const uint8_t* R, const uint8_t* S, const uint8_t* m,
                            size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status, uint8_t* sig_u, uint8_t* sig_R);
 
+/* ---- multisignature for committees drawn from a registered key set ----------------------------------------------
+ * A validator set registered once (jjs_keyset_create, JJS_SCHEME_SINGLE, any key format) of which every message is signed by
+ * another ordered subset: d_i = H(pk_i, pk_1 .. pk_n) changes with the subset, so a signer group does not fit, and the inline
+ * call rebuilds, in every lane, window tables the set already keeps on the device.  These calls take the inline call's ragged
+ * transcripts with the keys named by index: key_idx is N x uint32 (4-byte aligned for the _dev form), one entry per share,
+ * instead of the PK column (4 bytes a share instead of 64 or 96; no key is normalised in the extended format).  `format` is
+ * that of R and S: JJS_FORMAT_AFFINE (N x 64) or JJS_FORMAT_EXT (N x 96, normalised on the device as in
+ * jjs_msig_group_combine_ext_dev); JJS_FORMAT_WIRE gives -1.  z, m, offsets, n_transcripts, every output and its layout, the
+ * limits, the alignment and the asynchrony on `stream` are those of jjs_multisig_combine_dev.  The call acts on the calling
+ * thread's current device and uses that device's copy of the set; launches already queued keep reading a destroyed set until
+ * jjs_trim, as for jjs_keyset_verify_dev.  -1 for a set of another scheme and for an unknown or destroyed handle; -4 before
+ * jjs_init; n_transcripts == 0 returns 0 and writes nothing.
+ * Contract.  A row is USABLE when key_idx[i] < n_keys and key_status[key_idx[i]] == 0.
+ *   A transcript whose rows are all usable: every output (share_status, transcript_status, agg_pk, sig_u, sig_R) is, byte for
+ *     byte, what jjs_multisig_combine_dev writes for it with PK[i] = the registered key's canonical affine bytes (extended
+ *     format: what jjs_multisig_combine_ext_dev writes on the same affine keys expanded with Z = 1) -- rows with z >= r,
+ *     m >= q, or an R or S coordinate >= q or unusable included.  Only the two products by PK_i change method (a walk of 43
+ *     additions over the set's stored tables instead of a table built in the lane and a multiplication); a registered valid key
+ *     is on the curve, so both give the same group element, and every comparison and output is made in affine form.
+ *   A transcript that names an unusable row: every share of it gets status 3, transcript_status is 3, agg_pk[t], sig_u[t] and
+ *     sig_R[t] are all zero; the other transcripts of the call are not affected.  No lane reads outside the set: an unusable
+ *     row is replaced by a stand-in before any key or table is addressed.
+ *   An empty transcript gives status 5, as inline.
+ *   DIFFERENCE FROM THE REFERENCE: its multisignature validates no key; a key set refuses the identity, small-order and
+ *     off-curve keys (key_status 1) and non-canonical ones (3).  A committee with such a key uses the inline call.
+ * Per share the call runs the inline call's hashes, ONE variable-base multiplication (a * S_i), a comb and two walks of 43
+ * additions, against three variable-base multiplications and a comb inline.  These are operation counts; rates against the
+ * inline call: not measured (the record profiles/r11_msig_keyset.jsonl of tools/msig_keyset_rate.py does not exist yet).
+ * jjs_multisig_combine_keyset: the same from HOST buffers, blocking, as jjs_multisig_combine: no alignment is asked of the
+ * pointers, transcript_status may be NULL, one such call at a time per device. */
+int jjs_multisig_combine_keyset_dev(jjs_keyset ks, int format, const void* key_idx, const void* z, const void* R, const void* S,
+                                    const void* m, const uint32_t* offsets_host, size_t n_transcripts, void* share_status,
+                                    void* transcript_status, void* agg_pk, void* sig_u, void* sig_R, void* stream);
+int jjs_multisig_combine_keyset(jjs_keyset ks, int format, const uint32_t* key_idx, const uint8_t* z, const uint8_t* R,
+                                const uint8_t* S, const uint8_t* m, const uint32_t* offsets, size_t n_transcripts,
+                                uint8_t* share_status, uint8_t* transcript_status, uint8_t* agg_pk, uint8_t* sig_u, uint8_t* sig_R);
+
 /* ---- transcript parity (debug export): c_out = n x 32 bytes, the 250-bit challenge per item ---- */
 int jjs_challenge_single_dev(const void* R, const void* PK, const void* m, size_t n, void* c_out, void* stream);
 int jjs_challenge_double_dev(const void* R, const void* R_prime, const void* PK, const void* PK_prime, const void* m,

@@ -321,6 +321,7 @@ inline bool verify_all_vargen(const std::vector<PublicKeyVarGen::Item>& items, s
 
 // Registered key sets (include/jjs_gpu.h jjs_keyset_*): keys validated and tabled once on the device, then verified against by
 // index.  Move-only; the destructor destroys the set (calls already queued on a stream still complete).
+namespace multisig { struct CombineResult; }
 class KeySet {
   public:
     // raw form: scheme JJS_SCHEME_*, key format JJS_FORMAT_* and the key columns of jjs_keyset_create
@@ -368,6 +369,21 @@ class KeySet {
         if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_verify_all");
         return verdict == 1;
     }
+    // raw form of the multisignature call against the set (jjs_multisig_combine_keyset): host buffers, blocking; the columns and
+    // outputs of jjs_multisig_combine with key_idx (N x uint32) in place of PK; format JJS_FORMAT_AFFINE or JJS_FORMAT_EXT (R, S)
+    void multisig_combine(int format, const uint32_t* key_idx, const uint8_t* z, const uint8_t* R, const uint8_t* S, const uint8_t* m,
+                          const uint32_t* offsets, size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status, uint8_t* agg_pk,
+                          uint8_t* sig_u, uint8_t* sig_R) const {
+        int rc = jjs_multisig_combine_keyset(handle_, format, key_idx, z, R, S, m, offsets, n_transcripts, share_status, transcript_status, agg_pk,
+                                             sig_u, sig_R);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_combine_keyset");
+    }
+    // `combine` of ONE transcript whose signers are keys of this set (scheme single), named by index in the committee's order;
+    // R and S as the Rust side holds them.  A transcript that names an index outside the set or a key whose key_status is not 0
+    // is refused by the engine: BytesError with the index of its first such row (defined behind multisig::CombineResult).
+    inline multisig::CombineResult multisig_combine(const std::vector<uint32_t>& key_idx, const std::vector<JubJubScalar>& z_vec,
+                                                    const std::vector<ExtendedPoint>& R_vec, const std::vector<ExtendedPoint>& S_vec,
+                                                    const BlsScalar& msg) const;
     // (key index, signature, message): the signature type of the set's scheme
     template <typename Sig>
     struct Item { uint32_t index; Sig sig; BlsScalar message; };
@@ -446,6 +462,32 @@ inline CombineResult combine(const std::vector<JubJubScalar>& z_vec, const std::
     return CombineResult{Signature{u, R}, std::nullopt};
 }
 
+}  // namespace multisig
+
+inline multisig::CombineResult KeySet::multisig_combine(const std::vector<uint32_t>& key_idx, const std::vector<JubJubScalar>& z_vec,
+                                                        const std::vector<ExtendedPoint>& R_vec, const std::vector<ExtendedPoint>& S_vec,
+                                                        const BlsScalar& msg) const {
+    using namespace multisig;
+    const size_t n = key_idx.size();
+    if (n == 0 || z_vec.size() != n || R_vec.size() != n || S_vec.size() != n || n > 0xFFFFFFFFull)
+        return CombineResult{std::nullopt, CombineError{CombineError::InvalidMultisigTranscript, 0}};
+    const uint32_t offsets[2] = {0, (uint32_t)n};
+    std::vector<uint8_t> status(n);
+    uint8_t tstatus = 0;
+    AffinePoint agg{}, R{};
+    Scalar u{};
+    multisig_combine(JJS_FORMAT_EXT, key_idx.data(), z_vec[0].data(), R_vec[0].data(), S_vec[0].data(), msg.data(), offsets, 1, status.data(), &tstatus,
+                     agg.data(), u.data(), R.data());
+    if (tstatus)
+        for (size_t i = 0; i < n; ++i)           // a refused transcript: its first unusable row, from the indices and the set's key_status
+            if (key_idx[i] >= status_.size() || status_[key_idx[i]] != 0) return CombineResult{std::nullopt, CombineError{CombineError::BytesError, i}};
+    for (size_t i = 0; i < n; ++i)
+        if (status[i])
+            return CombineResult{std::nullopt, CombineError{status[i] == JJS_STATUS_INVALID_SHARE ? CombineError::InvalidMultisigShare : CombineError::BytesError, i}};
+    return CombineResult{Signature{u, R}, std::nullopt};
+}
+
+namespace multisig {
 class SignerGroup {
   public:
     // PK: host, n x 64 affine, the ordered pk_vec

@@ -83,6 +83,8 @@ SIGNATURES = {
     "jjs_msig_group_combine_ext_dev": [ctypes.c_uint64, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P],
     "jjs_multisig_combine": [_I, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P],
     "jjs_msig_group_combine": [ctypes.c_uint64, _I, _P, _P, _P, _P, _Z, _P, _P, _P, _P],
+    "jjs_multisig_combine_keyset_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P, _P],
+    "jjs_multisig_combine_keyset": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P],
     "jjs_verify_all_single": [_P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_double": [_P, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_vargen": [_P, _P, _P, _P, _P, _Z, _P, _P],

@@ -698,6 +698,51 @@ class KeySet:
         ok = verdict.value == 1
         return ok, (None if ok or status is None else status)
 
+    def multisig_combine(self, key_idx, z, R, S, m, offsets, fmt: str = "affine"):
+        """`Engine.multisig_combine` for committees drawn from this set (scheme "single"): key_idx (N,) uint32 names the key of
+        every share instead of a PK column; z (N, 32), R / S (N, 64) -- or (N, 96) with fmt="ext" -- m (B, 32), offsets B + 1
+        ints (host).  torch CUDA tensors run asynchronously on the current stream (jjs_multisig_combine_keyset_dev; key_idx an
+        int32 / uint32 tensor), numpy arrays block (jjs_multisig_combine_keyset).  Returns the tuple of
+        `Engine.multisig_combine`, byte for byte what it gives with the registered keys in the PK column -- except that a
+        transcript naming an index outside the set or a key whose `key_status` is not 0 is refused: status 3 on all its
+        shares and on the transcript, agg_pk / sig_u / sig_R zero."""
+        if self.handle == 0:
+            raise _ffi.JjsError("the key set is closed")
+        w = Engine._msig_width(fmt)
+        fmt_id = Engine._FORMAT_IDS[fmt]
+        offs = np.ascontiguousarray(offsets, dtype=np.uint32)
+        B, N = len(offs) - 1, z.shape[0]
+        if not _is_torch(z):
+            hidx = np.asarray(key_idx)
+            if hidx.dtype.kind not in "iu":
+                raise ValueError("key indices must be integers")
+            hidx = np.ascontiguousarray(hidx, dtype=np.uint32)
+            h = self._eng._host
+            hz, hr, hs, hm = h(z, 32), h(R, w), h(S, w), h(m, 32)
+            if hidx.shape != (N,) or any(x.shape[0] != N for x in (hr, hs)) or hm.shape[0] != B or (B and int(offs[-1]) != N):
+                raise ValueError("the columns do not have the rows the offsets ask for")
+            status, tstatus = np.zeros(N, np.uint8), np.zeros(B, np.uint8)
+            agg, su, sr = np.zeros((B, 64), np.uint8), np.zeros((B, 32), np.uint8), np.zeros((B, 64), np.uint8)
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+            _ffi.check(self._lib.jjs_multisig_combine_keyset(self.handle, fmt_id, p(hidx), p(hz), p(hr), p(hs), p(hm), p(offs), B, p(status),
+                                                             p(tstatus), p(agg), p(su), p(sr)), "jjs_multisig_combine_keyset")
+            return status, agg, su, sr, tstatus
+        import torch
+        if not (_is_torch(key_idx) and key_idx.is_cuda and key_idx.is_contiguous() and key_idx.shape == (N,)
+                and key_idx.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+            raise ValueError("expected a contiguous 1-d CUDA tensor of int32 / uint32 indices, one per share")
+        dev_ = z.device
+        new = lambda rows, w: torch.empty((max(rows, 1), w), dtype=torch.uint8, device=dev_)[:rows]  # noqa: E731
+        status = torch.empty(max(N, 1), dtype=torch.uint8, device=dev_)[:N]
+        tstatus = torch.empty(max(B, 1), dtype=torch.uint8, device=dev_)[:B]
+        agg, su, sr = new(B, 64), new(B, 32), new(B, 64)
+        o = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        d = Engine._dev_ptr
+        _ffi.check(self._lib.jjs_multisig_combine_keyset_dev(self.handle, fmt_id, o(key_idx), d(z, 32, N), d(R, w, N), d(S, w, N),
+                                                             d(m, 32, B), offs.ctypes.data_as(ctypes.c_void_p), B, o(status), o(tstatus),
+                                                             o(agg), o(su), o(sr), Engine._stream()), "jjs_multisig_combine_keyset_dev")
+        return status, agg, su, sr, tstatus
+
     def info(self) -> dict:
         out = (ctypes.c_uint64 * len(self.INFO_NAMES))()
         _ffi.check(self._lib.jjs_keyset_info(self.handle, out), "jjs_keyset_info")

@@ -780,3 +780,27 @@ __global__ __launch_bounds__(BLOCK, 2) void msig_group_share_kernel(msig_group_p
     const uint64_t total = (uint64_t)gridDim.x * BLOCK;
     for (uint64_t k = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; k < G.M.n_total; k += total) mg_share_item(G, mg_share_of_lane(G, k));
 }
+
+// ---- multisig over a registered key set (msig_keyset.h) --------------------------------------------------
+// The gather behind pass 0 and the refusals behind pass 6: a lane per share / per transcript, grid-stride
+__global__ __launch_bounds__(BLOCK) void msig_keyset_gather_kernel(msig_keyset_params K) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < K.M.n_total; i += total) mk_gather_item(K, i);
+}
+__global__ __launch_bounds__(BLOCK) void msig_keyset_refuse_kernel(msig_keyset_params K) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; t < K.M.n_transcripts; t += total) mk_refuse_item(K, (uint32_t)t);
+}
+// pass 1 over the set's tables (msig_kernel's lane rules: eight lanes per share when the call has few); no workspace
+__global__ __launch_bounds__(BLOCK, 2) void msig_keyset_delin_kernel(msig_keyset_params K) {
+    const uint64_t gtid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    const uint32_t hl = K.M.hash_lanes;
+    const int coop = hl > 1 ? (int)(gtid % hl) : -1;
+    for (uint64_t i = gtid / hl; i < K.M.n_total; i += total / hl) mk_delin_item(K, i, coop);
+}
+// pass 5: a comb and a walk over the set's tables per share; no workspace
+__global__ __launch_bounds__(BLOCK, 2) void msig_keyset_share_kernel(msig_keyset_params K) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < K.M.n_total; i += total) mk_share_item(K, i);
+}

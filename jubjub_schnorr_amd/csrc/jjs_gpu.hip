@@ -21,6 +21,7 @@
 //   (here)             device set-up and tear-down, the RCCL clique
 //   host_calls.h       the large blocking host-buffer calls: upload plan, staging copies, the pipeline
 //   msig_host_calls.h  the blocking host-buffer forms of the multisignature calls
+//   msig_keyset_calls.h  the multisignature call against a registered key set, both forms
 //   host_lanes.h       the small ones (included among the entry points, behind the table of call shapes): staging lanes
 //                      outside the engine's mutex, calls of several threads in one launch
 //   (here)             the table of call shapes and the staged_call builder it drives; the extern "C" entry points
@@ -62,6 +63,7 @@
 #include "sign_core.h"
 #include "multisig_core.h"
 #include "msig_group.h"
+#include "msig_keyset.h"
 #include "batch_verdict.h"
 #include "keyset_verdict.h"
 #include "jjs_sponge_tags_long.inc"
@@ -797,15 +799,20 @@ int jjs_compress_dev(const void* affine, size_t n, void* out, void* stream) {
 // in words: tr_of (1), d_words (8), dpk and e_pt (EXT_WORDS each) per share, then a_words and c_words (8 each), the offsets
 // (1, and one more) and the long tags (18) per transcript.  Behind them, once an *_ext call has asked for it (g->msig_ext_rows
 // rows; affine callers never pay for it): three columns of normalised points (64 bytes per row each) and the 9 words of prefix
-// product per row that normalize_lane keeps.
+// product per row that normalize_lane keeps.  Behind those, once a key-set call (msig_keyset.h) has asked for it (g->msig_ks_rows
+// rows in g->msig_ks_transcripts transcripts; no other caller pays for it): the gathered key column (64 bytes per row), the
+// table index of every row (4) and the refused word of every transcript (4).
 struct msig_scratch {
     uint32_t *tr_of, *d_words, *dpk, *e_pt, *a_words, *c_words, *offsets, *long_tags;
     uint8_t* norm[3];
     uint32_t* prefix;
+    uint8_t* ks_pk;
+    uint32_t *ks_row_key, *ks_refused;
 };
 constexpr size_t MSIG_EXT_ROW_BYTES = 3 * 64 + 9 * 4;
-static size_t msig_scratch_bytes(size_t items, size_t transcripts, size_t ext_rows) {
-    return items * 4 * (1 + 8 + 2 * EXT_WORDS) + transcripts * 4 * (16 + 1 + 18) + 64 + (ext_rows ? ext_rows * MSIG_EXT_ROW_BYTES + 64 : 0);
+static size_t msig_scratch_bytes(size_t items, size_t transcripts, size_t ext_rows, size_t ks_rows = 0, size_t ks_transcripts = 0) {
+    return items * 4 * (1 + 8 + 2 * EXT_WORDS) + transcripts * 4 * (16 + 1 + 18) + 64 + (ext_rows ? ext_rows * MSIG_EXT_ROW_BYTES + 64 : 0) +
+           (ks_rows ? ks_rows * (64 + 4) + ks_transcripts * 4 + 128 : 0);
 }
 static msig_scratch msig_scratch_carve() {
     msig_scratch W{};
@@ -822,20 +829,33 @@ static msig_scratch msig_scratch_carve() {
         uint8_t* q = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(w) + 63) & ~uintptr_t(63));
         for (int k = 0; k < 3; ++k) { W.norm[k] = q; q += 64 * g->msig_ext_rows; }
         W.prefix = reinterpret_cast<uint32_t*>(q);
+        w = W.prefix + 9 * g->msig_ext_rows;
+    }
+    if (g->msig_ks_rows) {
+        uint8_t* q = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(w) + 63) & ~uintptr_t(63));
+        W.ks_pk = q; q += 64 * g->msig_ks_rows;
+        W.ks_row_key = reinterpret_cast<uint32_t*>(q);
+        W.ks_refused = W.ks_row_key + g->msig_ks_rows;
     }
     return W;
 }
-static int ensure_msig_scratch(size_t n, size_t n_transcripts, size_t ext_rows = 0) {
-    if (n <= g->msig_items && n_transcripts <= g->msig_transcripts && ext_rows <= g->msig_ext_rows) return JJS_OK;
+static int ensure_msig_scratch(size_t n, size_t n_transcripts, size_t ext_rows = 0, size_t ks_rows = 0, size_t ks_transcripts = 0) {
+    if (n <= g->msig_items && n_transcripts <= g->msig_transcripts && ext_rows <= g->msig_ext_rows && ks_rows <= g->msig_ks_rows &&
+        ks_transcripts <= g->msig_ks_transcripts)
+        return JJS_OK;
     size_t ci = grown(n < 4096 ? 4096 : n), ct = grown(n_transcripts < 1024 ? 1024 : n_transcripts);
     size_t ce = ext_rows ? grown(ext_rows < 4096 ? 4096 : ext_rows) : 0;
     if (ci < g->msig_items) ci = g->msig_items;
     if (ct < g->msig_transcripts) ct = g->msig_transcripts;
     if (ce < g->msig_ext_rows) ce = g->msig_ext_rows;
+    size_t ck = ks_rows ? grown(ks_rows < 4096 ? 4096 : ks_rows) : 0, ckt = ks_rows ? grown(ks_transcripts < 1024 ? 1024 : ks_transcripts) : 0;
+    if (ck < g->msig_ks_rows) ck = g->msig_ks_rows;
+    if (ckt < g->msig_ks_transcripts) ckt = g->msig_ks_transcripts;
     device_mem<uint8_t> fresh;
-    HIP_TRY(fresh.alloc(msig_scratch_bytes(ci, ct, ce)));
+    HIP_TRY(fresh.alloc(msig_scratch_bytes(ci, ct, ce, ck, ckt)));
     g->msig.replace(std::move(fresh));
     g->msig_items = ci; g->msig_transcripts = ct; g->msig_ext_rows = ce;
+    g->msig_ks_rows = ck; g->msig_ks_transcripts = ckt;
     return JJS_OK;
 }
 // The normalisation in front of the passes of an extended call: `cols` columns of n rows (96 bytes a point) into the scratch's
@@ -927,6 +947,7 @@ int jjs_multisig_combine_ext_dev(const void* z, const void* PK_ext, const void* 
 
 #include "msig_group_calls.h"
 #include "msig_host_calls.h"
+#include "msig_keyset_calls.h"
 
 // ---- challenge export ---------------------------------------------------------------------------
 static int launch_challenge(challenge_params P, void* stream) {
