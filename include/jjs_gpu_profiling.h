@@ -2,7 +2,7 @@
  * Extra entry points of the PROFILING build of the engine (jubjub_schnorr_amd/libjjs_gpu_prof.so, compiled from
  * the same sources with -DJJS_PROFILING).  They switch verification work off or let several logical devices share
  * one card, so they are compiled OUT of the product library libjjs_gpu.so (tests/test_abi.py checks that the
- * symbols are absent there).  Used only by jubjub_schnorr_amd/tools/phase_profile.py and tests/multidevice_child.py.
+ * symbols are absent there).  Used only by the tools under jubjub_schnorr_amd/tools/ and by the child processes of the GPU tests.
  */
 #ifndef JJS_GPU_PROFILING_H
 #define JJS_GPU_PROFILING_H
@@ -46,6 +46,23 @@ int jjs_debug_pin_hash_seed(int on);
  * out[5] until everything was queued, out[6] waiting for the device to drain after that, out[7] copying the statuses
  * out. */
 int jjs_debug_host_timing(double out[8]);
+/* The bucket MSM of jjs_verify_all_* over the caller's own terms, every stage's output copied out (tests/test_msm_gpu.py).
+ * points: n_kinds * n affine points (64 bytes, canonical); scalars: as many, 32 bytes each, below 2^252 (short_shape != 0:
+ * within msm_weight_bits(c) bits); term t is negated when bit t / n of neg_kinds is set; c: the window width, 8 .. 16.
+ * The call carves the slot's verdict scratch, stores the terms, clears what a verdict call clears and runs the call's own
+ * MSM launches.  off_out: W * B + 1 words, the buckets' offsets; order_out: room for n_kinds * n * W words, of which
+ * off[W * B] are written, the sorted entries (term, bit 31: negated); win_out: W extended points (X, Y, Z, T of 9 limbs
+ * each, Montgomery form); total_out: one extended point, the windows combined.  Device pointers, 16-byte aligned;
+ * asynchronous on `stream`. */
+int jjs_debug_msm_dev(const void* points, const void* scalars, size_t n, unsigned n_kinds, unsigned neg_kinds, int c, int short_shape,
+                      void* off_out, void* order_out, void* win_out, void* total_out, void* stream);
+/* The run sums and key points of jjs_keyset_verify_all* under the caller's own scalar columns: the call's grouping of the
+ * items by key, then its run and key kernels.  key_idx: n indices inside the set; a0, a1: n x 32 bytes, every value below r,
+ * the items' scalars on point column 0 / 1 (a1 is not read for a set with one point column).  sums_out: S_k of every
+ * (point column, key), 32 bytes each, column 0 first; point_out: one extended point, the sum of S_k * P_k over both
+ * columns.  Device pointers, 16-byte aligned; asynchronous on `stream`. */
+int jjs_debug_keyset_sums_dev(jjs_keyset ks, const void* key_idx, const void* a0, const void* a1, size_t n, void* sums_out, void* point_out,
+                              void* stream);
 
 #ifdef __cplusplus
 }

@@ -100,6 +100,8 @@ PROFILING_SIGNATURES = {
     "jjs_debug_host_timing": [_P],
     "jjs_debug_fail_key_arena": [_I],
     "jjs_debug_pin_hash_seed": [_I],
+    "jjs_debug_msm_dev": [_P, _P, _Z, ctypes.c_uint, ctypes.c_uint, _I, _I, _P, _P, _P, _P, _P],
+    "jjs_debug_keyset_sums_dev": [ctypes.c_uint64, _P, _P, _P, _Z, _P, _P, _P],
 }
 _RESTYPES = {"jjs_shutdown": None, "jjs_last_error": ctypes.c_char_p, "jjs_debug_comb_table_bytes": _Z}
 

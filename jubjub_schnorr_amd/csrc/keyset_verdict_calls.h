@@ -18,14 +18,50 @@ static bool keyset_verdict_route(int scheme, int format, size_t n) {
     return n >= KEYSET_VERDICT_MIN_ITEMS[scheme];
 }
 
+// The key points of a call over n items against k (ksv_run_kernel, ksv_key_kernel): their geometry and their parts of the
+// verdict scratch, behind the MSM's: the items' scalars, the heads and the cells of the runs per point column, the blocks'
+// key points.
+struct ksv_key_geometry {
+    uint32_t cells, point_blocks;
+    size_t extra[7];
+};
+static ksv_key_geometry ksv_key_parts(const keyset_entry& k, size_t n) {
+    ksv_key_geometry G{};
+    G.cells = ksv_cells(n);
+    G.point_blocks = (uint32_t)(((uint64_t)k.n_cols * k.n_keys + BLOCK - 1) / BLOCK);
+    const size_t second = k.n_cols > 1 ? 1 : 0;          // (no second point column: no second scalar column)
+    const size_t extra[7] = {n * 32, second * n * 32, (size_t)k.n_keys * 32, second * k.n_keys * 32, (size_t)G.cells * 32, second * G.cells * 32,
+                             (size_t)G.point_blocks * MSM_EXT_WORDS * 4};
+    for (int i = 0; i < 7; ++i) G.extra[i] = extra[i];
+    return G;
+}
+// ... their descriptor over the front's sort (F), the scalar columns a0 / a1 and the carved parts q[2 .. 6]
+static ksv_key_params ksv_key_setup(const keyset_entry& k, const keyset_copy& c, const keyset_front& F, size_t n, const uint8_t* a0,
+                                    const uint8_t* a1, uint8_t* const* q) {
+    const uint32_t stride = k.n_keys < CURSOR_DENSE_FROM ? CURSOR_STRIDE : 1u;
+    ksv_key_params S{};
+    S.R = ksv_runs{F.K.key_cursor, stride, F.K.order, F.X.keyid, k.n_keys, n};
+    S.n_cols = k.n_cols;
+    S.a[0] = a0; S.a[1] = a1;
+    for (int i = 0; i < 2; ++i) {
+        S.head[i] = q[2 + i]; S.cell[i] = q[4 + i];
+        S.key_flags[i] = c.flags[i]; S.tables[i] = c.tables[i];
+    }
+    S.points = reinterpret_cast<uint32_t*>(q[6]);
+    return S;
+}
+// ... and their launches: the runs' pieces, then S_k * PK_k over the set's tables
+static void ksv_key_launch(const keyset_entry& k, const ksv_key_geometry& G, const ksv_key_params& S, hipStream_t s) {
+    hipLaunchKernelGGL(ksv_run_kernel, dim3((unsigned)grid_for(8192, (size_t)k.n_cols * (k.n_keys + G.cells))), dim3(BLOCK), 0, s, S);
+    hipLaunchKernelGGL(ksv_key_kernel, dim3(G.point_blocks), dim3(BLOCK), 0, s, S);
+}
+
 // The verdict algorithm on stream s (under L.mu; g is c's device): d = key_idx, u, R, R', m (device, affine signatures).
 static int keyset_verdict_launch_msm(keyset_entry& k, const keyset_copy& c, const void* const* d, size_t n, uint32_t* verdict, hipStream_t s) {
     ksv_params B{};
     if (int rc = batch_seed(B.seed)) return rc;
     keyset_front F;
     if (int rc = keyset_front_end(k, c, d[0], n, true, s, F)) return rc;
-    const key_params& K = F.K;
-    const uint32_t stride = k.n_keys < CURSOR_DENSE_FROM ? CURSOR_STRIDE : 1u;
     B.V = keyset_params(k.scheme, c, (const uint8_t*)d[1], (const uint8_t*)d[2], (const uint8_t*)d[3], (const uint8_t*)d[4], n,
                         out_ptrs{nullptr, nullptr, nullptr, nullptr});
     B.n_cols = k.n_cols;
@@ -38,23 +74,13 @@ static int keyset_verdict_launch_msm(keyset_entry& k, const keyset_copy& c, cons
     static_cast<msm_shape&>(M) = msm_shape_short(msm_window(msm_pick_short_window(M.N)));
     B.z_bits = msm_weight_bits(M.c);
     const uint32_t blocks = (uint32_t)grid_for(g->grid_prepare, n);
-    const uint32_t cells = ksv_cells(n), point_blocks = (uint32_t)(((uint64_t)k.n_cols * k.n_keys + BLOCK - 1) / BLOCK);
-    const size_t nb = (size_t)M.W * M.B, second = k.n_cols > 1 ? 1 : 0;       // (no second point column: no second scalar column)
-    // behind the MSM's parts: the items' scalars, the heads and the cells of the runs per point column, the blocks' key points
-    const size_t extra[7] = {n * 32, second * n * 32, (size_t)k.n_keys * 32, second * k.n_keys * 32, (size_t)cells * 32, second * cells * 32,
-                             (size_t)point_blocks * MSM_EXT_WORDS * 4};
+    const size_t nb = (size_t)M.W * M.B;
+    const ksv_key_geometry G = ksv_key_parts(k, n);
     uint8_t* q[7];
     uint32_t* span_sum = nullptr;
-    if (int rc = verdict_scratch(B, M, blocks, extra, 7, q, span_sum)) return rc;
+    if (int rc = verdict_scratch(B, M, blocks, G.extra, 7, q, span_sum)) return rc;
     B.a[0] = q[0]; B.a[1] = q[1];
-    ksv_key_params S{};
-    S.R = ksv_runs{K.key_cursor, stride, K.order, F.X.keyid, k.n_keys, n};
-    S.n_cols = k.n_cols;
-    for (int i = 0; i < 2; ++i) {
-        S.a[i] = B.a[i]; S.head[i] = q[2 + i]; S.cell[i] = q[4 + i];
-        S.key_flags[i] = c.flags[i]; S.tables[i] = c.tables[i];
-    }
-    S.points = reinterpret_cast<uint32_t*>(q[6]);
+    const ksv_key_params S = ksv_key_setup(k, c, F, n, B.a[0], B.a[1], q);
 
     if (int rc = begin_shared(s)) return rc;
     clear_params Z{};
@@ -64,11 +90,9 @@ static int keyset_verdict_launch_msm(keyset_entry& k, const keyset_copy& c, cons
     hipLaunchKernelGGL(clear_kernel, dim3((unsigned)grid_for(256, (nb > n ? nb : n) / 16 + 1)), dim3(BLOCK), 0, s, Z);
     keyset_front_launch(F, true, s);
     hipLaunchKernelGGL(ksv_item_kernel, dim3(blocks), dim3(BLOCK), 0, s, B);
-    // the key points: the runs' pieces, then S_k * PK_k over the set's tables
-    hipLaunchKernelGGL(ksv_run_kernel, dim3((unsigned)grid_for(8192, (size_t)k.n_cols * (k.n_keys + cells))), dim3(BLOCK), 0, s, S);
-    hipLaunchKernelGGL(ksv_key_kernel, dim3(point_blocks), dim3(BLOCK), 0, s, S);
+    ksv_key_launch(k, G, S, s);
     msm_launch(M, span_sum, s);                          // over the R terms
-    hipLaunchKernelGGL(ksv_final_kernel, dim3(1), dim3(BLOCK), 0, s, B, M, blocks, (const uint32_t*)S.points, point_blocks, verdict);
+    hipLaunchKernelGGL(ksv_final_kernel, dim3(1), dim3(BLOCK), 0, s, B, M, blocks, (const uint32_t*)S.points, G.point_blocks, verdict);
     HIP_TRY(hipGetLastError());
     return end_shared(s);
 }
@@ -150,5 +174,44 @@ int jjs_keyset_verify_all(jjs_keyset ks, int format, const uint32_t* key_idx, co
                             },
                             per_item, status, verdict);
 }
+
+#if defined(JJS_PROFILING)
+// include/jjs_gpu_profiling.h: the run sums and the key points of keyset_verdict_launch_msm under the caller's own scalar
+// columns -- the same front end, scratch, descriptor and launches, then dbg_ksv_sums_kernel
+int jjs_debug_keyset_sums_dev(jjs_keyset ks, const void* key_idx, const void* a0, const void* a1, size_t n, void* sums_out, void* point_out,
+                              void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    keyset_entry* k = g_keysets.find(ks);
+    if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
+    if (n == 0 || n >= 0x80000000ull) return fail(JJS_ERR_ARG, "the item count is out of range");
+    if (!all_ok(key_idx, a0, sums_out, point_out) || (k->n_cols > 1 && !all_ok(a1))) return fail(JJS_ERR_ARG, "null or misaligned pointer");
+    const keyset_copy* c = copy_for(*k, g);
+    if (!c) return fail(JJS_ERR_ARG, "the key set has no copy on this device");
+    hipStream_t s = (hipStream_t)stream;
+    return no_throw([&]() -> int {
+        keyset_front F;
+        if (int rc = keyset_front_end(*k, *c, key_idx, n, true, s, F)) return rc;
+        ksv_params B{};
+        msm_params M{};                                      // no terms: the smallest shape
+        M.n = n;
+        static_cast<msm_shape&>(M) = msm_shape_short(8);
+        const ksv_key_geometry G = ksv_key_parts(*k, n);
+        uint8_t* q[7];
+        uint32_t* span_sum = nullptr;
+        if (int rc = verdict_scratch(B, M, 1, G.extra, 7, q, span_sum)) return rc;
+        const ksv_key_params S = ksv_key_setup(*k, *c, F, n, (const uint8_t*)a0, (const uint8_t*)a1, q);
+        if (int rc = begin_shared(s)) return rc;
+        clear_params Z{};
+        Z.p[2] = wire_bad(); Z.bytes[2] = n;
+        hipLaunchKernelGGL(clear_kernel, dim3((unsigned)grid_for(256, n / 16 + 1)), dim3(BLOCK), 0, s, Z);
+        keyset_front_launch(F, true, s);
+        ksv_key_launch(*k, G, S, s);
+        hipLaunchKernelGGL(dbg_ksv_sums_kernel, dim3(G.point_blocks), dim3(BLOCK), 0, s, S, G.point_blocks, (uint8_t*)sums_out, (uint32_t*)point_out);
+        HIP_TRY(hipGetLastError());
+        return end_shared(s);
+    });
+}
+#endif
 
 }  // extern "C"

@@ -81,3 +81,21 @@ __global__ __launch_bounds__(BLOCK) void ksv_final_kernel(ksv_params B, msm_para
         *verdict = bv_verdict(B.V, total, zu, *B.fail != 0u) ? 1u : 0u;
     }
 }
+
+#if defined(JJS_PROFILING)
+// jjs_debug_keyset_sums_dev (include/jjs_gpu_profiling.h): S_k of every (point column, key), 32 bytes each, and, from one
+// lane, the sum of the blocks' key points
+__global__ __launch_bounds__(BLOCK) void dbg_ksv_sums_kernel(ksv_key_params S, uint32_t point_blocks, uint8_t* sums_out, uint32_t* point_out) {
+    const uint64_t id = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (id < (uint64_t)S.n_cols * S.R.n_keys) {
+        const bool second = id >= S.R.n_keys;
+        store_words(sums_out, id, ksv_key_sum(S.R, second ? S.head[1] : S.head[0], second ? S.cell[1] : S.cell[0],
+                                              (uint32_t)(second ? id - S.R.n_keys : id)));
+    }
+    if (id == 0) {
+        ext_pt sum = ext_identity();
+        for (uint32_t b = 0; b < point_blocks; ++b) sum = msm_add_ext(sum, msm_load_ext(S.points + (size_t)b * MSM_EXT_WORDS));
+        msm_store_ext(point_out, sum);
+    }
+}
+#endif

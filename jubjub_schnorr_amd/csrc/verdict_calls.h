@@ -264,5 +264,41 @@ int jjs_verify_all_vargen_dev(const void* u, const void* R, const void* PK, cons
     return verdict_dev(JJS_SCHEME_VARGEN, d, n, verdict, stream);
 }
 
+#if defined(JJS_PROFILING)
+// include/jjs_gpu_profiling.h: the MSM of a verdict call over the caller's own terms -- verdict_scratch, the calls' clear,
+// msm_launch -- with every stage's output copied out
+int jjs_debug_msm_dev(const void* points, const void* scalars, size_t n, unsigned n_kinds, unsigned neg_kinds, int c, int short_shape,
+                      void* off_out, void* order_out, void* win_out, void* total_out, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    if (n == 0 || n_kinds < 1 || n_kinds > 4 || (uint64_t)n_kinds * n >= 0x80000000ull) return fail(JJS_ERR_ARG, "the term count is out of range");
+    if (c < 8 || c > MSM_MAX_WINDOW) return fail(JJS_ERR_ARG, "the window width is out of range");
+    if (!all_ok(points, scalars, off_out, order_out, win_out, total_out)) return fail(JJS_ERR_ARG, "null or misaligned pointer");
+    hipStream_t s = (hipStream_t)stream;
+    return no_throw([&]() -> int {
+        bv_params B{};
+        msm_params M{};
+        M.n = n; M.N = (uint64_t)n_kinds * n;
+        M.neg_kinds = neg_kinds & ((1u << n_kinds) - 1u);
+        static_cast<msm_shape&>(M) = short_shape ? msm_shape_short(c) : msm_shape_full(c);
+        pick_slot(n, s);
+        uint32_t* span_sum = nullptr;
+        if (int rc = verdict_scratch(B, M, 1, nullptr, 0, nullptr, span_sum)) return rc;
+        if (int rc = begin_shared(s)) return rc;
+        const size_t nb = (size_t)M.W * M.B;
+        clear_params Z{};
+        Z.p[0] = B.fail; Z.bytes[0] = 4;
+        Z.p[1] = M.off; Z.bytes[1] = (nb + 1) * 4;
+        hipLaunchKernelGGL(clear_kernel, dim3((unsigned)grid_for(256, nb / 16 + 1)), dim3(BLOCK), 0, s, Z);
+        hipLaunchKernelGGL(dbg_msm_terms_kernel, dim3((unsigned)((M.N + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const uint8_t*)points,
+                           (const uint8_t*)scalars, M.N, B.terms, B.scalars);
+        msm_launch(M, span_sum, s);
+        hipLaunchKernelGGL(dbg_msm_out_kernel, dim3((unsigned)grid_for(256, nb + 1)), dim3(BLOCK), 0, s, M, (uint32_t*)off_out, (uint32_t*)order_out,
+                           (uint32_t*)win_out, (uint32_t*)total_out);
+        HIP_TRY(hipGetLastError());
+        return end_shared(s);
+    });
+}
+#endif
 
 }  // extern "C"

@@ -171,3 +171,25 @@ __global__ __launch_bounds__(BLOCK) void bv_final_kernel(bv_params B, msm_params
 __global__ void tally_verdict_kernel(const unsigned long long* tally, uint64_t n, uint32_t* verdict) {
     if (threadIdx.x == 0) *verdict = tally[0] == n ? 1u : 0u;
 }
+
+#if defined(JJS_PROFILING)
+// jjs_debug_msm_dev (include/jjs_gpu_profiling.h): the caller's points and scalars as an item pass leaves them, one lane per term
+__global__ __launch_bounds__(BLOCK) void dbg_msm_terms_kernel(const uint8_t* points, const uint8_t* scalars, uint64_t N, uint32_t* terms,
+                                                              uint8_t* term_scalars) {
+    const uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= N) return;
+    const fe_src src{points, 64, 0};
+    msm_store_term(terms + t * MSM_TERM_WORDS, load_fq(src, t), load_fq(src, t, 32));
+    store_words(term_scalars, t, load_words(fe_src{scalars, 32, 0}, t));
+}
+// ... and what the MSM left: off (W * B + 1 words), order (off[W * B] words), win (W points), msm_combine(win) from one lane
+__global__ __launch_bounds__(BLOCK) void dbg_msm_out_kernel(msm_params M, uint32_t* off_out, uint32_t* order_out, uint32_t* win_out,
+                                                            uint32_t* total_out) {
+    const uint64_t nb = (uint64_t)M.W * M.B, total = (uint64_t)gridDim.x * BLOCK, id = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint64_t room = M.N * (uint64_t)M.W, entries = M.off[nb] < room ? M.off[nb] : room;
+    for (uint64_t i = id; i <= nb; i += total) off_out[i] = M.off[i];
+    for (uint64_t i = id; i < entries; i += total) order_out[i] = M.order[i];
+    for (uint64_t i = id; i < (uint64_t)M.W * MSM_EXT_WORDS; i += total) win_out[i] = M.win[i];
+    if (id == 0) msm_store_ext(total_out, msm_combine(M.win, M.W, M.c));
+}
+#endif

@@ -1,5 +1,5 @@
 // CPU build of csrc/keyset_verdict.h (the batch verdict against a registered key set, jjs_keyset_verify_all*) for
-// tests/test_keyset_verify_all_host.py: the device's steps run here in loops with the same functions -- the set built as
+// tests/test_keyset_verify_all_host.py and tests/test_msm_host.py: the device's steps run here in loops with the same functions -- the set built as
 // keyset_harness.cpp builds it, the index pass, the keyed item pass (ksv_item), the counting sort by key, the heads and
 // cells of the runs, the key points (ksv_key_point), the bucket method (host_msm.h) over the R terms with the short
 // weights' windows, bv_verdict.  The comb tables and the double scheme's tag come from host_harness.cpp.
@@ -7,7 +7,94 @@
 #include "keyset_verdict.h"
 #include "host_msm.h"
 
+namespace {
+
+// a set built as keyset_harness.cpp builds it: flags, bases and window tables per point column (tables for the valid keys
+// only, as on the device; with poison the tables of the others are filled with 0xFF), the items' clamped key indices
+struct host_set {
+    uint32_t cols, n_keys;
+    std::vector<uint32_t> key_item, tables[2], bases[2], keyid;
+    std::vector<uint8_t> flags[2];
+    key_column col[2] = {};
+
+    host_set(int scheme, const uint8_t* keys0, const uint8_t* keys1, uint32_t n_keys_, size_t n, int poison)
+        : cols(scheme == 0 ? 1u : 2u), n_keys(n_keys_), key_item(n_keys_), keyid(n + 1) {
+        const int w = KEYSET_WINDOW;
+        const uint8_t* keys[2] = {keys0, keys1};
+        for (uint32_t k = 0; k < n_keys; ++k) key_item[k] = k;
+        const size_t key_table_words = (size_t)kt_positions(w) * kt_table_words(w);
+        for (uint32_t ci = 0; ci < cols; ++ci) {
+            key_column& C = col[ci];
+            flags[ci].assign(n_keys, 0);
+            bases[ci].assign((size_t)n_keys * kt_positions(w) * KT_BASE_WORDS + 4, 0);
+            tables[ci].assign((size_t)n_keys * key_table_words + 8, 0);
+            C.src = fe_src{keys[ci], 64, 0};
+            C.key_item = key_item.data(); C.key_flags = flags[ci].data(); C.bases = bases[ci].data();
+            C.tables = align16(tables[ci]);
+            C.keyid = keyid.data();
+            for (uint32_t k = 0; k < n_keys; ++k) {
+                if (kt_chain_key(C, k, w)) {
+                    for (uint32_t pos = 0; pos < (uint32_t)kt_positions(w); ++pos) kt_table_lane(C, k, pos, w);
+                } else if (poison) {
+                    memset(C.tables + (size_t)k * key_table_words, 0xFF, key_table_words * 4);
+                }
+            }
+        }
+    }
+};
+
+// the counting sort by key: counts, exclusive scan, scatter (the cursors end at the ends of the runs)
+void sort_by_key(const std::vector<uint32_t>& keyid, uint32_t n_keys, size_t n, std::vector<uint32_t>& cursor, std::vector<uint32_t>& order) {
+    cursor.assign(n_keys, 0); order.assign(n, 0);
+    for (uint64_t i = 0; i < n; ++i) ++cursor[keyid[i]];
+    uint32_t run = 0;
+    for (uint32_t k = 0; k < n_keys; ++k) { const uint32_t cnt = cursor[k]; cursor[k] = run; run += cnt; }
+    for (uint64_t i = 0; i < n; ++i) order[cursor[keyid[i]]++] = (uint32_t)i;
+}
+
+}  // namespace
+
 extern "C" {
+
+// The run sums and the key points alone, under the caller's own scalar columns, for n_cases cases against one set: case i has
+// ns[i] items, its key indices and its columns a0, a1 (32 bytes per item, below r; a1 NULL for single) follow those of case
+// i - 1.  sums_out = per case the S_k of point column 0 then 1 (n_keys x 32 each), point_out = per case the affine sum of
+// S_k * P_k (64 bytes).
+int jjs_ksv_host_key_sums(int scheme, const uint8_t* keys0, const uint8_t* keys1, uint32_t n_keys, size_t n_cases, const size_t* ns,
+                          const uint32_t* key_idx, const uint8_t* a0, const uint8_t* a1, int poison, uint8_t* sums_out, uint8_t* point_out) {
+    if (scheme < 0 || scheme > 2 || n_keys == 0 || !ns || !sums_out || !point_out) return -1;
+    size_t n_max = 0;
+    for (size_t i = 0; i < n_cases; ++i) n_max = ns[i] > n_max ? ns[i] : n_max;
+    host_set set(scheme, keys0, keys1, n_keys, n_max, poison);
+    size_t first = 0;
+    for (size_t ci = 0; ci < n_cases; first += ns[ci], ++ci) {
+        const size_t n = ns[ci];
+        if (n == 0) return -1;
+        for (uint64_t i = 0; i < n; ++i) {
+            if (key_idx[first + i] >= n_keys) return -1;
+            set.keyid[i] = key_idx[first + i];
+        }
+        std::vector<uint32_t> cursor, order;
+        sort_by_key(set.keyid, n_keys, n, cursor, order);
+        const ksv_runs Rn{cursor.data(), 1u, order.data(), set.keyid.data(), n_keys, n};
+        const uint32_t cells = ksv_cells(n);
+        const uint8_t* a[2] = {a0 + 32 * first, a1 ? a1 + 32 * first : nullptr};
+        uint8_t* sums = sums_out + ci * set.cols * n_keys * 32;
+        ext_pt total = ext_identity();
+        for (uint32_t col = 0; col < set.cols; ++col) {
+            std::vector<uint8_t> head((size_t)n_keys * 32 + 16), cell((size_t)cells * 32 + 16);
+            uint8_t *h = align16(head), *cl = align16(cell);
+            for (uint32_t k = 0; k < n_keys; ++k) store_words(h, k, ksv_head(Rn, a[col], k));
+            for (uint32_t g = 0; g < cells; ++g) store_words(cl, g, ksv_cell(Rn, a[col], g));
+            for (uint32_t k = 0; k < n_keys; ++k) {
+                total = msm_add_ext(total, ksv_key_point(Rn, set.col[col], h, cl, k));
+                store_words(sums, (uint64_t)col * n_keys + k, ksv_key_sum(Rn, h, cl, k));
+            }
+        }
+        to_affine_bytes(total, point_out + 64 * ci);
+    }
+    return 0;
+}
 
 // scheme 0 / 1 / 2; keys0, keys1: n_keys x 64 affine (keys1 NULL for single); affine signature columns; seed: 32 bytes;
 // c: the window width of the bucket method (0: by size); poison: the tables of the keys that are not valid are filled with
@@ -19,31 +106,13 @@ int jjs_ksv_host_verify_all(int scheme, const uint8_t* keys0, const uint8_t* key
     if (scheme < 0 || scheme > 2 || n_keys == 0 || n == 0 || !verdict) return -1;
     ensure_tables();
     const int w = KEYSET_WINDOW;
-    const uint32_t cols = scheme == 0 ? 1u : 2u;
-    const uint8_t* keys[2] = {keys0, keys1};
-    std::vector<uint32_t> key_item(n_keys), tables[2], bases[2], keyid(n + 1);
-    std::vector<uint8_t> flags[2], gathered[2], bad(n + 1, 0);
-    for (uint32_t k = 0; k < n_keys; ++k) key_item[k] = k;
-    key_column col[2] = {};
-    const size_t key_table_words = (size_t)kt_positions(w) * kt_table_words(w);
-    for (uint32_t ci = 0; ci < cols; ++ci) {
-        key_column& C = col[ci];
-        flags[ci].assign(n_keys, 0);
-        bases[ci].assign((size_t)n_keys * kt_positions(w) * KT_BASE_WORDS + 4, 0);
-        tables[ci].assign((size_t)n_keys * key_table_words + 8, 0);
-        gathered[ci].assign(64 * n + 64, 0);
-        C.src = fe_src{keys[ci], 64, 0};
-        C.key_item = key_item.data(); C.key_flags = flags[ci].data(); C.bases = bases[ci].data();
-        C.tables = align16(tables[ci]);
-        C.keyid = keyid.data();
-        for (uint32_t k = 0; k < n_keys; ++k) {
-            if (kt_chain_key(C, k, w)) {                      // tables for the valid keys only, as on the device
-                for (uint32_t pos = 0; pos < (uint32_t)kt_positions(w); ++pos) kt_table_lane(C, k, pos, w);
-            } else if (poison) {
-                memset(C.tables + (size_t)k * key_table_words, 0xFF, key_table_words * 4);
-            }
-        }
-    }
+    host_set set(scheme, keys0, keys1, n_keys, n, poison);
+    const uint32_t cols = set.cols;
+    std::vector<uint32_t>& keyid = set.keyid;
+    std::vector<uint8_t>* flags = set.flags;
+    key_column* col = set.col;
+    std::vector<uint8_t> gathered[2], bad(n + 1, 0);
+    for (uint32_t ci = 0; ci < cols; ++ci) gathered[ci].assign(64 * n + 64, 0);
     if (key_status)
         for (uint32_t k = 0; k < n_keys; ++k) key_status[k] = (uint8_t)ks_key_status(flags[0][k], cols > 1 ? flags[1][k] : (uint32_t)KT_KEY_VALID);
     uint8_t* g0 = align16(gathered[0]);
@@ -81,12 +150,8 @@ int jjs_ksv_host_verify_all(int scheme, const uint8_t* keys0, const uint8_t* key
         sum[0] = fr_add(sum[0], zu[0]);
         sum[1] = fr_add(sum[1], zu[1]);
     }
-    // the counting sort by key: counts, exclusive scan, scatter (the cursors end at the ends of the runs)
-    std::vector<uint32_t> cursor(n_keys, 0), order(n);
-    for (uint64_t i = 0; i < n; ++i) ++cursor[keyid[i]];
-    uint32_t run = 0;
-    for (uint32_t k = 0; k < n_keys; ++k) { const uint32_t cnt = cursor[k]; cursor[k] = run; run += cnt; }
-    for (uint64_t i = 0; i < n; ++i) order[cursor[keyid[i]]++] = (uint32_t)i;
+    std::vector<uint32_t> cursor, order;
+    sort_by_key(keyid, n_keys, n, cursor, order);
     const ksv_runs Rn{cursor.data(), 1u, order.data(), keyid.data(), n_keys, n};
     ext_pt total = host_msm(B.terms, B.scalars, N, msm_shape_short(c), [](uint64_t) { return true; });     // every term is a -R
     for (uint32_t ci = 0; ci < cols; ++ci) {

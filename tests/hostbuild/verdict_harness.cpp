@@ -1,4 +1,5 @@
-// CPU build of csrc/batch_verdict.h and csrc/msm.h (the batch verdict of jjs_verify_all_*) for tests/test_verify_all_host.py:
+// CPU build of csrc/batch_verdict.h and csrc/msm.h (the batch verdict of jjs_verify_all_*) for tests/test_verify_all_host.py and
+// tests/test_msm_host.py:
 // the device's steps run here in loops -- the per-item pass (bv_item), then the bucket method (host_msm.h) -- with the same
 // functions.  The comb tables and the double scheme's tag come from host_harness.cpp.
 #include "host_harness.cpp"
@@ -16,16 +17,25 @@ int jjs_vh_chacha20_block(const uint8_t key[32], uint32_t counter, const uint8_t
     return 0;
 }
 
-// points: N x 64 affine (u || v, canonical little-endian); scalars: N x 32 (< 2^252); neg: N flags; c: window width (0: by N).
-// out: the affine sum (64 bytes)
-int jjs_vh_msm(const uint8_t* points, const uint8_t* scalars, const uint8_t* neg, size_t N, int c, uint8_t* out) {
-    if (c == 0) c = msm_pick_window(N);
+// points: N x 64 affine (u || v, canonical little-endian); scalars: N x 32 (< 2^252; short_shape != 0: within
+// msm_weight_bits(c) bits, the windows of msm_shape_short); neg: N flags; c: window width (0: by N).
+// out: the affine sum (64 bytes).  Nullable: off_out (W * B + 1 words), order_out (room for N * W words; off[W * B] are
+// written), win_out (W affine window sums of 64 bytes)
+int jjs_vh_msm(const uint8_t* points, const uint8_t* scalars, const uint8_t* neg, size_t N, int c, int short_shape, uint8_t* out,
+               uint32_t* off_out, uint32_t* order_out, uint8_t* win_out) {
+    if (c == 0) c = short_shape ? msm_pick_short_window(N) : msm_pick_window(N);
     if (c < 2 || c > MSM_MAX_WINDOW) return -1;
     std::vector<uint32_t> terms(N * MSM_TERM_WORDS + 4);
     uint32_t* t = align16(terms);
     const fe_src src{points, 64, 0};
     for (size_t i = 0; i < N; ++i) msm_store_term(t + i * MSM_TERM_WORDS, load_fq(src, i), load_fq(src, i, 32));
-    to_affine_bytes(host_msm(t, scalars, N, msm_shape_full(c), [&](uint64_t i) { return neg[i] != 0; }), out);
+    const msm_shape S = short_shape ? msm_shape_short(c) : msm_shape_full(c);
+    host_msm_stages st;
+    to_affine_bytes(host_msm(t, scalars, N, S, [&](uint64_t i) { return neg[i] != 0; }, &st), out);
+    if (off_out) memcpy(off_out, st.off.data(), st.off.size() * 4);
+    if (order_out) memcpy(order_out, st.order.data(), st.order.size() * 4);
+    if (win_out)
+        for (int j = 0; j < S.W; ++j) to_affine_bytes(msm_load_ext(&st.win[(size_t)j * MSM_EXT_WORDS]), win_out + 64 * j);
     return 0;
 }
 

@@ -22,7 +22,7 @@ def build_hostlib(src, lib):
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         # JJS_HOST_SANITIZE=1 python -m pytest tests/test_hostbuild.py  -> the same tests under UBSan
         san = ["-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=undefined"] if os.environ.get("JJS_HOST_SANITIZE") else ["-O2"]
-        subprocess.check_call(["g++", *san, "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas",
+        subprocess.check_call(["g++", *san, "-std=c++17", "-pthread", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas",
                                "-I" + CSRC, "-o", lib, src])
     return ctypes.CDLL(lib)
 

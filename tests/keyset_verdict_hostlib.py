@@ -39,3 +39,21 @@ def verify_all(scheme, keys, idx, b, seed=bytes(32), c=0, poison=False):
                                         ctypes.byref(verdict), _p(total), _p(sums), _p(key_status), ctypes.byref(z_bits))
     assert rc == 0
     return {"verdict": verdict.value, "total": total, "key_sums": sums, "key_status": key_status, "z_bits": z_bits.value}
+
+
+def key_sums(scheme, keys, idxs, cols, poison=True):
+    """The run sums and key points alone, for several cases against one set: idxs[i] the key indices of case i, cols[i] its
+    scalar columns (list of (n_i, 32), below r).  Returns (sums (cases, point columns, n_keys, 32), the affine sums of
+    S_k * P_k (cases, 64))."""
+    keys = [np.ascontiguousarray(k, dtype=np.uint8) for k in keys]
+    ns = np.array([len(i) for i in idxs], np.uint64)
+    idx = np.ascontiguousarray(np.concatenate(idxs), dtype=np.uint32)
+    a = [np.ascontiguousarray(np.concatenate([c[ci] for c in cols]), dtype=np.uint8) for ci in range(len(keys))]
+    assert all(x.shape == (len(idx), 32) for x in a)
+    nk = len(keys[0])
+    sums, point = np.zeros((len(ns), len(keys), nk, 32), np.uint8), np.zeros((len(ns), 64), np.uint8)
+    rc = load().jjs_ksv_host_key_sums(SCHEMES[scheme], _p(keys[0]), _p(keys[1]) if len(keys) > 1 else None, ctypes.c_uint32(nk),
+                                      ctypes.c_size_t(len(ns)), _p(ns), _p(idx), _p(a[0]), _p(a[1]) if len(a) > 1 else None, int(poison),
+                                      _p(sums), _p(point))
+    assert rc == 0
+    return sums, point

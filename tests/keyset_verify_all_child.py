@@ -4,7 +4,8 @@ jjs_keyset_verify_all* (jjs_debug_force_path 0x2000) and checks it -- valid batc
 index and an invalid registered key (verdict 0, statuses byte for byte those of KeySet.verify and the oracle); cancelling
 equations, cancelling torsion and an exact cofactorless equation with torsion, their keys registered; two bad items under
 ONE key whose defects cancel (with random 128-bit weights this check fails spuriously with probability 2^-128); a pinned
-seed (two calls agree, _dev agrees with the host call); the set's call counters, which the verdict algorithm does not
+seed (two calls agree, _dev agrees with the host call); every window width from 8 to 16 forced (w << 16) on a valid batch of
+300 items and on one bad item at three positions; the set's call counters, which the verdict algorithm does not
 move and the forced per-item route (0x4000) moves as KeySet.verify does.  Prints "ok" and exits 0 when every check holds."""
 import os
 import sys
@@ -111,6 +112,25 @@ def main() -> None:
                 v2, _ = ks.verify_all(idx, *sigs, statuses_on_failure=False)
                 assert v1 == v2 == bool(dev_verdict(ks, idx, sigs)) == bool((oracle_verify(scheme, b) == 0).all())
             assert counts(ks) == (0, 0)
+    assert lib.jjs_debug_pin_hash_seed(0) == 0
+
+    # every window width of the MSM forced through the real calls (by size only 8, 12, 13, 15 and 16 run above), the weights
+    # pinned: a valid batch, and the same batch with one bad u at the first, middle and last item
+    assert lib.jjs_debug_pin_hash_seed(2) == 0
+    for scheme in ("single", "double", "vargen"):
+        good = make_batch(scheme, 300, seed=43, n_keys=40, mix=False)
+        bad = [b for name, b in spoil_cases(scheme, good) if name.startswith("bad_u@")]
+        assert len(bad) == 3 and (oracle_verify(scheme, good) == 0).all() and all((oracle_verify(scheme, b) != 0).sum() == 1 for b in bad)
+        keys, idx = register_cols(scheme, good)
+        with eng.keyset(scheme, *keys) as ks:
+            for w in range(8, 17):
+                assert lib.jjs_debug_force_path(0x2000 | (w << 16)) == 0
+                for b, want in [(good, 1)] + [(b, 0) for b in bad]:
+                    sigs = sig_cols(eng, scheme, b, "affine")
+                    v, _ = ks.verify_all(idx, *sigs, statuses_on_failure=False)
+                    assert int(v) == want == dev_verdict(ks, idx, sigs), (scheme, w, want)
+            assert counts(ks) == (0, 0)
+    assert lib.jjs_debug_force_path(0x2000) == 0
     assert lib.jjs_debug_pin_hash_seed(0) == 0
 
     # the per-item route forced: the counters move exactly as under KeySet.verify

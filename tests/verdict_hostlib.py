@@ -31,14 +31,21 @@ def chacha20_block(key: bytes, counter: int, nonce: bytes) -> bytes:
     return out.raw
 
 
-def msm(points, scalars, neg=None, c=0):
-    """points: (N, 64) affine; scalars: (N, 32) below 2^252; neg: N flags (the term is -P).  Returns the affine sum (64 bytes)."""
+def msm(points, scalars, neg=None, c=0, short=False, stages=False):
+    """points: (N, 64) affine; scalars: (N, 32) below 2^252 (short: within the weights' bits); neg: N flags (the term is -P).
+    Returns the affine sum (64 bytes); with stages a dict: total, off (W * B + 1), order (off[-1] entries), win (W, 64)."""
     points = np.ascontiguousarray(points, np.uint8)
     scalars = np.ascontiguousarray(scalars, np.uint8)
     neg = np.ascontiguousarray(np.zeros(len(points), np.uint8) if neg is None else neg, np.uint8)
     out = np.zeros(64, np.uint8)
-    assert load().jjs_vh_msm(_p(points), _p(scalars), _p(neg), ctypes.c_size_t(len(points)), c, _p(out)) == 0
-    return out
+    off = order = win = None
+    if stages:
+        assert c
+        W = (129 if short else 253) // c + ((129 if short else 253) % c != 0)
+        off, order, win = np.zeros((W << (c - 1)) + 1, np.uint32), np.zeros(len(points) * W, np.uint32), np.zeros((W, 64), np.uint8)
+    assert load().jjs_vh_msm(_p(points), _p(scalars), _p(neg), ctypes.c_size_t(len(points)), c, int(short), _p(out), _p(off), _p(order),
+                             _p(win)) == 0
+    return {"total": out, "off": off, "order": order[:off[-1]], "win": win} if stages else out
 
 
 def verify_all(scheme, b, seed=bytes(32), c=0):

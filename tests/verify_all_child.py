@@ -2,7 +2,8 @@
 at every size (jjs_debug_force_path 0x2000) and checks it -- valid batches of every scheme up to 2^17 items and one
 2^20-item single batch with unique keys; one spoilt item per failure class at the first, middle and last position
 (verdict 0, statuses byte for byte those of the inline call and the oracle); cancelling equations and cancelling
-torsion; an exact cofactorless equation with torsion; a pinned seed (two calls agree, _dev agrees with the host call).
+torsion; an exact cofactorless equation with torsion; a pinned seed (two calls agree, _dev agrees with the host call);
+every window width from 8 to 16 forced (w << 16) on a valid batch of 300 items and on one bad item at three positions.
 Prints "ok" and exits 0 when every check holds."""
 import os
 import sys
@@ -72,6 +73,22 @@ def main() -> None:
             v1, _ = eng.verify_all(scheme, *cols, statuses_on_failure=False)
             v2, _ = eng.verify_all(scheme, *cols, statuses_on_failure=False)
             assert v1 == v2 == int(dev_verdict(scheme, [dev(c) for c in cols])) == bool((oracle_verify(scheme, b) == 0).all())
+    assert lib.jjs_debug_pin_hash_seed(0) == 0
+
+    # every window width of the MSM forced through the real calls (by size only 8, 11 and 16 run above), the weights pinned:
+    # a valid batch, and the same batch with one bad u at the first, middle and last item
+    assert lib.jjs_debug_pin_hash_seed(2) == 0
+    for scheme in ("single", "double", "vargen"):
+        good = make_batch(scheme, 300, seed=43, n_keys=300, mix=False)
+        bad = [b for name, b in spoil_cases(scheme, good) if name.startswith("bad_u@")]
+        assert len(bad) == 3 and (oracle_verify(scheme, good) == 0).all() and all((oracle_verify(scheme, b) != 0).sum() == 1 for b in bad)
+        for w in range(8, 17):
+            assert lib.jjs_debug_force_path(0x2000 | (w << 16)) == 0
+            for b, want in [(good, 1)] + [(b, 0) for b in bad]:
+                cols = [b[k] for k in ARG_ORDER[scheme]]
+                v, _ = eng.verify_all(scheme, *cols, statuses_on_failure=False)
+                assert int(v) == want == dev_verdict(scheme, [dev(c) for c in cols]), (scheme, w, want)
+    assert lib.jjs_debug_force_path(0x2000) == 0
     assert lib.jjs_debug_pin_hash_seed(0) == 0
     print("ok")
 
