@@ -468,6 +468,74 @@ int jjs_multisig_combine_keyset(jjs_keyset ks, int format, const uint32_t* key_i
                                 const uint8_t* S, const uint8_t* m, const uint32_t* offsets, size_t n_transcripts,
                                 uint8_t* share_status, uint8_t* transcript_status, uint8_t* agg_pk, uint8_t* sig_u, uint8_t* sig_R);
 
+/* ---- verifying aggregate multisignatures: aggregate_pk, and aggregate_pk followed by PublicKey::verify ------------
+ * The verifier's half of the scheme (reference src/multisig.rs:90-92: pk = aggregate_pk(&pk_vec); pk.verify(&sig, message)).
+ * A verifier receives (key vector, message, aggregate signature) and never sees a share, so the combine calls do not serve
+ * it.  Two operations, aggregation alone and aggregation followed by the single-scheme verification, each with the keys
+ * inline or named by index into a JJS_SCHEME_SINGLE key set, each as a _dev call (device pointers, asynchronous on `stream`)
+ * and as a blocking host-buffer call.  Layouts are those of the multisig calls: offsets is a HOST array of B + 1 non-decreasing
+ * uint32 starting at 0 (vector t owns rows [offsets[t], offsets[t+1])); PK is N x 64 affine or N x 96 extended; key_idx is
+ * N x uint32; u is B x 32, R is B x 64 or B x 96, m is B x 32; agg_pk is B x 64 affine and a required output of every call;
+ * vec_status and status are B bytes, tally is 4 x uint64 (status, tally and vec_status may each be NULL).
+ * `format` is JJS_FORMAT_AFFINE or JJS_FORMAT_EXT (JJS_FORMAT_WIRE: -1); for the inline calls it describes PK and R, for the
+ * key-set calls R alone.
+ * Unusable key vectors.  A vector is UNUSABLE when
+ *   inline affine:   a coordinate of one of its keys is >= q, or a key is not on the curve;
+ *   inline extended: a key is unusable by the rule of jjs_multisig_combine_ext_dev (U, V or Z >= q, or Z = 0), or its
+ *                    normalised point is not on the curve;
+ *   key set:         key_idx[i] >= n_keys or key_status[key_idx[i]] != 0 (as in jjs_multisig_combine_keyset, no lane
+ *                    addresses the set before the row has been replaced by its stand-in).
+ *   The on-curve test is particular to these calls: a few products per key, unreachable through the Rust types (which cannot
+ *   hold an off-curve point), and what makes a verifier's call total on bytes it did not produce.  Apart from it keys are not
+ *   validated, as in the reference: the identity, small-order points and repeated keys aggregate, and for such vectors agg_pk
+ *   is what jjs_multisig_combine_dev writes for the same PK and offsets.
+ * Aggregation.  agg_pk[t] = aggregate_pk(pk_vec_t), byte for byte the agg_pk row of jjs_multisig_combine_dev for every
+ *   usable, non-empty vector; vec_status[t] = 0.  An unusable vector gets vec_status 3 and agg_pk[t] all zero; the other
+ *   vectors are not affected.  An EMPTY vector is usable: aggregate_pk(&[]) is the identity (src/multisig.rs:416-429), so
+ *   agg_pk[t] is the affine bytes of (0, 1) and vec_status 0 -- on purpose unlike combine, which rejects an empty transcript
+ *   with status 5: aggregate_pk has no error.
+ * Verification.  agg_pk as above.  status[t] is exactly what jjs_verify_single returns for (u[t], R[t], PK = agg_pk[t], m[t]),
+ *   with its statuses and their precedence: an aggregate that is the identity or has a torsion part gives 1, and so does an
+ *   empty vector.  An unusable vector gives status 3 and agg_pk[t] all zero, whatever the signature holds.  tally counts the
+ *   statuses as jjs_verify_single_dev does.
+ * Extended format.  The outputs are, byte for byte, those of the affine call on derived columns in which every usable point
+ *   is its canonical (U/Z, V/Z) and every unusable point is 64 bytes of 0xFF.  An unusable R therefore gives 3, not 1: this
+ *   is the multisignature family's rule ("multisignature from extended coordinates" above), NOT that of jjs_verify_single_ext,
+ *   where Z = 0 is InvalidPoint.
+ * n_transcripts == 0 returns 0, zeroes tally if given and writes nothing else.  -4 before jjs_init; -1 for a bad format, a
+ * NULL or misaligned pointer, offsets that do not start at 0 or decrease, an unknown or destroyed handle, a set of another
+ * scheme.  _dev pointers are 16-byte aligned (key_idx 4-byte, tally 8-byte, vec_status none); the host forms ask for no
+ * alignment, upload whole columns into the multisig staging area and run one such call at a time per device, as
+ * jjs_multisig_combine does.  Scratch is the grow-only multisignature scratch; no call allocates per call.
+ * Per vector of n keys the call runs n hashes of 2 + 2n inputs, n multiplications (key set: walks of the stored tables), one
+ * inversion, and for a verification one five-input hash and one equation: the first two of the combine call's seven passes.
+ * Rates (profiles/r12_msig_verify.jsonl, the record of tools/msig_verify_rate.py: one MI355X, resident inputs, 7 rounds, medians;
+ * DESIGN.md 6.6) against the only earlier route, jjs_multisig_combine_dev with dummy shares followed by jjs_verify_single_dev:
+ * faster at all 18 recorded shapes by more than the spread of either side -- vectors of 8 keys 2.3-2.8x inline and 3.1-4.7x by
+ * key set (B = 1, 64, 4 096: 2.1 / 2.1 / 2.9 ms inline, 1.3 / 1.4 / 2.1 ms key set), 64 keys 2.7-2.9x and 3.1-3.5x at B <= 64,
+ * 1.57x and 1.75x at B = 4 096 (30.2 and 27.2 ms), 256 keys 3.1x at B = 1 (19.6 ms), 2.1-2.2x at B = 64, 1.16x and 1.21x at
+ * B = 4 096 (411 and 396 ms for 2^20 key rows: the n hashes of 2 + 2n inputs are then nearly all of either route).  Against
+ * jjs_oracle_c on 16 host threads (jjo_multisig_combine, which has no aggregate-only entry, and jjo_verify_single; timed on the
+ * distinct vectors and scaled to B): 4x at one vector of 8 keys, 110x at one vector of 256, about 800-1 700x at B = 4 096. */
+int jjs_multisig_aggregate_pk_dev(int format, const void* PK, const uint32_t* offsets_host, size_t n_transcripts,
+                                  void* agg_pk, void* vec_status, void* stream);
+int jjs_multisig_aggregate_pk(int format, const uint8_t* PK, const uint32_t* offsets, size_t n_transcripts,
+                              uint8_t* agg_pk, uint8_t* vec_status);
+int jjs_multisig_aggregate_pk_keyset_dev(jjs_keyset ks, const void* key_idx, const uint32_t* offsets_host,
+                                         size_t n_transcripts, void* agg_pk, void* vec_status, void* stream);
+int jjs_multisig_aggregate_pk_keyset(jjs_keyset ks, const uint32_t* key_idx, const uint32_t* offsets,
+                                     size_t n_transcripts, uint8_t* agg_pk, uint8_t* vec_status);
+int jjs_multisig_verify_dev(int format, const void* PK, const uint32_t* offsets_host, const void* u, const void* R,
+                            const void* m, size_t n_transcripts, void* agg_pk, void* status, void* tally, void* stream);
+int jjs_multisig_verify(int format, const uint8_t* PK, const uint32_t* offsets, const uint8_t* u, const uint8_t* R,
+                        const uint8_t* m, size_t n_transcripts, uint8_t* agg_pk, uint8_t* status, uint64_t tally[4]);
+int jjs_multisig_verify_keyset_dev(jjs_keyset ks, int format, const void* key_idx, const uint32_t* offsets_host,
+                                   const void* u, const void* R, const void* m, size_t n_transcripts,
+                                   void* agg_pk, void* status, void* tally, void* stream);
+int jjs_multisig_verify_keyset(jjs_keyset ks, int format, const uint32_t* key_idx, const uint32_t* offsets,
+                               const uint8_t* u, const uint8_t* R, const uint8_t* m, size_t n_transcripts,
+                               uint8_t* agg_pk, uint8_t* status, uint64_t tally[4]);
+
 /* ---- transcript parity (debug export): c_out = n x 32 bytes, the 250-bit challenge per item ---- */
 int jjs_challenge_single_dev(const void* R, const void* PK, const void* m, size_t n, void* c_out, void* stream);
 int jjs_challenge_double_dev(const void* R, const void* R_prime, const void* PK, const void* PK_prime, const void* m,

@@ -384,6 +384,37 @@ class KeySet {
     inline multisig::CombineResult multisig_combine(const std::vector<uint32_t>& key_idx, const std::vector<JubJubScalar>& z_vec,
                                                     const std::vector<ExtendedPoint>& R_vec, const std::vector<ExtendedPoint>& S_vec,
                                                     const BlsScalar& msg) const;
+    // raw forms of the verifier's multisignature calls against the set (jjs_multisig_aggregate_pk_keyset,
+    // jjs_multisig_verify_keyset): host buffers, blocking; key_idx (N x uint32) names the keys of every vector, vector t owning
+    // rows [offsets[t], offsets[t+1]); format (of R) JJS_FORMAT_AFFINE or JJS_FORMAT_EXT; vec_status, status and tally may be null
+    void multisig_aggregate_pk(const uint32_t* key_idx, const uint32_t* offsets, size_t n_vectors, uint8_t* agg_pk, uint8_t* vec_status) const {
+        int rc = jjs_multisig_aggregate_pk_keyset(handle_, key_idx, offsets, n_vectors, agg_pk, vec_status);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_aggregate_pk_keyset");
+    }
+    void multisig_verify(int format, const uint32_t* key_idx, const uint32_t* offsets, const uint8_t* u, const uint8_t* R, const uint8_t* m,
+                         size_t n_vectors, uint8_t* agg_pk, uint8_t* status, uint64_t tally[4] = nullptr) const {
+        int rc = jjs_multisig_verify_keyset(handle_, format, key_idx, offsets, u, R, m, n_vectors, agg_pk, status, tally);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_verify_keyset");
+    }
+    // `aggregate_pk` of ONE vector of this set's keys (scheme single), named by index in the committee's order: the aggregate key,
+    // or nothing for a vector that names an index outside the set or a key whose key_status is not 0
+    std::optional<AffinePoint> multisig_aggregate_pk(const std::vector<uint32_t>& key_idx) const {
+        const uint32_t offsets[2] = {0, (uint32_t)key_idx.size()};
+        AffinePoint agg{};
+        uint8_t vst = 0;
+        multisig_aggregate_pk(key_idx.data(), offsets, 1, agg.data(), &vst);
+        return vst ? std::nullopt : std::optional<AffinePoint>(agg);
+    }
+    // `aggregate_pk(&pk_vec).verify(&sig, msg)` for ONE such vector: what PublicKey::verify answers for the aggregate key; a
+    // refused vector is BytesError.  agg (nullable) receives the aggregate key (zero for a refused vector).
+    VerifyResult multisig_verify(const std::vector<uint32_t>& key_idx, const Signature& sig, const BlsScalar& msg, AffinePoint* agg = nullptr) const {
+        const uint32_t offsets[2] = {0, (uint32_t)key_idx.size()};
+        AffinePoint a{};
+        uint8_t st = 0;
+        multisig_verify(JJS_FORMAT_AFFINE, key_idx.data(), offsets, sig.u.data(), sig.R.data(), msg.data(), 1, a.data(), &st);
+        if (agg) *agg = a;
+        return from_status(st);
+    }
     // (key index, signature, message): the signature type of the set's scheme
     template <typename Sig>
     struct Item { uint32_t index; Sig sig; BlsScalar message; };
@@ -460,6 +491,67 @@ inline CombineResult combine(const std::vector<JubJubScalar>& z_vec, const std::
         if (status[i])
             return CombineResult{std::nullopt, CombineError{status[i] == JJS_STATUS_INVALID_SHARE ? CombineError::InvalidMultisigShare : CombineError::BytesError, i}};
     return CombineResult{Signature{u, R}, std::nullopt};
+}
+
+
+// The verifier's half (reference src/multisig.rs:90-92: pk = aggregate_pk(&pk_vec); pk.verify(&sig, message)), from the types
+// the Rust side holds, through the blocking host forms jjs_multisig_aggregate_pk / jjs_multisig_verify.  Keys pass through as
+// get_u / get_v / get_z bytes; a vector with a key the Rust types cannot hold (a coordinate >= q, Z = 0) or that is not on the
+// curve is refused.
+// `aggregate_pk`: the aggregate key (the identity for an empty vector), or nothing for a refused vector.
+inline std::optional<AffinePoint> aggregate_pk(const std::vector<ExtendedPoint>& pk_vec) {
+    if (pk_vec.size() > 0xFFFFFFFFull) throw std::invalid_argument("a key vector is indexed with 32 bits");
+    const uint32_t offsets[2] = {0, (uint32_t)pk_vec.size()};
+    AffinePoint agg{};
+    uint8_t vst = 0;
+    const int rc = jjs_multisig_aggregate_pk(JJS_FORMAT_EXT, pk_vec.empty() ? nullptr : pk_vec[0].data(), offsets, 1, agg.data(), &vst);
+    if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_aggregate_pk");
+    return vst ? std::nullopt : std::optional<AffinePoint>(agg);
+}
+// (key vector, aggregate signature, message)
+struct VerifyItem {
+    std::vector<ExtendedPoint> pk_vec;
+    Signature sig;
+    BlsScalar message;
+};
+// The batch form: one result per item, as PublicKey::verify_batch gives them for the aggregate keys; BytesError for a refused
+// vector.  agg (nullable) receives the aggregate keys (zero for a refused vector), tally (nullable) the four status counts.
+inline std::vector<VerifyResult> verify_batch(const std::vector<VerifyItem>& items, std::vector<AffinePoint>* agg = nullptr, uint64_t tally[4] = nullptr) {
+    const size_t B = items.size();
+    std::vector<uint32_t> offsets(B + 1, 0);
+    size_t n = 0;
+    for (size_t t = 0; t < B; ++t) {
+        n += items[t].pk_vec.size();
+        if (n > 0xFFFFFFFFull) throw std::invalid_argument("the key rows of a call are indexed with 32 bits");
+        offsets[t + 1] = (uint32_t)n;
+    }
+    std::vector<ExtendedPoint> pk(n), R(B);
+    std::vector<Scalar> u(B), m(B);
+    std::vector<AffinePoint> a(B);
+    std::vector<uint8_t> status(B);
+    for (size_t t = 0, at = 0; t < B; ++t) {
+        for (const ExtendedPoint& p : items[t].pk_vec) pk[at++] = p;
+        u[t] = items[t].sig.u; m[t] = items[t].message;
+        R[t].fill(0);                                            // the affine R as (u, v, 1)
+        std::memcpy(R[t].data(), items[t].sig.R.data(), 64);
+        R[t][64] = 1;
+    }
+    if (B) {
+        const int rc = jjs_multisig_verify(JJS_FORMAT_EXT, n ? pk[0].data() : nullptr, offsets.data(), u[0].data(), R[0].data(), m[0].data(), B,
+                                           a[0].data(), status.data(), tally);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_verify");
+    } else if (tally) {
+        for (int k = 0; k < 4; ++k) tally[k] = 0;
+    }
+    if (agg) *agg = a;
+    return detail::results(status);
+}
+// `aggregate_pk(&pk_vec).verify(&sig, msg)` of ONE vector: Ok, or the scheme's error as PublicKey::verify answers it
+inline VerifyResult verify(const std::vector<ExtendedPoint>& pk_vec, const Signature& sig, const BlsScalar& msg, AffinePoint* agg = nullptr) {
+    std::vector<AffinePoint> a;
+    const VerifyResult r = verify_batch({VerifyItem{pk_vec, sig, msg}}, &a)[0];
+    if (agg) *agg = a[0];
+    return r;
 }
 
 }  // namespace multisig

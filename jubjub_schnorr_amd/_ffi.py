@@ -85,6 +85,14 @@ SIGNATURES = {
     "jjs_msig_group_combine": [ctypes.c_uint64, _I, _P, _P, _P, _P, _Z, _P, _P, _P, _P],
     "jjs_multisig_combine_keyset_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P, _P],
     "jjs_multisig_combine_keyset": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P],
+    "jjs_multisig_aggregate_pk_dev": [_I, _P, _P, _Z, _P, _P, _P],
+    "jjs_multisig_aggregate_pk": [_I, _P, _P, _Z, _P, _P],
+    "jjs_multisig_aggregate_pk_keyset_dev": [ctypes.c_uint64, _P, _P, _Z, _P, _P, _P],
+    "jjs_multisig_aggregate_pk_keyset": [ctypes.c_uint64, _P, _P, _Z, _P, _P],
+    "jjs_multisig_verify_dev": [_I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P],
+    "jjs_multisig_verify": [_I, _P, _P, _P, _P, _P, _Z, _P, _P, _P],
+    "jjs_multisig_verify_keyset_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P],
+    "jjs_multisig_verify_keyset": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P],
     "jjs_verify_all_single": [_P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_double": [_P, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_vargen": [_P, _P, _P, _P, _P, _Z, _P, _P],

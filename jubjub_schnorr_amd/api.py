@@ -284,6 +284,77 @@ class Engine:
                                             o(sr), self._stream()), name)
         return status, agg, su, sr, tstatus
 
+    def _msig_verifier(self, handle, keys, offsets, sig, fmt, want_status):
+        """The four verifier's calls (include/jjs_gpu.h "verifying aggregate multisignatures"): handle None for inline keys
+        (`keys` a PK column in `fmt`), a key-set handle for indices; sig None for aggregation alone, else (u, R, m)."""
+        w = self._msig_width(fmt)
+        fmt_id = self._FORMAT_IDS[fmt]
+        offs = np.ascontiguousarray(offsets, dtype=np.uint32)
+        B, N = len(offs) - 1, keys.shape[0]
+        if B and int(offs[-1]) != N:
+            raise ValueError("the key column does not have the rows the offsets ask for")
+        name = "jjs_multisig_" + ("verify" if sig is not None else "aggregate_pk") + ("_keyset" if handle is not None else "")
+        head = [] if handle is None else [handle]
+        if handle is None or sig is not None:
+            head.append(fmt_id)
+        po = offs.ctypes.data_as(ctypes.c_void_p)
+        if not _is_torch(keys):
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+            if handle is None:
+                hk = self._host(keys, w)
+            else:
+                hk = np.asarray(keys)
+                if hk.dtype.kind not in "iu" or hk.ndim != 1:
+                    raise ValueError("key indices must be a 1-d array of integers")
+                hk = np.ascontiguousarray(hk, dtype=np.uint32)
+            agg = np.zeros((B, 64), np.uint8)
+            if sig is None:
+                vst = np.zeros(B, np.uint8)
+                _ffi.check(getattr(self._lib, name)(*head, p(hk), po, B, p(agg), p(vst)), name)
+                return agg, vst
+            hu, hr, hm = self._host(sig[0], 32), self._host(sig[1], w), self._host(sig[2], 32)
+            if any(h.shape[0] != B for h in (hu, hr, hm)):
+                raise ValueError("u, R and m take one row per key vector")
+            status = np.zeros(B, np.uint8) if want_status else None
+            tally = np.zeros(4, np.uint64)
+            _ffi.check(getattr(self._lib, name)(*head, p(hk), po, p(hu), p(hr), p(hm), B, p(agg), p(status), p(tally)), name)
+            return status, tally, agg
+        import torch
+        name += "_dev"
+        dev_ = keys.device
+        o = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        if handle is None:
+            pk = self._dev_ptr(keys, w, N)
+        else:
+            if not (keys.is_cuda and keys.is_contiguous() and keys.dim() == 1
+                    and keys.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+                raise ValueError("expected a contiguous 1-d CUDA tensor of int32 / uint32 indices, one per key row")
+            pk = o(keys)
+        agg = torch.empty((max(B, 1), 64), dtype=torch.uint8, device=dev_)[:B]
+        if sig is None:
+            vst = torch.empty(max(B, 1), dtype=torch.uint8, device=dev_)[:B]
+            _ffi.check(getattr(self._lib, name)(*head, pk, po, B, o(agg), o(vst), self._stream()), name)
+            return agg, vst
+        status = torch.empty(max(B, 1), dtype=torch.uint8, device=dev_)[:B] if want_status else None
+        tally = torch.zeros(4, dtype=torch.int64, device=dev_)
+        _ffi.check(getattr(self._lib, name)(*head, pk, po, self._dev_ptr(sig[0], 32, B), self._dev_ptr(sig[1], w, B),
+                                            self._dev_ptr(sig[2], 32, B), B, o(agg), o(status), o(tally), self._stream()), name)
+        return status, tally, agg
+
+    def multisig_aggregate_pk(self, PK, offsets, fmt: str = "affine"):
+        """Batch `aggregate_pk` (reference src/multisig.rs:154-156) over many key vectors: PK (N, 64) -- or (N, 96) with
+        fmt="ext" -- vector t owning rows offsets[t]:offsets[t+1] (B + 1 host ints).  torch CUDA tensors run asynchronously on
+        the current stream (jjs_multisig_aggregate_pk_dev), numpy arrays block (jjs_multisig_aggregate_pk).  Returns
+        (agg_pk (B, 64), vec_status (B,)): 0, or 3 and a zero aggregate for a vector with a key that is out of range or off the
+        curve; an empty vector gives the identity."""
+        return self._msig_verifier(None, PK, offsets, None, fmt, True)
+
+    def multisig_verify(self, PK, offsets, u, R, m, fmt: str = "affine", want_status: bool = True):
+        """`aggregate_pk(pk_vec).verify(sig, m)` over many (key vector, signature, message): PK and offsets as in
+        `multisig_aggregate_pk`, u (B, 32), R (B, 64) or (B, 96) with fmt="ext", m (B, 32).  Returns (status, tally, agg_pk):
+        the statuses of `verify("single", u, R, agg_pk, m)`, 3 and a zero aggregate for an unusable key vector."""
+        return self._msig_verifier(None, PK, offsets, (u, R, m), fmt, want_status)
+
     def multisig_group(self, PK, fmt: str = "affine") -> "SignerGroup":
         """Register the ordered key vector of a committee once (jjs_msig_group_create; fmt="ext": (n, 96) extended keys,
         jjs_msig_group_create_ext): its delinearisation coefficients, its aggregate key and the window tables of its keys are
@@ -742,6 +813,19 @@ class KeySet:
                                                              d(m, 32, B), offs.ctypes.data_as(ctypes.c_void_p), B, o(status), o(tstatus),
                                                              o(agg), o(su), o(sr), Engine._stream()), "jjs_multisig_combine_keyset_dev")
         return status, agg, su, sr, tstatus
+
+    def multisig_aggregate_pk(self, key_idx, offsets):
+        """`Engine.multisig_aggregate_pk` with the keys named by index into this set (scheme "single"): key_idx (N,) uint32.  A
+        vector naming an index outside the set or a key whose `key_status` is not 0 is refused (vec_status 3, zero aggregate)."""
+        if self.handle == 0:
+            raise _ffi.JjsError("the key set is closed")
+        return self._eng._msig_verifier(self.handle, key_idx, offsets, None, "affine", True)
+
+    def multisig_verify(self, key_idx, offsets, u, R, m, fmt: str = "affine", want_status: bool = True):
+        """`Engine.multisig_verify` with the keys named by index into this set; fmt is that of R.  Returns (status, tally, agg_pk)."""
+        if self.handle == 0:
+            raise _ffi.JjsError("the key set is closed")
+        return self._eng._msig_verifier(self.handle, key_idx, offsets, (u, R, m), fmt, want_status)
 
     def info(self) -> dict:
         out = (ctypes.c_uint64 * len(self.INFO_NAMES))()

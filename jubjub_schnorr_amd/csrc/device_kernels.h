@@ -804,3 +804,19 @@ __global__ __launch_bounds__(BLOCK, 2) void msig_keyset_share_kernel(msig_keyset
     const uint64_t total = (uint64_t)gridDim.x * BLOCK;
     for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < K.M.n_total; i += total) mk_share_item(K, i);
 }
+
+// ---- the verifier's half of the multisignature scheme (msig_verify.h) -----------------------------------
+// The check pass behind pass 0 (a lane per key row), the sum pass behind pass 1 and the clear pass behind the verification (a
+// lane per vector): grid-stride, as the gather and the refusals above
+__global__ __launch_bounds__(BLOCK) void msig_verify_check_kernel(msig_verify_params V) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < V.M.n_total; i += total) mv_check_item(V, i);
+}
+__global__ __launch_bounds__(BLOCK) void msig_verify_sum_kernel(msig_verify_params V) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; t < V.M.n_transcripts; t += total) mv_sum_item(V, (uint32_t)t);
+}
+__global__ __launch_bounds__(BLOCK) void msig_verify_clear_kernel(msig_verify_params V) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; t < V.M.n_transcripts; t += total) mv_clear_item(V, (uint32_t)t);
+}

@@ -22,6 +22,7 @@
 //   host_calls.h       the large blocking host-buffer calls: upload plan, staging copies, the pipeline
 //   msig_host_calls.h  the blocking host-buffer forms of the multisignature calls
 //   msig_keyset_calls.h  the multisignature call against a registered key set, both forms
+//   msig_verify_calls.h  the verifier's half: aggregate_pk, and aggregate_pk followed by the single-scheme verification
 //   host_lanes.h       the small ones (included among the entry points, behind the table of call shapes): staging lanes
 //                      outside the engine's mutex, calls of several threads in one launch
 //   (here)             the table of call shapes and the staged_call builder it drives; the extern "C" entry points
@@ -64,6 +65,7 @@
 #include "multisig_core.h"
 #include "msig_group.h"
 #include "msig_keyset.h"
+#include "msig_verify.h"
 #include "batch_verdict.h"
 #include "keyset_verdict.h"
 #include "jjs_sponge_tags_long.inc"
@@ -948,6 +950,7 @@ int jjs_multisig_combine_ext_dev(const void* z, const void* PK_ext, const void* 
 #include "msig_group_calls.h"
 #include "msig_host_calls.h"
 #include "msig_keyset_calls.h"
+#include "msig_verify_calls.h"
 
 // ---- challenge export ---------------------------------------------------------------------------
 static int launch_challenge(challenge_params P, void* stream) {

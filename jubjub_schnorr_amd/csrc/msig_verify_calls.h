@@ -1,0 +1,227 @@
+// Part of jjs_gpu.hip (included among the extern "C" entry points, behind msig_keyset_calls.h): the verifier's half of the
+// multisignature scheme (msig_verify.h, include/jjs_gpu.h jjs_multisig_aggregate_pk*, jjs_multisig_verify*) -- the two front
+// passes of the combine call with a check (or the key set's gather) between them, the sum pass, and for a verification call the
+// resident single-scheme call on the aggregate column with the clear pass behind it.
+// Lifetime: the passes use the multisignature scratch, which belongs to slot 0; the verification stage runs in a slot of its
+// own choosing and reads the aggregate from the caller's memory, but in the extended format its R column is the normalised
+// one in that scratch.  So slot 0's event is recorded only after the verification's launches and the clear pass have been
+// queued: the scratch's next user, on whatever stream, waits for all of them.
+
+extern "C++" {
+struct mv_call {
+    bool keyset, ext, verify;             // ext: the inline form's PK and R, the key-set form's R
+    const keyset_entry* k;                // the key-set form: the set and its copy on the device
+    const keyset_copy* c;
+    const void *keys;                     // PK (N x 64 / N x 96) or key_idx (N x uint32)
+    const void *u, *R, *m;                // a verification call
+    void *agg_pk, *vec_status, *status, *tally;
+};
+// one column of `rows` extended points into normalised column `slot` of the scratch, in poison mode; col is re-aimed at it
+static int mv_normalize(const msig_scratch& W, const uint8_t*& col, int slot, size_t rows, hipStream_t s) {
+    normalize_params N{};
+    N.n_src = 1; N.poison = 1; N.scratch = W.prefix;
+    N.src[0] = fe_src{col, 96, 0};
+    N.out[0] = W.norm[slot];
+    col = W.norm[slot];
+    return launch_normalize(N, 0, rows, rows, s);
+}
+// The call on device columns, queued on s (under the engine's mutex, g the device; n_transcripts > 0).
+static int msig_verify_locked(const mv_call& A, const uint32_t* offsets_host, size_t n_transcripts, hipStream_t s) {
+    size_t n = 0;
+    if (int rc = msig_check_offsets(offsets_host, n_transcripts, n)) return rc;
+    if (n && (A.keyset ? (!A.keys || (reinterpret_cast<uintptr_t>(A.keys) & 3u)) : !all_ok(A.keys))) return fail(JJS_ERR_ARG, "null or misaligned pointer");
+    if (!all_ok(A.agg_pk)) return fail(JJS_ERR_ARG, "null or misaligned pointer");
+    if (A.verify && (!all_ok(A.u, A.R, A.m) || (A.status && !aligned16(A.status)) || (reinterpret_cast<uintptr_t>(A.tally) & 7u)))
+        return fail(JJS_ERR_ARG, "null or misaligned pointer");
+    const size_t B = n_transcripts;
+    const size_t ext_rows = !A.ext ? 0 : (A.keyset ? (A.verify ? B : 0) : (A.verify && B > n ? B : n));
+    if (int rc = A.keyset ? ensure_msig_scratch(n, B, ext_rows, n ? n : 1, B) : ensure_msig_scratch(n, B, ext_rows)) return rc;
+    const msig_scratch W = msig_scratch_carve();
+    msig_verify_keyset_params VK{};
+    msig_params& P = VK.K.M;
+    P.n_transcripts = (uint32_t)B; P.n_total = n;
+    P.agg_pk = (uint8_t*)A.agg_pk;
+    P.tr_of = W.tr_of; P.d_words = W.d_words; P.dpk = W.dpk; P.offsets = W.offsets;
+    P.tags = g->tags_long; P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
+    P.max_table_participants = JJS_MSIG_MAX_PARTICIPANTS;
+    P.long_tags = W.long_tags;
+    P.hash_lanes = 1;
+    VK.vec_status = (uint8_t*)A.vec_status; VK.poison = A.verify ? 1u : 0u;
+    if (A.keyset) {
+        msig_keyset_params& K = VK.K;
+        P.PK = W.ks_pk;
+        K.key_idx = (const uint32_t*)A.keys; K.n_keys = A.k->n_keys;
+        K.keys = A.c->keys[0]; K.flags = A.c->flags[0]; K.tables = A.c->tables[0];
+        K.pk_col = W.ks_pk; K.row_key = W.ks_row_key; K.refused = W.ks_refused;
+    } else {
+        VK.K.refused = W.a_words;          // the inline form: a verifier's call computes no `a`, its words hold the refused flags
+    }
+    const uint8_t *pk = A.keyset ? nullptr : (const uint8_t*)A.keys, *r = (const uint8_t*)A.R;
+    big_slot();
+    if (int rc = begin_shared(s)) return rc;
+    auto queue = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(W.offsets, offsets_host, (B + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(VK.K.refused, 0, B * sizeof(uint32_t), s));
+        if (A.ext && !A.keyset)
+            if (int rc = mv_normalize(W, pk, 0, n, s)) return rc;
+        if (A.ext && A.verify)
+            if (int rc = mv_normalize(W, r, A.keyset ? 0 : 1, B, s)) return rc;
+        if (!A.keyset) P.PK = pk;
+        const dim3 per_row(grid_for(g->grid_msig, n)), per_vector(grid_for(g->grid_msig, B));
+        hipLaunchKernelGGL(msig_kernel, per_vector, dim3(BLOCK), 0, s, P, 0);
+        if (n) {
+            // behind the map: both read tr_of
+            if (A.keyset) hipLaunchKernelGGL(msig_keyset_gather_kernel, per_row, dim3(BLOCK), 0, s, VK.K);
+            else hipLaunchKernelGGL(msig_verify_check_kernel, per_row, dim3(BLOCK), 0, s, mv_of(VK));
+            // the hash pass: eight lanes per row when the call has few (multisig_core.h hash_lanes)
+            P.hash_lanes = msig_hash_lanes(n);
+            const dim3 hashing(grid_for(g->grid_msig, n * P.hash_lanes));
+            if (A.keyset) hipLaunchKernelGGL(msig_keyset_delin_kernel, hashing, dim3(BLOCK), 0, s, VK.K);
+            else hipLaunchKernelGGL(msig_kernel, hashing, dim3(BLOCK), 0, s, P, 1);
+            P.hash_lanes = 1;
+        }
+        hipLaunchKernelGGL(msig_verify_sum_kernel, per_vector, dim3(BLOCK), 0, s, mv_of(VK));
+        HIP_TRY(hipGetLastError());
+        if (!A.verify) return JJS_OK;
+        // the verification stage: the resident single-scheme affine call on (u, R, agg_pk, m), in a slot of its own (build_call
+        // moves sl), on the same stream, under this hold of the mutex
+        const void* d[4] = {A.u, r, A.agg_pk, A.m};
+        staged_call C;
+        if (int rc = build_call(SHAPES[JJS_SCHEME_SINGLE][JJS_FORMAT_AFFINE], d, B, A.status, A.tally, s, C)) return rc;
+        if (int rc = launch_staged(C, s)) return rc;
+        hipLaunchKernelGGL(msig_verify_clear_kernel, per_vector, dim3(BLOCK), 0, s, mv_of(VK));
+        HIP_TRY(hipGetLastError());
+        return JJS_OK;
+    };
+    const int rc = queue();
+    sl = &g->slots[0];                          // the scratch's slot again: its event covers the verification and the clear pass,
+    const int rc2 = end_shared(s);              // and whatever was queued when a step failed
+    return rc ? rc : rc2;
+}
+
+// a _dev entry point: the checks in front of the call, under the engine's mutex
+static int msig_verify_dev(mv_call A, const jjs_keyset* ks, int format, const uint32_t* offsets_host, size_t n_transcripts, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    if (ks) {
+        keyset_entry* k = nullptr;
+        if (int rc = msig_keyset_find(*ks, g, k, A.c)) return rc;
+        A.k = k;
+    }
+    if (int rc = msig_format(format, A.ext)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (n_transcripts == 0) {
+        if (A.verify && A.tally) HIP_TRY(hipMemsetAsync(A.tally, 0, 4 * sizeof(unsigned long long), s));
+        return JJS_OK;
+    }
+    return no_throw([&] { return msig_verify_locked(A, offsets_host, n_transcripts, s); });
+}
+
+// a host-buffer entry point: blocking, as jjs_multisig_combine (msig_host_calls.h).  A's pointers are the caller's host buffers.
+static int msig_verify_host(mv_call A, const jjs_keyset* ks, int format, const uint32_t* offsets, size_t n_transcripts, uint64_t* tally) {
+    device_state* dev = nullptr;
+    size_t n = 0;
+    {
+        std::lock_guard<std::mutex> lock(L.mu);
+        if (int rc = check_ready()) return rc;
+        if (ks) {
+            keyset_entry* k = nullptr;
+            if (int rc = msig_keyset_find(*ks, g, k, A.c)) return rc;
+        }
+        if (int rc = msig_format(format, A.ext)) return rc;
+        if (n_transcripts == 0) {
+            if (A.verify && tally) for (int k = 0; k < 4; ++k) tally[k] = 0;
+            return JJS_OK;
+        }
+        if (int rc = msig_check_offsets(offsets, n_transcripts, n)) return rc;
+        if ((n && !A.keys) || !A.agg_pk || (A.verify && (!A.u || !A.R || !A.m))) return fail(JJS_ERR_ARG, "null pointer");
+        dev = g;
+        ++g_blocking_calls;              // jjs_shutdown does not free `dev` before this call has left
+    }
+    blocking_call_leave leave_on_every_way_out;
+    std::lock_guard<std::mutex> big(dev->host_mu);
+    g = dev;
+    return no_throw([&]() -> int {
+        const size_t B = n_transcripts, w = A.ext ? 96 : 64, v = A.verify ? 1 : 0;
+        const void* src[5] = {A.keys, A.u, A.R, A.m, nullptr};
+        const size_t in_bytes[5] = {n * (A.keyset ? 4 : w), v * B * 32, v * B * w, v * B * 32, 0};
+        const size_t out_bytes[5] = {B * 64, v * B, v * 32, (1 - v) * B, 0};
+        msig_stage St{};
+        if (int rc = msig_stage_in(dev, src, in_bytes, out_bytes, St)) return rc;
+        {
+            std::lock_guard<std::mutex> lock(L.mu);
+            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
+            mv_call D = A;
+            if (ks) {                    // (the set is looked up again: it may have been destroyed meanwhile)
+                keyset_entry* k = nullptr;
+                if (int rc = msig_keyset_find(*ks, dev, k, D.c)) return rc;
+                D.k = k;
+            }
+            D.keys = St.in[0]; D.u = St.in[1]; D.R = St.in[2]; D.m = St.in[3];
+            D.agg_pk = St.out[0];
+            D.status = A.status ? St.out[1] : nullptr;
+            D.tally = tally ? St.out[2] : nullptr;
+            D.vec_status = A.vec_status ? St.out[3] : nullptr;
+            if (int rc = msig_verify_locked(D, offsets, B, St.s)) return rc;
+        }
+        uint8_t* const dst[5] = {(uint8_t*)A.agg_pk, (uint8_t*)A.status, (uint8_t*)tally, (uint8_t*)A.vec_status, nullptr};
+        return msig_stage_out(St, dst, out_bytes);
+    });
+}
+}  // extern "C++"
+
+extern "C" {
+
+int jjs_multisig_aggregate_pk_dev(int format, const void* PK, const uint32_t* offsets_host, size_t n_transcripts, void* agg_pk,
+                                  void* vec_status, void* stream) {
+    mv_call A{};
+    A.keys = PK; A.agg_pk = agg_pk; A.vec_status = vec_status;
+    return msig_verify_dev(A, nullptr, format, offsets_host, n_transcripts, stream);
+}
+int jjs_multisig_aggregate_pk(int format, const uint8_t* PK, const uint32_t* offsets, size_t n_transcripts, uint8_t* agg_pk,
+                              uint8_t* vec_status) {
+    mv_call A{};
+    A.keys = PK; A.agg_pk = agg_pk; A.vec_status = vec_status;
+    return msig_verify_host(A, nullptr, format, offsets, n_transcripts, nullptr);
+}
+int jjs_multisig_aggregate_pk_keyset_dev(jjs_keyset ks, const void* key_idx, const uint32_t* offsets_host, size_t n_transcripts,
+                                         void* agg_pk, void* vec_status, void* stream) {
+    mv_call A{};
+    A.keyset = true; A.keys = key_idx; A.agg_pk = agg_pk; A.vec_status = vec_status;
+    return msig_verify_dev(A, &ks, JJS_FORMAT_AFFINE, offsets_host, n_transcripts, stream);
+}
+int jjs_multisig_aggregate_pk_keyset(jjs_keyset ks, const uint32_t* key_idx, const uint32_t* offsets, size_t n_transcripts,
+                                     uint8_t* agg_pk, uint8_t* vec_status) {
+    mv_call A{};
+    A.keyset = true; A.keys = key_idx; A.agg_pk = agg_pk; A.vec_status = vec_status;
+    return msig_verify_host(A, &ks, JJS_FORMAT_AFFINE, offsets, n_transcripts, nullptr);
+}
+
+int jjs_multisig_verify_dev(int format, const void* PK, const uint32_t* offsets_host, const void* u, const void* R, const void* m,
+                            size_t n_transcripts, void* agg_pk, void* status, void* tally, void* stream) {
+    mv_call A{};
+    A.verify = true; A.keys = PK; A.u = u; A.R = R; A.m = m; A.agg_pk = agg_pk; A.status = status; A.tally = tally;
+    return msig_verify_dev(A, nullptr, format, offsets_host, n_transcripts, stream);
+}
+int jjs_multisig_verify(int format, const uint8_t* PK, const uint32_t* offsets, const uint8_t* u, const uint8_t* R, const uint8_t* m,
+                        size_t n_transcripts, uint8_t* agg_pk, uint8_t* status, uint64_t tally[4]) {
+    mv_call A{};
+    A.verify = true; A.keys = PK; A.u = u; A.R = R; A.m = m; A.agg_pk = agg_pk; A.status = status;
+    return msig_verify_host(A, nullptr, format, offsets, n_transcripts, tally);
+}
+int jjs_multisig_verify_keyset_dev(jjs_keyset ks, int format, const void* key_idx, const uint32_t* offsets_host, const void* u,
+                                   const void* R, const void* m, size_t n_transcripts, void* agg_pk, void* status, void* tally,
+                                   void* stream) {
+    mv_call A{};
+    A.keyset = true; A.verify = true; A.keys = key_idx; A.u = u; A.R = R; A.m = m; A.agg_pk = agg_pk; A.status = status; A.tally = tally;
+    return msig_verify_dev(A, &ks, format, offsets_host, n_transcripts, stream);
+}
+int jjs_multisig_verify_keyset(jjs_keyset ks, int format, const uint32_t* key_idx, const uint32_t* offsets, const uint8_t* u,
+                               const uint8_t* R, const uint8_t* m, size_t n_transcripts, uint8_t* agg_pk, uint8_t* status,
+                               uint64_t tally[4]) {
+    mv_call A{};
+    A.keyset = true; A.verify = true; A.keys = key_idx; A.u = u; A.R = R; A.m = m; A.agg_pk = agg_pk; A.status = status;
+    return msig_verify_host(A, &ks, format, offsets, n_transcripts, tally);
+}
+
+}  // extern "C"
