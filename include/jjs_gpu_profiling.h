@@ -63,6 +63,24 @@ int jjs_debug_msm_dev(const void* points, const void* scalars, size_t n, unsigne
  * columns.  Device pointers, 16-byte aligned; asynchronous on `stream`. */
 int jjs_debug_keyset_sums_dev(jjs_keyset ks, const void* key_idx, const void* a0, const void* a1, size_t n, void* sums_out, void* point_out,
                               void* stream);
+/* The per-item pass of jjs_verify_all_* with what it wrote copied out (tests/test_fr_gpu.py): the descriptor, scratch, clear
+ * and item kernel exactly as a verdict call runs them, the weights drawn under the call's seed (jjs_debug_pin_hash_seed(2)
+ * fixes it) with the bits of window width c (8 .. 16).  d0 .. d5: the scheme's affine columns in the order of
+ * jjs_verify_all_*_dev (the unused ones null).  blocks: the item kernel's grid, 0 = the call's own (at most ceil(n / 256)).
+ * scalars_out: n_kinds * n scalars of 32 bytes, kind k's at k * n (single: z on R, z c on PK; double: the same for the second
+ * equation behind them; per-item generator: z on R, z c on PK, z u on Gen); partial_out: 64 bytes per block, its sum of z u
+ * and of z' u mod r; fail_out: the fail word; zu_out: 64 bytes, the two totals as the final kernel adds the partial sums up.
+ * *blocks_out (host) is the grid that ran, written before the call returns.  Device pointers, 16-byte aligned; asynchronous
+ * on `stream`. */
+int jjs_debug_verdict_items_dev(int scheme, const void* d0, const void* d1, const void* d2, const void* d3, const void* d4, const void* d5,
+                                size_t n, int c, unsigned blocks, void* scalars_out, void* partial_out, void* fail_out, void* zu_out,
+                                unsigned* blocks_out, void* stream);
+/* The same for jjs_keyset_verify_all* (affine signatures): the grouping by key and the keyed item kernel as a verdict call
+ * runs them.  scalars_out: n_eq * n weights on R (and R'); a0_out, a1_out: n x 32 bytes, the items' scalars on point column 0 / 1
+ * of their key (a1_out is not written for a set with one point column); the rest as above. */
+int jjs_debug_keyset_items_dev(jjs_keyset ks, const void* key_idx, const void* u, const void* R, const void* Rp, const void* m, size_t n, int c,
+                               unsigned blocks, void* scalars_out, void* a0_out, void* a1_out, void* partial_out, void* fail_out, void* zu_out,
+                               unsigned* blocks_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -110,6 +110,8 @@ PROFILING_SIGNATURES = {
     "jjs_debug_pin_hash_seed": [_I],
     "jjs_debug_msm_dev": [_P, _P, _Z, ctypes.c_uint, ctypes.c_uint, _I, _I, _P, _P, _P, _P, _P],
     "jjs_debug_keyset_sums_dev": [ctypes.c_uint64, _P, _P, _P, _Z, _P, _P, _P],
+    "jjs_debug_verdict_items_dev": [_I, _P, _P, _P, _P, _P, _P, _Z, _I, ctypes.c_uint, _P, _P, _P, _P, _P, _P],
+    "jjs_debug_keyset_items_dev": [ctypes.c_uint64, _P, _P, _P, _P, _P, _Z, _I, ctypes.c_uint, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 _RESTYPES = {"jjs_shutdown": None, "jjs_last_error": ctypes.c_char_p, "jjs_debug_comb_table_bytes": _Z}
 

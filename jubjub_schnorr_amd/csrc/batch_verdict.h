@@ -58,34 +58,6 @@ JJS_HD void bv_weights(const uint32_t seed[8], uint64_t item, int bits, words8& 
     }
 }
 
-// ---- arithmetic mod r -----------------------------------------------------------------------------------------------------
-JJS_HD words8 fr_mul(const words8& a, const words8& b) {     // a*b mod r; a, b < r
-    words8 r2;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r2.w[i] = JJS_FR_R2_WORDS[i];
-    return fr_mont_mul(fr_mont_mul(a, r2), b);
-}
-JJS_HD words8 fr_add(const words8& a, const words8& b) {     // a+b mod r; a, b < r
-    words8 s, d;
-    uint64_t carry = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { carry += (uint64_t)a.w[i] + b.w[i]; s.w[i] = (uint32_t)carry; carry >>= 32; }
-    uint32_t borrow = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint64_t t = (uint64_t)s.w[i] - JJS_FR_WORDS[i] - borrow;
-        d.w[i] = (uint32_t)t;
-        borrow = (uint32_t)(t >> 63);
-    }
-    return select_words(borrow != 0, s, d);                 // r < 2^252: the sum never carries out of 256 bits
-}
-JJS_HD words8 words_zero() {
-    words8 z;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) z.w[i] = 0;
-    return z;
-}
-
 // ---- the per-item pass ----------------------------------------------------------------------------------------------------
 // Terms of item i: kind k has term index k * n + i.  Kinds: for each equation e, R_e (negated) then PK_e; then Gen for the
 // per-item generator.

@@ -56,9 +56,23 @@ static void ksv_key_launch(const keyset_entry& k, const ksv_key_geometry& G, con
     hipLaunchKernelGGL(ksv_key_kernel, dim3(G.point_blocks), dim3(BLOCK), 0, s, S);
 }
 
-// The verdict algorithm on stream s (under L.mu; g is c's device): d = key_idx, u, R, R', m (device, affine signatures).
-static int keyset_verdict_launch_msm(keyset_entry& k, const keyset_copy& c, const void* const* d, size_t n, uint32_t* verdict, hipStream_t s) {
-    ksv_params B{};
+// The front of the verdict algorithm on stream s (under L.mu; g is c's device), up to and including the item pass: the seed,
+// the grouping of the items by key, the descriptor over d = key_idx, u, R, R', m (device, affine signatures), the MSM's shape
+// (window: its width, 0 = by size), the scratch, the clear, ksv_item_kernel over `blocks` blocks (0: the call's own grid).  It
+// returns with the slot shared (begin_shared): the caller queues what reads the scratch and ends with end_shared.
+struct keyset_verdict_front {
+    ksv_params B;
+    msm_params M;
+    ksv_key_geometry G;
+    ksv_key_params S;
+    uint32_t blocks;
+    uint32_t* span_sum;
+};
+static int keyset_verdict_front_launch(keyset_entry& k, const keyset_copy& c, const void* const* d, size_t n, int window, uint32_t blocks,
+                                       hipStream_t s, keyset_verdict_front& V) {
+    ksv_params& B = V.B;
+    msm_params& M = V.M;
+    B = ksv_params{};
     if (int rc = batch_seed(B.seed)) return rc;
     keyset_front F;
     if (int rc = keyset_front_end(k, c, d[0], n, true, s, F)) return rc;
@@ -68,19 +82,19 @@ static int keyset_verdict_launch_msm(keyset_entry& k, const keyset_copy& c, cons
     B.keyid = F.X.keyid;
     for (uint32_t i = 0; i < k.n_cols; ++i) B.key_flags[i] = c.flags[i];
 
-    msm_params M{};
+    M = msm_params{};
     M.n = n; M.N = (uint64_t)B.V.n_eq * n;
     M.neg_kinds = (1u << B.V.n_eq) - 1u;                 // every term is a -R
-    static_cast<msm_shape&>(M) = msm_shape_short(msm_window(msm_pick_short_window(M.N)));
+    static_cast<msm_shape&>(M) = msm_shape_short(window ? window : msm_window(msm_pick_short_window(M.N)));
     B.z_bits = msm_weight_bits(M.c);
-    const uint32_t blocks = (uint32_t)grid_for(g->grid_prepare, n);
+    V.blocks = blocks ? blocks : (uint32_t)grid_for(g->grid_prepare, n);
     const size_t nb = (size_t)M.W * M.B;
-    const ksv_key_geometry G = ksv_key_parts(k, n);
+    V.G = ksv_key_parts(k, n);
     uint8_t* q[7];
-    uint32_t* span_sum = nullptr;
-    if (int rc = verdict_scratch(B, M, blocks, G.extra, 7, q, span_sum)) return rc;
+    V.span_sum = nullptr;
+    if (int rc = verdict_scratch(B, M, V.blocks, V.G.extra, 7, q, V.span_sum)) return rc;
     B.a[0] = q[0]; B.a[1] = q[1];
-    const ksv_key_params S = ksv_key_setup(k, c, F, n, B.a[0], B.a[1], q);
+    V.S = ksv_key_setup(k, c, F, n, B.a[0], B.a[1], q);
 
     if (int rc = begin_shared(s)) return rc;
     clear_params Z{};
@@ -89,10 +103,16 @@ static int keyset_verdict_launch_msm(keyset_entry& k, const keyset_copy& c, cons
     Z.p[2] = wire_bad(); Z.bytes[2] = n;
     hipLaunchKernelGGL(clear_kernel, dim3((unsigned)grid_for(256, (nb > n ? nb : n) / 16 + 1)), dim3(BLOCK), 0, s, Z);
     keyset_front_launch(F, true, s);
-    hipLaunchKernelGGL(ksv_item_kernel, dim3(blocks), dim3(BLOCK), 0, s, B);
-    ksv_key_launch(k, G, S, s);
-    msm_launch(M, span_sum, s);                          // over the R terms
-    hipLaunchKernelGGL(ksv_final_kernel, dim3(1), dim3(BLOCK), 0, s, B, M, blocks, (const uint32_t*)S.points, G.point_blocks, verdict);
+    hipLaunchKernelGGL(ksv_item_kernel, dim3(V.blocks), dim3(BLOCK), 0, s, B);
+    return JJS_OK;
+}
+// The verdict algorithm on stream s (under L.mu; g is c's device): d = key_idx, u, R, R', m (device, affine signatures).
+static int keyset_verdict_launch_msm(keyset_entry& k, const keyset_copy& c, const void* const* d, size_t n, uint32_t* verdict, hipStream_t s) {
+    keyset_verdict_front V;
+    if (int rc = keyset_verdict_front_launch(k, c, d, n, 0, 0, s, V)) return rc;
+    ksv_key_launch(k, V.G, V.S, s);
+    msm_launch(V.M, V.span_sum, s);                      // over the R terms
+    hipLaunchKernelGGL(ksv_final_kernel, dim3(1), dim3(BLOCK), 0, s, V.B, V.M, V.blocks, (const uint32_t*)V.S.points, V.G.point_blocks, verdict);
     HIP_TRY(hipGetLastError());
     return end_shared(s);
 }
@@ -176,6 +196,34 @@ int jjs_keyset_verify_all(jjs_keyset ks, int format, const uint32_t* key_idx, co
 }
 
 #if defined(JJS_PROFILING)
+// include/jjs_gpu_profiling.h: the item pass of a key-set verdict call -- keyset_verdict_front_launch, as
+// keyset_verdict_launch_msm runs it -- with what it wrote copied out
+int jjs_debug_keyset_items_dev(jjs_keyset ks, const void* key_idx, const void* u, const void* R, const void* Rp, const void* m, size_t n, int c,
+                               unsigned blocks, void* scalars_out, void* a0_out, void* a1_out, void* partial_out, void* fail_out, void* zu_out,
+                               unsigned* blocks_out, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    keyset_entry* k = g_keysets.find(ks);
+    if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
+    if (int rc = debug_items_args(n, 2ull * n, c, blocks, scalars_out, partial_out, fail_out, zu_out, blocks_out)) return rc;
+    if (!all_ok(a0_out) || (k->n_cols > 1 && !all_ok(a1_out))) return fail(JJS_ERR_ARG, "null or misaligned pointer");
+    if (int rc = keyset_check_cols(k->scheme, JJS_FORMAT_AFFINE, key_idx, u, R, Rp, m, true)) return rc;
+    const keyset_copy* cp = copy_for(*k, g);
+    if (!cp) return fail(JJS_ERR_ARG, "the key set has no copy on this device");
+    const void* d[] = {key_idx, u, R, Rp, m};
+    hipStream_t s = (hipStream_t)stream;
+    return no_throw([&]() -> int {
+        keyset_verdict_front V;
+        if (int rc = keyset_verdict_front_launch(*k, *cp, d, n, c, blocks, s, V)) return rc;
+        *blocks_out = V.blocks;
+        int rc = debug_items_out(V.B.scalars, (size_t)V.M.N * 32, V.B.partial, V.blocks, V.B.fail, scalars_out, partial_out, fail_out, zu_out, s);
+        if (!rc && hipMemcpyAsync(a0_out, V.B.a[0], n * 32, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = fail(JJS_ERR_HIP, "copying the scalar column");
+        if (!rc && k->n_cols > 1 && hipMemcpyAsync(a1_out, V.B.a[1], n * 32, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            rc = fail(JJS_ERR_HIP, "copying the scalar column");
+        const int rc2 = end_shared(s);
+        return rc ? rc : rc2;
+    });
+}
 // include/jjs_gpu_profiling.h: the run sums and the key points of keyset_verdict_launch_msm under the caller's own scalar
 // columns -- the same front end, scratch, descriptor and launches, then dbg_ksv_sums_kernel
 int jjs_debug_keyset_sums_dev(jjs_keyset ks, const void* key_idx, const void* a0, const void* a1, size_t n, void* sums_out, void* point_out,

@@ -54,29 +54,13 @@ __global__ __launch_bounds__(BLOCK, 2) void ksv_key_kernel(ksv_key_params S) {
 // fixed-base part, the verdict word
 __global__ __launch_bounds__(BLOCK) void ksv_final_kernel(ksv_params B, msm_params M, uint32_t blocks, const uint32_t* points,
                                                           uint32_t point_blocks, uint32_t* verdict) {
-    __shared__ words8 red[2][BLOCK];
     __shared__ uint32_t pts[BLOCK * MSM_EXT_WORDS];
-    words8 acc[2] = {words_zero(), words_zero()};
-    for (uint32_t b = threadIdx.x; b < blocks; b += BLOCK) {
-        acc[0] = fr_add(acc[0], load_words(fe_src{B.partial, 32, 0}, 2 * b));
-        acc[1] = fr_add(acc[1], load_words(fe_src{B.partial, 32, 0}, 2 * b + 1));
-    }
+    words8 zu[2];
+    verdict_sum_partials(B.partial, blocks, zu);
     ext_pt sum = ext_identity();
     for (uint32_t b = threadIdx.x; b < point_blocks; b += BLOCK) sum = msm_add_ext(sum, msm_load_ext(points + (size_t)b * MSM_EXT_WORDS));
-    red[0][threadIdx.x] = acc[0];
-    red[1][threadIdx.x] = acc[1];
-    msm_store_ext(pts + threadIdx.x * MSM_EXT_WORDS, sum);
-    __syncthreads();
-    for (int step = BLOCK / 2; step > 0; step >>= 1) {
-        if ((int)threadIdx.x < step) {
-            for (int e = 0; e < 2; ++e) red[e][threadIdx.x] = fr_add(red[e][threadIdx.x], red[e][threadIdx.x + step]);
-            msm_store_ext(pts + threadIdx.x * MSM_EXT_WORDS,
-                          msm_add_ext(msm_load_ext(pts + threadIdx.x * MSM_EXT_WORDS), msm_load_ext(pts + (threadIdx.x + step) * MSM_EXT_WORDS)));
-        }
-        __syncthreads();
-    }
+    block_sum_ext(pts, sum);
     if (threadIdx.x == 0) {
-        const words8 zu[2] = {red[0][0], red[1][0]};
         const ext_pt total = msm_add_ext(msm_combine(M.win, M.W, M.c), msm_load_ext(pts));
         *verdict = bv_verdict(B.V, total, zu, *B.fail != 0u) ? 1u : 0u;
     }

@@ -111,9 +111,7 @@ JJS_HD void mg_share_item(const msig_group_params& G, uint64_t i) {
     bool malformed = !words_lt(z, JJS_FR_WORDS) || !words_lt(load_words(ms, t), JJS_Q_WORDS);
     for (int e = 0; e < 2; ++e)
         malformed = malformed || !words_lt(load_words(rs, i, 32u * e), JJS_Q_WORDS) || !words_lt(load_words(ss, i, 32u * e), JJS_Q_WORDS);
-    words8 r2;
-    for (int k = 0; k < 8; ++k) r2.w[k] = JJS_FR_R2_WORDS[k];
-    const words8 cd = fr_mont_mul(fr_mont_mul(load_w8(P.c_words + 8 * t), r2), load_w8(G.d_words + 8 * (size_t)j));
+    const words8 cd = fr_mul(load_w8(P.c_words + 8 * t), load_w8(G.d_words + 8 * (size_t)j));
     key_column C{};
     C.tables = const_cast<uint32_t*>(G.tables);
     ext_pt lhs = kt_add_scalar(ext_identity(), C, j, cd, MG_WINDOW);          // T valid: the comb additions need it

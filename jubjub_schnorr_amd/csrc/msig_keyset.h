@@ -82,9 +82,7 @@ JJS_HD void mk_share_item(const msig_keyset_params& K, uint64_t i) {
     bool malformed = !words_lt(z, JJS_FR_WORDS) || !words_lt(load_words(ms, t), JJS_Q_WORDS);
     for (int e = 0; e < 2; ++e)
         malformed = malformed || !words_lt(load_words(rs, i, 32u * e), JJS_Q_WORDS) || !words_lt(load_words(ss, i, 32u * e), JJS_Q_WORDS);
-    words8 r2;
-    for (int k = 0; k < 8; ++k) r2.w[k] = JJS_FR_R2_WORDS[k];
-    const words8 cd = fr_mont_mul(fr_mont_mul(load_w8(P.c_words + 8 * t), r2), load_w8(P.d_words + 8 * i));
+    const words8 cd = fr_mul(load_w8(P.c_words + 8 * t), load_w8(P.d_words + 8 * i));
     ext_pt lhs = kt_add_scalar(ext_identity(), mk_column(K), K.row_key[i], cd, KEYSET_WINDOW);   // T valid: the comb additions need it
     lhs = add_comb(lhs, P.comb_g, z);
     const ext_pt e = load_ext(P.e_pt + EXT_WORDS * i);

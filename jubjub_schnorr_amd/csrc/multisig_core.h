@@ -133,15 +133,7 @@ JJS_HD void msig_final_range(const msig_params& P, uint32_t t, uint32_t lo, uint
     store_w8(P.c_words + 8 * t, truncate250(dg));
     // u = sum z_i mod r
     words8 u = small_words(0);
-    for (uint32_t i = lo; i < hi; ++i) {
-        const words8 z = load_words(zs, i);
-        uint64_t carry = 0;
-        words8 s, d;
-        for (int k = 0; k < 8; ++k) { uint64_t x = (uint64_t)u.w[k] + z.w[k] + carry; s.w[k] = (uint32_t)x; carry = x >> 32; }
-        uint32_t borrow = 0;
-        for (int k = 0; k < 8; ++k) { uint64_t x = (uint64_t)s.w[k] - JJS_FR_WORDS[k] - borrow; d.w[k] = (uint32_t)x; borrow = (uint32_t)(x >> 63); }
-        u = select_words(borrow != 0, s, d);      // both addends < r < 2^252: no carry out of 256 bits
-    }
+    for (uint32_t i = lo; i < hi; ++i) u = fr_add(u, load_words(zs, i));
     store_words(P.sig_u, t, u);
 }
 JJS_HD void msig_final_item(const msig_params& P, uint32_t t, int coop = -1) {
@@ -157,9 +149,7 @@ JJS_HD void msig_share_item(const msig_params& P, uint64_t i, uint32_t* ws) {
         malformed = malformed || !words_lt(load_words(pk, i, 32u * e), JJS_Q_WORDS) || !words_lt(load_words(rs, i, 32u * e), JJS_Q_WORDS) ||
                     !words_lt(load_words(ss, i, 32u * e), JJS_Q_WORDS);
     }
-    words8 r2;
-    for (int k = 0; k < 8; ++k) r2.w[k] = JJS_FR_R2_WORDS[k];
-    const words8 cd = fr_mont_mul(fr_mont_mul(load_w8(P.c_words + 8 * t), r2), load_w8(P.d_words + 8 * i));
+    const words8 cd = fr_mul(load_w8(P.c_words + 8 * t), load_w8(P.d_words + 8 * i));
     build_point_table(ws, load_fq(pk, i), load_fq(pk, i, 32));
     ext_pt lhs = table_mul(ws, cd, true);                          // T needed by the comb additions
     lhs = add_comb(lhs, P.comb_g, z);

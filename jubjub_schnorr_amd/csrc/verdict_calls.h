@@ -103,30 +103,47 @@ static void msm_launch(const msm_params& M, uint32_t* span_sum, hipStream_t s) {
     hipLaunchKernelGGL(msm_window_kernel, dim3((unsigned)M.W), dim3(BLOCK), 0, s, M);
 }
 
-// The verdict algorithm on stream s (under L.mu; g is the device): d = the affine columns in the entry point's order.
-static int verdict_launch_msm(int scheme, const void* const* d, size_t n, uint32_t* verdict, hipStream_t s) {
-    bv_params B{};
+// The front of the verdict algorithm on stream s (under L.mu; g is the device), up to and including the item pass: the
+// descriptor over d = the affine columns in the entry point's order, the seed, the MSM's shape (window: its width, 0 = by
+// size), the slot and its scratch, the clear, bv_item_kernel over `blocks` blocks (0: the call's own grid).  It returns with the
+// slot shared (begin_shared): the caller queues what reads the scratch and ends with end_shared.
+struct verdict_front {
+    bv_params B;
+    msm_params M;
+    uint32_t blocks;
+    uint32_t* span_sum;
+};
+static int verdict_front_launch(int scheme, const void* const* d, size_t n, int window, uint32_t blocks, hipStream_t s, verdict_front& F) {
+    bv_params& B = F.B;
+    msm_params& M = F.M;
+    B = bv_params{};
     B.V = verdict_params(scheme, d, n);
     if (int rc = batch_seed(B.seed)) return rc;
     B.n_kinds = bv_kinds(B.V);
-    msm_params M{};
+    M = msm_params{};
     M.n = n; M.N = (uint64_t)B.n_kinds * n;
     for (uint32_t k = 0; k < B.n_kinds; ++k) M.neg_kinds |= bv_kind_negated(B.V, k) ? 1u << k : 0u;
-    static_cast<msm_shape&>(M) = msm_shape_full(msm_window(msm_pick_window(M.N)));
+    static_cast<msm_shape&>(M) = msm_shape_full(window ? window : msm_window(msm_pick_window(M.N)));
     B.z_bits = msm_weight_bits(M.c);
-    const uint32_t blocks = (uint32_t)grid_for(g->grid_prepare, n);
+    F.blocks = blocks ? blocks : (uint32_t)grid_for(g->grid_prepare, n);
     pick_slot(n, s);
-    uint32_t* span_sum = nullptr;
-    if (int rc = verdict_scratch(B, M, blocks, nullptr, 0, nullptr, span_sum)) return rc;
+    F.span_sum = nullptr;
+    if (int rc = verdict_scratch(B, M, F.blocks, nullptr, 0, nullptr, F.span_sum)) return rc;
     if (int rc = begin_shared(s)) return rc;
     const size_t nb = (size_t)M.W * M.B;
     clear_params Z{};
     Z.p[0] = B.fail; Z.bytes[0] = 4;
     Z.p[1] = M.off; Z.bytes[1] = (nb + 1) * 4;
     hipLaunchKernelGGL(clear_kernel, dim3((unsigned)grid_for(256, nb / 16 + 1)), dim3(BLOCK), 0, s, Z);
-    hipLaunchKernelGGL(bv_item_kernel, dim3(blocks), dim3(BLOCK), 0, s, B);
-    msm_launch(M, span_sum, s);
-    hipLaunchKernelGGL(bv_final_kernel, dim3(1), dim3(BLOCK), 0, s, B, M, blocks, verdict);
+    hipLaunchKernelGGL(bv_item_kernel, dim3(F.blocks), dim3(BLOCK), 0, s, B);
+    return JJS_OK;
+}
+// The verdict algorithm on stream s (under L.mu; g is the device): d = the affine columns in the entry point's order.
+static int verdict_launch_msm(int scheme, const void* const* d, size_t n, uint32_t* verdict, hipStream_t s) {
+    verdict_front F;
+    if (int rc = verdict_front_launch(scheme, d, n, 0, 0, s, F)) return rc;
+    msm_launch(F.M, F.span_sum, s);
+    hipLaunchKernelGGL(bv_final_kernel, dim3(1), dim3(BLOCK), 0, s, F.B, F.M, F.blocks, verdict);
     HIP_TRY(hipGetLastError());
     return end_shared(s);
 }
@@ -265,6 +282,48 @@ int jjs_verify_all_vargen_dev(const void* u, const void* R, const void* PK, cons
 }
 
 #if defined(JJS_PROFILING)
+// what the item-pass debug entries check: the forced window width and block count, the output pointers
+static int debug_items_args(size_t n, uint64_t terms, int c, unsigned blocks, const void* scalars_out, const void* partial_out, const void* fail_out,
+                            const void* zu_out, const unsigned* blocks_out) {
+    if (n == 0 || terms >= 0x80000000ull) return fail(JJS_ERR_ARG, "the item count is out of range");
+    if (c < 8 || c > MSM_MAX_WINDOW) return fail(JJS_ERR_ARG, "the window width is out of range");
+    if (blocks > 65536u) return fail(JJS_ERR_ARG, "the block count is out of range");
+    if (!all_ok(scalars_out, partial_out, fail_out, zu_out) || !blocks_out) return fail(JJS_ERR_ARG, "null or misaligned pointer");
+    return JJS_OK;
+}
+// ... and what they copy out behind the item pass: the scalars, the blocks' partial sums, the fail word, then the final
+// kernels' sum of the partial sums from one block
+static int debug_items_out(const uint8_t* scalars, size_t scalar_bytes, const uint8_t* partial, uint32_t blocks, const uint32_t* fail_word,
+                           void* scalars_out, void* partial_out, void* fail_out, void* zu_out, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(scalars_out, scalars, scalar_bytes, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(partial_out, partial, (size_t)blocks * 64, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(fail_out, fail_word, 4, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(dbg_verdict_totals_kernel, dim3(1), dim3(BLOCK), 0, s, partial, blocks, (uint8_t*)zu_out);
+    HIP_TRY(hipGetLastError());
+    return JJS_OK;
+}
+// include/jjs_gpu_profiling.h: the item pass of a verdict call -- verdict_front_launch, as verdict_launch_msm runs it -- with
+// what it wrote copied out
+int jjs_debug_verdict_items_dev(int scheme, const void* d0, const void* d1, const void* d2, const void* d3, const void* d4, const void* d5,
+                                size_t n, int c, unsigned blocks, void* scalars_out, void* partial_out, void* fail_out, void* zu_out,
+                                unsigned* blocks_out, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    if (scheme < 0 || scheme > 2) return fail(JJS_ERR_ARG, "scheme out of range");
+    if (int rc = debug_items_args(n, 4ull * n, c, blocks, scalars_out, partial_out, fail_out, zu_out, blocks_out)) return rc;
+    const void* d[] = {d0, d1, d2, d3, d4, d5};
+    for (size_t k = 0; k < verdict_cols(scheme); ++k)
+        if (!all_ok(d[k])) return fail(JJS_ERR_ARG, "null or misaligned input pointer");
+    hipStream_t s = (hipStream_t)stream;
+    return no_throw([&]() -> int {
+        verdict_front F;
+        if (int rc = verdict_front_launch(scheme, d, n, c, blocks, s, F)) return rc;
+        *blocks_out = F.blocks;
+        const int rc = debug_items_out(F.B.scalars, (size_t)F.M.N * 32, F.B.partial, F.blocks, F.B.fail, scalars_out, partial_out, fail_out, zu_out, s);
+        const int rc2 = end_shared(s);
+        return rc ? rc : rc2;
+    });
+}
 // include/jjs_gpu_profiling.h: the MSM of a verdict call over the caller's own terms -- verdict_scratch, the calls' clear,
 // msm_launch -- with every stage's output copied out
 int jjs_debug_msm_dev(const void* points, const void* scalars, size_t n, unsigned n_kinds, unsigned neg_kinds, int c, int short_shape,

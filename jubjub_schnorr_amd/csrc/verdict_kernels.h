@@ -145,13 +145,14 @@ __global__ __launch_bounds__(BLOCK) void msm_window_kernel(msm_params M) {
     block_sum_ext(red, acc);
     if (threadIdx.x < MSM_EXT_WORDS) M.win[(size_t)j * MSM_EXT_WORDS + threadIdx.x] = red[threadIdx.x];
 }
-// one block: the per-block sums of z u added, the windows combined, the fixed-base part, the verdict word
-__global__ __launch_bounds__(BLOCK) void bv_final_kernel(bv_params B, msm_params M, uint32_t blocks, uint32_t* verdict) {
+// The blocks' partial sums of z u (z' u) added by one block: every lane takes its share of the blocks, then a tree.  Every
+// lane returns with the two totals in sum[0], sum[1].
+__device__ inline void verdict_sum_partials(const uint8_t* partial, uint32_t blocks, words8 sum[2]) {
     __shared__ words8 red[2][BLOCK];
     words8 acc[2] = {words_zero(), words_zero()};
     for (uint32_t b = threadIdx.x; b < blocks; b += BLOCK) {
-        acc[0] = fr_add(acc[0], load_words(fe_src{B.partial, 32, 0}, 2 * b));
-        acc[1] = fr_add(acc[1], load_words(fe_src{B.partial, 32, 0}, 2 * b + 1));
+        acc[0] = fr_add(acc[0], load_words(fe_src{partial, 32, 0}, 2 * b));
+        acc[1] = fr_add(acc[1], load_words(fe_src{partial, 32, 0}, 2 * b + 1));
     }
     red[0][threadIdx.x] = acc[0];
     red[1][threadIdx.x] = acc[1];
@@ -161,8 +162,14 @@ __global__ __launch_bounds__(BLOCK) void bv_final_kernel(bv_params B, msm_params
             for (int e = 0; e < 2; ++e) red[e][threadIdx.x] = fr_add(red[e][threadIdx.x], red[e][threadIdx.x + step]);
         __syncthreads();
     }
+    sum[0] = red[0][0];
+    sum[1] = red[1][0];
+}
+// one block: the per-block sums of z u added, the windows combined, the fixed-base part, the verdict word
+__global__ __launch_bounds__(BLOCK) void bv_final_kernel(bv_params B, msm_params M, uint32_t blocks, uint32_t* verdict) {
+    words8 zu[2];
+    verdict_sum_partials(B.partial, blocks, zu);
     if (threadIdx.x == 0) {
-        const words8 zu[2] = {red[0][0], red[1][0]};
         const ext_pt total = msm_combine(M.win, M.W, M.c);
         *verdict = bv_verdict(B.V, total, zu, *B.fail != 0u) ? 1u : 0u;
     }
@@ -181,6 +188,15 @@ __global__ __launch_bounds__(BLOCK) void dbg_msm_terms_kernel(const uint8_t* poi
     const fe_src src{points, 64, 0};
     msm_store_term(terms + t * MSM_TERM_WORDS, load_fq(src, t), load_fq(src, t, 32));
     store_words(term_scalars, t, load_words(fe_src{scalars, 32, 0}, t));
+}
+// jjs_debug_verdict_items_dev, jjs_debug_keyset_items_dev: the final kernels' sum of the item pass's partial sums, written out
+__global__ __launch_bounds__(BLOCK) void dbg_verdict_totals_kernel(const uint8_t* partial, uint32_t blocks, uint8_t* zu_out) {
+    words8 zu[2];
+    verdict_sum_partials(partial, blocks, zu);
+    if (threadIdx.x == 0) {
+        store_words(zu_out, 0, zu[0]);
+        store_words(zu_out, 1, zu[1]);
+    }
 }
 // ... and what the MSM left: off (W * B + 1 words), order (off[W * B] words), win (W points), msm_combine(win) from one lane
 __global__ __launch_bounds__(BLOCK) void dbg_msm_out_kernel(msm_params M, uint32_t* off_out, uint32_t* order_out, uint32_t* win_out,

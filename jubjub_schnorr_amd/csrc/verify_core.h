@@ -191,7 +191,22 @@ JJS_HD ext_pt add_window(const ext_pt& acc, const uint32_t* tab, const words8& s
     return ext_add_niels(acc, load_niels(tab + idx * ENTRY_WORDS), neg != flip, need_t);
 }
 
-// ---- arithmetic mod r (JubJubScalar), 8 x 32-bit Montgomery; only u = r - c*sk needs it ----------
+// ---- arithmetic mod r (JubJubScalar), 8 x 32-bit words: the signer's u = r - c*sk, the half-size equation's b*u, the batch
+// verdicts' weighted scalars and their sums, the multisignature's c*d and sum z ----------------------------------------------
+JJS_HD words8 select_words(bool c, const words8& a, const words8& b) {
+    words8 r;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.w[i] = c ? a.w[i] : b.w[i];
+    return r;
+}
+JJS_HD words8 words_zero() {
+    words8 z;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) z.w[i] = 0;
+    return z;
+}
+// a*b*2^-256 mod r.  Contract: inputs below r give a result below r; any 256-bit inputs give a congruent 256-bit result
+// (not always below r: only half_scalar_times_u on a malformed u >= r passes one, and its item is malformed whatever comes out).
 JJS_HD words8 fr_mont_mul(const words8& a, const words8& b) {
     uint32_t t[10];
 #pragma unroll
@@ -234,6 +249,26 @@ JJS_HD words8 fr_mont_mul(const words8& a, const words8& b) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) r.w[i] = keep ? r.w[i] : s.w[i];
     return r;
+}
+JJS_HD words8 fr_mul(const words8& a, const words8& b) {     // a*b mod r; a, b < r
+    words8 r2;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r2.w[i] = JJS_FR_R2_WORDS[i];
+    return fr_mont_mul(fr_mont_mul(a, r2), b);
+}
+JJS_HD words8 fr_add(const words8& a, const words8& b) {     // a+b mod r; a, b < r
+    words8 s, d;
+    uint64_t carry = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { carry += (uint64_t)a.w[i] + b.w[i]; s.w[i] = (uint32_t)carry; carry >>= 32; }
+    uint32_t borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint64_t t = (uint64_t)s.w[i] - JJS_FR_WORDS[i] - borrow;
+        d.w[i] = (uint32_t)t;
+        borrow = (uint32_t)(t >> 63);
+    }
+    return select_words(borrow != 0, s, d);                 // r < 2^252: the sum never carries out of 256 bits
 }
 // (a - b*c) mod r for canonical a, b, c
 JJS_HD words8 fr_sub_mul(const words8& a, const words8& b, const words8& c) {
@@ -617,13 +652,6 @@ JJS_HD words8 recode_signed4_128(const u128w& s) {
         r.w[i] = (uint32_t)t;
         carry = t >> 32;
     }
-    return r;
-}
-
-JJS_HD words8 select_words(bool c, const words8& a, const words8& b) {
-    words8 r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.w[i] = c ? a.w[i] : b.w[i];
     return r;
 }
 

@@ -16,6 +16,7 @@
 #include "safe_tag.h"
 #include "../../jubjub_schnorr_amd/tools/scalar_stages.h"
 #include "../../jubjub_schnorr_amd/tools/ingest_stages.h"
+#include "../../jubjub_schnorr_amd/tools/fr_stages.h"
 
 using namespace jjs;
 
@@ -237,8 +238,39 @@ struct host_ingest {
     }
 };
 
+// tools/fr_stages.h on this thread: the items of a record one after the other
+struct host_fr {
+    const uint32_t* in;
+    size_t in_words, pos = 0;
+    int records = 0;
+    std::vector<uint32_t> out;
+    template <typename S>
+    int step(uint32_t n) {
+        if (!fr::record_fits<S>(in_words, pos, n)) return 1;
+        uint32_t res[S::OUT];
+        for (uint32_t i = 0; i < n; ++i) {
+            memset(res, 0xff, sizeof(res));
+            S::run(in + pos + (size_t)S::IN * i, res);
+            out.insert(out.end(), res, res + S::OUT);
+        }
+        pos += (size_t)S::IN * n;
+        return 0;
+    }
+};
+
 extern "C" {
 
+// the records of tools/fr_stages.h (the arithmetic mod r, truncate250, the ChaCha20 block, the batch weights); returns 0 and
+// the number of output words, or the failing record's code
+int jjs_host_fr_records(const uint32_t* in, size_t in_words, uint32_t* out, size_t out_cap, size_t* out_words) {
+    host_fr x{in, in_words};
+    const int rc = fr::run_records(x);
+    if (rc) return rc;
+    if (x.out.size() > out_cap) return 4;
+    memcpy(out, x.out.data(), 4 * x.out.size());
+    *out_words = x.out.size();
+    return 0;
+}
 // the records of tools/ingest_stages.h (inversion, inverse square roots, decoding, normalisation, the square-root tables);
 // returns 0 and the number of output words, or the failing record's code
 int jjs_host_ingest_records(const uint32_t* in, size_t in_words, uint32_t* out, size_t out_cap, size_t* out_words) {

@@ -100,10 +100,16 @@ int jjs_ksv_host_key_sums(int scheme, const uint8_t* keys0, const uint8_t* keys1
 // c: the window width of the bucket method (0: by size); poison: the tables of the keys that are not valid are filled with
 // 0xFF before the call.  Outputs (nullable): total = the affine sum (sum z u) G + sum_k S_k PK_k - sum z_i R_i (64 bytes),
 // key_sums = the S_k of point column 0 then 1 (n_keys x 32 each), key_status, z_bits = the bits of the weights.
-int jjs_ksv_host_verify_all(int scheme, const uint8_t* keys0, const uint8_t* keys1, uint32_t n_keys, const uint32_t* key_idx,
-                            const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* m, size_t n, const uint8_t seed[32],
-                            int c, int poison, int* verdict, uint8_t* total_out, uint8_t* key_sums, uint8_t* key_status, int* z_bits) {
-    if (scheme < 0 || scheme > 2 || n_keys == 0 || n == 0 || !verdict) return -1;
+// The item pass alone (items != 0), as jjs_debug_keyset_items_dev copies it out on the device: scalars_out = the n_eq * n
+// weights, a_out[0], a_out[1] = the items' scalars on their key's point columns (n x 32), partial_out = for each grid of
+// grids[0 .. n_grids) the partial sums of its blocks (item i belongs to block (i / 256) mod blocks; 64 bytes per block, grid after
+// grid), fail_out, zu_out = the two totals (64 bytes).
+static int ksv_host_run(int scheme, const uint8_t* keys0, const uint8_t* keys1, uint32_t n_keys, const uint32_t* key_idx,
+                        const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* m, size_t n, const uint8_t seed[32],
+                        int c, int poison, int* verdict, uint8_t* total_out, uint8_t* key_sums, uint8_t* key_status, int* z_bits,
+                        int items, const uint32_t* grids, size_t n_grids, uint8_t* scalars_out, uint8_t* const* a_out, uint8_t* partial_out, uint32_t* fail_out,
+                        uint8_t* zu_out) {
+    if (scheme < 0 || scheme > 2 || n_keys == 0 || n == 0) return -1;
     ensure_tables();
     const int w = KEYSET_WINDOW;
     host_set set(scheme, keys0, keys1, n_keys, n, poison);
@@ -144,11 +150,32 @@ int jjs_ksv_host_verify_all(int scheme, const uint8_t* keys0, const uint8_t* key
     }
     bool failed = false;
     words8 sum[2] = {words_zero(), words_zero()};
+    std::vector<words8> per_item;
     for (uint64_t i = 0; i < n; ++i) {
         words8 zu[2];
         failed = !ksv_item(B, i, zu) || failed;
-        sum[0] = fr_add(sum[0], zu[0]);
-        sum[1] = fr_add(sum[1], zu[1]);
+        for (int e = 0; e < 2; ++e) {
+            sum[e] = fr_add(sum[e], zu[e]);
+            per_item.push_back(zu[e]);
+        }
+    }
+    if (items) {
+        memcpy(scalars_out, B.scalars, N * 32);
+        for (uint32_t ci = 0; ci < cols; ++ci) memcpy(a_out[ci], B.a[ci], n * 32);
+        for (size_t g = 0; g < n_grids; ++g) {
+            if (grids[g] == 0) return -1;
+            std::vector<words8> part(2 * (size_t)grids[g], words_zero());
+            for (uint64_t i = 0; i < n; ++i)
+                for (int e = 0; e < 2; ++e) {
+                    words8& p = part[2 * (size_t)((i / 256) % grids[g]) + e];
+                    p = fr_add(p, per_item[2 * i + e]);
+                }
+            memcpy(partial_out, part.data(), 64 * (size_t)grids[g]);
+            partial_out += 64 * (size_t)grids[g];
+        }
+        *fail_out = failed ? 1u : 0u;
+        memcpy(zu_out, sum[0].w, 32); memcpy(zu_out + 32, sum[1].w, 32);
+        return 0;
     }
     std::vector<uint32_t> cursor, order;
     sort_by_key(keyid, n_keys, n, cursor, order);
@@ -170,6 +197,21 @@ int jjs_ksv_host_verify_all(int scheme, const uint8_t* keys0, const uint8_t* key
         to_affine_bytes(total, total_out);
     }
     return 0;
+}
+int jjs_ksv_host_verify_all(int scheme, const uint8_t* keys0, const uint8_t* keys1, uint32_t n_keys, const uint32_t* key_idx,
+                            const uint8_t* u, const uint8_t* R, const uint8_t* Rp, const uint8_t* m, size_t n, const uint8_t seed[32],
+                            int c, int poison, int* verdict, uint8_t* total_out, uint8_t* key_sums, uint8_t* key_status, int* z_bits) {
+    if (!verdict) return -1;
+    return ksv_host_run(scheme, keys0, keys1, n_keys, key_idx, u, R, Rp, m, n, seed, c, poison, verdict, total_out, key_sums, key_status, z_bits,
+                        0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+int jjs_ksv_host_items(int scheme, const uint8_t* keys0, const uint8_t* keys1, uint32_t n_keys, const uint32_t* key_idx, const uint8_t* u,
+                       const uint8_t* R, const uint8_t* Rp, const uint8_t* m, size_t n, const uint8_t seed[32], int c, const uint32_t* grids,
+                       size_t n_grids, uint8_t* scalars_out, uint8_t* a0_out, uint8_t* a1_out, uint8_t* partial_out, uint32_t* fail_out, uint8_t* zu_out) {
+    if (c < 8 || !scalars_out || !a0_out || !partial_out || !fail_out || !zu_out) return -1;
+    uint8_t* const a_out[2] = {a0_out, a1_out};
+    return ksv_host_run(scheme, keys0, keys1, n_keys, key_idx, u, R, Rp, m, n, seed, c, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                        1, grids, n_grids, scalars_out, a_out, partial_out, fail_out, zu_out);
 }
 
 }  // extern "C"

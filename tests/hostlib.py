@@ -17,7 +17,8 @@ def build_hostlib(src, lib):
     """Compile a harness under tests/hostbuild into `lib` unless it is newer than its sources, and load it."""
     hostbuild = os.path.dirname(SRC)
     deps = [src, SRC, os.path.join(hostbuild, "host_msm.h"), os.path.join(ROOT, "jubjub_schnorr_amd", "tools", "scalar_stages.h"),
-            os.path.join(ROOT, "jubjub_schnorr_amd", "tools", "ingest_stages.h")] + \
+            os.path.join(ROOT, "jubjub_schnorr_amd", "tools", "ingest_stages.h"),
+            os.path.join(ROOT, "jubjub_schnorr_amd", "tools", "fr_stages.h")] + \
         [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         # JJS_HOST_SANITIZE=1 python -m pytest tests/test_hostbuild.py  -> the same tests under UBSan
@@ -109,6 +110,16 @@ def ingest_records(words, out_words):
     out = np.empty(out_words, np.uint32)
     got = ctypes.c_size_t(0)
     rc = load().jjs_host_ingest_records(_p(words), ctypes.c_size_t(len(words)), _p(out), ctypes.c_size_t(out_words), ctypes.byref(got))
+    assert rc == 0 and got.value == out_words, (rc, got.value, out_words)
+    return out
+
+
+def fr_records(words, out_words):
+    """The records of tools/fr_stages.h through the product's functions on the CPU build: uint32 in, uint32 out."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    out = np.empty(out_words, np.uint32)
+    got = ctypes.c_size_t(0)
+    rc = load().jjs_host_fr_records(_p(words), ctypes.c_size_t(len(words)), _p(out), ctypes.c_size_t(out_words), ctypes.byref(got))
     assert rc == 0 and got.value == out_words, (rc, got.value, out_words)
     return out
 

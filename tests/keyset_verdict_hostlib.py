@@ -57,3 +57,24 @@ def key_sums(scheme, keys, idxs, cols, poison=True):
                                       _p(sums), _p(point))
     assert rc == 0
     return sums, point
+
+
+def items(scheme, keys, idx, b, seed, c, grids):
+    """The keyed item pass alone on the CPU build, as jjs_debug_keyset_items_dev copies it out on the device.  Returns a dict:
+    scalars, a (one column per point column of the set), partial ({blocks: the partial sums of a grid of that many blocks}),
+    fail, zu."""
+    keys = [np.ascontiguousarray(k, dtype=np.uint8) for k in keys]
+    idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    cols = [np.ascontiguousarray(b[k], dtype=np.uint8) if b.get(k) is not None else None for k in ("u", "R", "Rp", "m")]
+    n, nk, n_eq = len(idx), len(keys[0]), 2 if scheme == "double" else 1
+    scalars, partial, zu = np.zeros(n_eq * n * 32, np.uint8), np.zeros(sum(grids) * 64, np.uint8), np.zeros(64, np.uint8)
+    g = np.array(grids, np.uint32)
+    a = [np.zeros(n * 32, np.uint8) for _ in keys]
+    fail = ctypes.c_uint32(7)
+    rc = load().jjs_ksv_host_items(SCHEMES[scheme], _p(keys[0]), _p(keys[1]) if len(keys) > 1 else None, ctypes.c_uint32(nk), _p(idx),
+                                   *[_p(x) for x in cols], ctypes.c_size_t(n), seed, c, _p(g), ctypes.c_size_t(len(g)), _p(scalars), _p(a[0]),
+                                   _p(a[1]) if len(a) > 1 else None, _p(partial), ctypes.byref(fail), _p(zu))
+    assert rc == 0
+    ends = np.cumsum(g) * 64
+    return {"scalars": scalars.tobytes(), "a": [x.tobytes() for x in a], "partial": {int(k): partial[e - 64 * int(k):e].tobytes() for k, e in zip(g, ends)},
+            "fail": fail.value, "zu": zu.tobytes()}

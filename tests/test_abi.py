@@ -46,7 +46,8 @@ def test_product_library_has_no_bypass_switch():
     from jubjub_schnorr_amd import _ffi
     prof_syms = header_symbols("jjs_gpu_profiling.h")
     assert prof_syms == ["jjs_debug_allow_virtual_devices", "jjs_debug_fail_key_arena", "jjs_debug_force_path", "jjs_debug_host_timing",
-                         "jjs_debug_keyset_sums_dev", "jjs_debug_msm_dev", "jjs_debug_pin_hash_seed", "jjs_debug_skip_phases"] == sorted(_ffi.PROFILING_SIGNATURES)
+                         "jjs_debug_keyset_items_dev", "jjs_debug_keyset_sums_dev", "jjs_debug_msm_dev", "jjs_debug_pin_hash_seed",
+                         "jjs_debug_skip_phases", "jjs_debug_verdict_items_dev"] == sorted(_ffi.PROFILING_SIGNATURES)
     product = exported(os.path.join(ROOT, "jubjub_schnorr_amd", "libjjs_gpu.so"))
     for s in prof_syms:
         assert s not in product, s

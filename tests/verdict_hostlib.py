@@ -57,3 +57,23 @@ def verify_all(scheme, b, seed=bytes(32), c=0):
                                   _p(cols["m"]), ctypes.c_size_t(len(cols["u"])), seed, c, ctypes.byref(verdict))
     assert rc == 0
     return verdict.value
+
+
+def verdict_items(scheme, cols, seed, c, grids):
+    """The item pass of the batch verdict on the CPU build, as jjs_debug_verdict_items_dev copies it out on the device.  cols:
+    the six column slots (verdict_item_cases.batch_columns); grids: block counts.  Returns a dict: scalars, partial ({blocks: the
+    partial sums of a grid of that many blocks}), fail, zu."""
+    cols = [np.ascontiguousarray(x, np.uint8) if x is not None else None for x in cols]
+    n = len(cols[0])
+    u, r, rp, pk, second, m = (cols[0], cols[1], cols[2], cols[3], cols[4], cols[5]) if scheme == "double" else \
+        (cols[0], cols[1], None, cols[2], None, cols[3]) if scheme == "single" else (cols[0], cols[1], None, cols[2], cols[3], cols[4])
+    kinds = {"single": 2, "double": 4, "vargen": 3}[scheme]
+    scalars, partial, zu = np.zeros(kinds * n * 32, np.uint8), np.zeros(sum(grids) * 64, np.uint8), np.zeros(64, np.uint8)
+    fail = ctypes.c_uint32(7)
+    g = np.array(grids, np.uint32)
+    rc = load().jjs_vh_verdict_items(SCHEMES[scheme], _p(u), _p(r), _p(rp), _p(pk), _p(second), _p(m), ctypes.c_size_t(n), seed, c,
+                                     _p(g), ctypes.c_size_t(len(g)), _p(scalars), _p(partial), ctypes.byref(fail), _p(zu))
+    assert rc == 0
+    ends = np.cumsum(g) * 64
+    return {"scalars": scalars.tobytes(), "partial": {int(k): partial[e - 64 * int(k):e].tobytes() for k, e in zip(g, ends)}, "fail": fail.value,
+            "zu": zu.tobytes()}
