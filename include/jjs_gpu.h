@@ -205,7 +205,8 @@ int jjs_memory_stats(uint64_t out[JJS_MEMORY_STATS]);
  *   jjs_keyset_destroy(ks): the handle becomes stale (-1 from then on).  Launches already queued still read the set's
  *     device memory, which jjs_trim or jjs_shutdown frees; jjs_trim never frees a live set, jjs_shutdown frees every set.
  *   jjs_keyset_info(ks, out): JJS_KEYSET_* words below.
- * Memory per key on each device: 64 B + 1 B + 43 x 33 x 144 B = 204 KB per point column (twice that for double and var-gen).
+ * Memory per key on each device: 64 B + 1 B + 43 x 33 x 144 B = 204 KB per point column (twice that for double and var-gen),
+ * and at most 65 B for the lookup table of the by-key calls below.
  * Threading: every keyset call may come from any thread; the registry is read and changed under the engine's mutex, which
  * no keyset call holds while it waits for the device.
  * Return codes: -4 before jjs_init; -1 for an unknown or destroyed handle, a bad scheme or format, a NULL column the
@@ -227,6 +228,46 @@ int jjs_keyset_verify(jjs_keyset ks, int format, const uint32_t* key_idx, const 
                       const uint8_t* m, size_t n, uint8_t* status, uint64_t tally[4]);
 int jjs_keyset_verify_dev(jjs_keyset ks, int format, const void* key_idx, const void* s0, const void* s1, const void* s2,
                           const void* m, size_t n, void* status, void* tally, void* stream);
+
+/* ---- registered key sets by key ------------------------------------------------------------------
+ * The reference's `PublicKey::verify(&self, &Signature, BlsScalar)` arrives with a KEY, not an index.  Every set carries a
+ * lookup table over its keys (built with the set, on every driven device: at most 64 B per key), and these calls take the
+ * key columns of the inline call of the set's scheme in `format` where jjs_keyset_verify takes key_idx:
+ *   affine / extended: K0 = PK, K1 = PK' (double) or Gen (var-gen), n x 64 / n x 96; K1 = NULL for single;
+ *   wire:              K0 = the `pk` column of the _wire calls (n x 32, or n x 64 for the two-point schemes), K1 = NULL.
+ * A key is FOUND when it is the point (pair of points) registered at some index: an affine query by equality of its 64 (128)
+ * bytes with the set's canonical affine key, an extended one after normalisation (a point with U, V or Z >= q or Z = 0 is
+ * found nowhere), a wire one by equality of its encoding with that of a registered key that is on the curve -- the result
+ * of jjs_decompress_dev followed by the affine lookup.  Keys registered but not `is_valid` are found (their items get
+ * status 1, as inline); a key registered as malformed (key_status 3) has no canonical bytes and is never found.  A key
+ * registered at several indices is found at the LOWEST of them.
+ *   jjs_keyset_find(_dev)(ks, format, K0, K1, n, idx_out): idx_out[i] = the index of item i's key, or 0xFFFFFFFF.  These are
+ *     the indices jjs_keyset_verify*, jjs_keyset_verify_all* and the jjs_multisig_*_keyset* calls take: those calls have no
+ *     by-key form of their own.  _dev: device pointers (K0, K1 16-byte, idx_out 4-byte aligned), asynchronous on `stream`.
+ *   jjs_keyset_verify_keys_dev(ks, format, K0, K1, s0, s1, s2, m, n, status, tally, idx_out, stream): asynchronous; s0..s2, m,
+ *     alignment and return codes of jjs_keyset_verify_dev; idx_out nullable (as jjs_keyset_find_dev).  An item whose key is
+ *     found gets exactly the status of jjs_keyset_verify_dev with that index; one whose key is not gets
+ *     JJS_STATUS_KEY_NOT_IN_SET and is counted in NO tally word (tally[0..3] sum to n minus the misses); no lane addresses
+ *     the set for it.  The call counts under JJS_KEYSET_SMALL_CALLS / JJS_KEYSET_LARGE_CALLS as the by-index call does.
+ *   jjs_keyset_verify_keys(...): from HOST buffers, blocking, on the route of jjs_keyset_verify (and with its cost against
+ *     the inline host calls, see above).  A drop-in for the inline host call: status and tally are byte for byte those of
+ *     jjs_verify_{single,double,vargen}{,_ext,_wire} on the same columns, for every item, whatever the set holds -- the items
+ *     whose key is not in the set are gathered on the host and verified by that inline call once the by-key call has left
+ *     the device's host-call lock.  idx_out (nullable) tells which items were found.  When every key is registered there is
+ *     one device round trip and no inline call.
+ * Cost: the by-index call plus the probe, one lane per item (and the normalisation of the key columns for extended keys).
+ * Measured resident, by key against inline (profiles/r13_keyset_by_key.jsonl): 2^17 single signatures over
+ * 2^15 keys 0.55x (affine), 0.60x (ext), 0.56x (wire); calls of 1 .. 16 384 items 0.80-0.94x single, 0.64-0.97x double,
+ * 0.55-0.88x var-gen; against the by-index call a small call takes 2-10 us longer (two more launches).  2^20 items over
+ * 4 096 keys LOSES to inline, 1.01x (inside the spread), as the by-index call does: the keys repeat within that call.
+ * n == 0, stale handles, a NULL column the format needs and -4 before jjs_init: as jjs_keyset_verify(_dev). */
+#define JJS_STATUS_KEY_NOT_IN_SET 6
+int jjs_keyset_find_dev(jjs_keyset ks, int format, const void* K0, const void* K1, size_t n, void* idx_out, void* stream);
+int jjs_keyset_find(jjs_keyset ks, int format, const uint8_t* K0, const uint8_t* K1, size_t n, uint32_t* idx_out);
+int jjs_keyset_verify_keys_dev(jjs_keyset ks, int format, const void* K0, const void* K1, const void* s0, const void* s1,
+                               const void* s2, const void* m, size_t n, void* status, void* tally, void* idx_out, void* stream);
+int jjs_keyset_verify_keys(jjs_keyset ks, int format, const uint8_t* K0, const uint8_t* K1, const uint8_t* s0, const uint8_t* s1,
+                           const uint8_t* s2, const uint8_t* m, size_t n, uint8_t* status, uint64_t tally[4], uint32_t* idx_out);
 
 /* ---- one verdict per batch: randomized batch verification -------------------------------------
  * Affine columns in the layouts of jjs_verify_*.  The verdict is 1 (accepted) or 0.

@@ -360,6 +360,41 @@ class KeySet {
         int rc = jjs_keyset_verify(handle_, format, key_idx, s0, s1, s2, m, n, status, tally);
         if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_verify");
     }
+    // BY KEY (jjs_keyset_find, jjs_keyset_verify_keys): K0, K1 are the key columns of the inline call of the set's scheme in
+    // `format`.  find: idx_out[i] = the index of item i's key, or 0xFFFFFFFF -- what verify(), verify_all() and the multisig_*
+    // calls take as key_idx.  verify_keys: status and tally of the inline call on the same columns, whatever the set holds (items
+    // whose key is not registered are verified inline); idx_out (nullable) tells which were found.  Host buffers, blocking.
+    void find(int format, const uint8_t* K0, const uint8_t* K1, size_t n, uint32_t* idx_out) const {
+        int rc = jjs_keyset_find(handle_, format, K0, K1, n, idx_out);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_find");
+    }
+    void verify_keys(int format, const uint8_t* K0, const uint8_t* K1, const uint8_t* s0, const uint8_t* s1, const uint8_t* s2,
+                     const uint8_t* m, size_t n, uint8_t* status, uint64_t tally[4] = nullptr, uint32_t* idx_out = nullptr) const {
+        int rc = jjs_keyset_verify_keys(handle_, format, K0, K1, s0, s1, s2, m, n, status, tally, idx_out);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_verify_keys");
+    }
+    // `PublicKey::verify(&self, &Signature, BlsScalar)` in its batch form against a set of PublicKey: the results of
+    // PublicKey::verify_batch(items), with the registered keys' tables where an item's key is in the set
+    std::vector<VerifyResult> verify(const std::vector<PublicKey::Item>& items, uint64_t tally[4] = nullptr) const {
+        if (scheme_ != JJS_SCHEME_SINGLE) throw std::invalid_argument("PublicKey items need a key set of PublicKey");
+        const size_t n = items.size();
+        detail::Soa u(n, 32), r(n, 64), pk(n, 64), m(n, 32);
+        for (size_t i = 0; i < n; ++i) {
+            u.put(i, 0, items[i].sig.u); r.put(i, 0, items[i].sig.R);
+            pk.put(i, 0, items[i].pk); m.put(i, 0, items[i].message);
+        }
+        std::vector<uint8_t> status(n);
+        verify_keys(JJS_FORMAT_AFFINE, pk.data(), nullptr, u.data(), r.data(), nullptr, m.data(), n, status.data(), tally);
+        return detail::results(status);
+    }
+    // the index of every key in the set (0xFFFFFFFF: not registered)
+    std::vector<uint32_t> find(const std::vector<PublicKey>& keys) const {
+        if (scheme_ != JJS_SCHEME_SINGLE) throw std::invalid_argument("PublicKey queries need a key set of PublicKey");
+        std::vector<uint32_t> idx(keys.size());
+        const detail::Soa c = column(keys, [](const PublicKey& k) { return k.as_ref(); });
+        find(JJS_FORMAT_AFFINE, c.data(), nullptr, keys.size(), idx.data());
+        return idx;
+    }
     // one verdict for the batch (jjs_keyset_verify_all): true when every item verifies; `status` (nullable, n bytes) holds
     // the statuses of verify() when the verdict is false and is all zero otherwise
     bool verify_all(int format, const uint32_t* key_idx, const uint8_t* s0, const uint8_t* s1, const uint8_t* s2, const uint8_t* m, size_t n,

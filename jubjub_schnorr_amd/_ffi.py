@@ -71,6 +71,10 @@ SIGNATURES = {
     "jjs_keyset_info": [ctypes.c_uint64, _P],
     "jjs_keyset_verify": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_keyset_verify_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P],
+    "jjs_keyset_find_dev": [ctypes.c_uint64, _I, _P, _P, _Z, _P, _P],
+    "jjs_keyset_find": [ctypes.c_uint64, _I, _P, _P, _Z, _P],
+    "jjs_keyset_verify_keys_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P],
+    "jjs_keyset_verify_keys": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _P],
     "jjs_keyset_verify_all": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_keyset_verify_all_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_msig_group_create": [_P, _Z, _P],

@@ -617,8 +617,9 @@ class PublicKeyVarGen:
 # registered key sets (include/jjs_gpu.h jjs_keyset_*)
 # ------------------------------------------------------------------------------------------------
 class KeySet:
-    """Keys registered once, verified against by index (`Engine.keyset`).  `key_status[k]`: 0 valid, 1 not `is_valid`,
-    3 malformed.  Usable as a context manager; `close()` destroys the set (queued device calls still complete)."""
+    """Keys registered once, verified against by index (`verify`) or by key (`find`, `verify_keys`: the set looks the keys
+    up on the device) (`Engine.keyset`).  `key_status[k]`: 0 valid, 1 not `is_valid`, 3 malformed.  Usable as a context
+    manager; `close()` destroys the set (queued device calls still complete)."""
     INFO_NAMES = ("scheme", "keys", "valid_keys", "window_bits", "device_bytes", "small_calls", "large_calls")
     _SIG_WIDTHS = {  # (s0, s1, s2) per format; 0: the column is not used
         ("single", "affine"): (32, 64, 0), ("double", "affine"): (32, 64, 64), ("vargen", "affine"): (32, 64, 0),
@@ -713,6 +714,88 @@ class KeySet:
                                                status.ctypes.data_as(ctypes.c_void_p), tally.ctypes.data_as(ctypes.c_void_p)),
                    "jjs_keyset_verify")
         return status, tally
+
+    # ---- by key (include/jjs_gpu.h "registered key sets by key") ----------------------------------------------
+    NOT_IN_SET = 6                   # JJS_STATUS_KEY_NOT_IN_SET
+    MISS = 0xFFFFFFFF                # the index `find` reports for a key that is not in the set
+
+    def _key_cols(self, keys, fmt: str):
+        """The key columns of the inline call of the set's scheme in `fmt`, as (pointers K0, K1; n; torch?)."""
+        two = self.scheme != "single"
+        want = 1 if (fmt == "wire" or not two) else 2
+        if len(keys) != want:
+            raise ValueError(f"{self.scheme} {fmt} keys come in {want} column(s)")
+        w = (64 if two else 32) if fmt == "wire" else (96 if fmt == "ext" else 64)
+        on_dev = _is_torch(keys[0])
+        n = keys[0].shape[0]
+        if on_dev:
+            ptrs = [self._eng._dev_ptr(k, w, n) for k in keys]
+        else:
+            host = [self._eng._host(k, w) for k in keys]
+            if any(h.shape[0] != n for h in host):
+                raise ValueError("both key columns must have the same number of items")
+            ptrs = [h.ctypes.data_as(ctypes.c_void_p) for h in host]      # (each keeps its array alive)
+        return ptrs + [None] * (2 - len(ptrs)), n, on_dev
+
+    def find(self, *keys, fmt: str = "affine"):
+        """The index of every item's key in the set, or `KeySet.MISS`: `keys` are the key columns of the inline call of the
+        set's scheme in `fmt` -- affine / ext (PK[, PK' | Gen]), wire (pk).  Torch CUDA tensors run asynchronously on the
+        current stream and give an int32 tensor (a miss reads -1); numpy arrays block and give uint32."""
+        if self.handle == 0:
+            raise _ffi.JjsError("the key set is closed")
+        (k0, k1), n, on_dev = self._key_cols(keys, fmt)
+        fmt_id = Engine._FORMAT_IDS[fmt]
+        if on_dev:
+            import torch
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=keys[0].device)[:n]
+            _ffi.check(self._lib.jjs_keyset_find_dev(self.handle, fmt_id, k0, k1, n, ctypes.c_void_p(idx.data_ptr()), self._eng._stream()),
+                       "jjs_keyset_find_dev")
+            return idx
+        idx = np.empty(n, np.uint32)
+        _ffi.check(self._lib.jjs_keyset_find(self.handle, fmt_id, k0, k1, n, idx.ctypes.data_as(ctypes.c_void_p)), "jjs_keyset_find")
+        return idx
+
+    def verify_keys(self, keys, *cols, fmt: str = "affine", want_status: bool = True, want_idx: bool = False):
+        """Verify against the set BY KEY: `keys` is the tuple of key columns `find` takes, then the signature columns and the
+        messages of `verify`.  Torch CUDA tensors: asynchronous; an item whose key is not in the set gets status
+        `KeySet.NOT_IN_SET` and is counted in no tally word.  numpy arrays: blocking, and a drop-in for the inline call --
+        such items are verified inline, status and tally are those of `Engine.verify` / `verify_ext` / `verify_wire` on the
+        same columns.  Returns (status, tally), and the found indices as a third value with `want_idx`."""
+        if self.handle == 0:
+            raise _ffi.JjsError("the key set is closed")
+        if not isinstance(keys, (tuple, list)):
+            keys = (keys,)
+        (k0, k1), n, on_dev = self._key_cols(keys, fmt)
+        widths = [w for w in self._SIG_WIDTHS[(self.scheme, fmt)] if w] + [32]
+        if len(cols) != len(widths):
+            raise ValueError(f"{self.scheme} {fmt} keyset verify takes {len(widths)} columns after the keys")
+        fmt_id = Engine._FORMAT_IDS[fmt]
+        slots = [None, None, None, None]          # s0, s1, s2, m
+        positions = [0, 1, 2][:len(widths) - 1] + [3]
+        if on_dev:
+            import torch
+            dev = keys[0].device
+            for pos, c, w in zip(positions, cols, widths):
+                slots[pos] = self._eng._dev_ptr(c, w, n)
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[:n] if want_status else None
+            tally = torch.empty(4, dtype=torch.int64, device=dev)
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n] if want_idx else None
+            _ffi.check(self._lib.jjs_keyset_verify_keys_dev(self.handle, fmt_id, k0, k1, *slots, n,
+                                                            ctypes.c_void_p(status.data_ptr()) if want_status and n else None,
+                                                            ctypes.c_void_p(tally.data_ptr()),
+                                                            ctypes.c_void_p(idx.data_ptr()) if want_idx and n else None, self._eng._stream()),
+                       "jjs_keyset_verify_keys_dev")
+            return (status, tally, idx) if want_idx else (status, tally)
+        host = [self._eng._host(c, w) for c, w in zip(cols, widths)]
+        if any(h.shape[0] != n for h in host):
+            raise ValueError("all columns must have the same number of items as the keys")
+        for pos, h in zip(positions, host):
+            slots[pos] = h.ctypes.data_as(ctypes.c_void_p)
+        status, tally, idx = np.empty(n, np.uint8), np.zeros(4, np.uint64), np.empty(n, np.uint32)
+        _ffi.check(self._lib.jjs_keyset_verify_keys(self.handle, fmt_id, k0, k1, *slots, n, status.ctypes.data_as(ctypes.c_void_p),
+                                                    tally.ctypes.data_as(ctypes.c_void_p),
+                                                    idx.ctypes.data_as(ctypes.c_void_p) if want_idx else None), "jjs_keyset_verify_keys")
+        return (status, tally, idx) if want_idx else (status, tally)
 
     def verify_all_batch(self, items: Sequence[tuple]) -> bool:
         """items: as for `verify_batch`.  True when every item verifies (one verdict: jjs_keyset_verify_all)."""

@@ -701,6 +701,42 @@ __global__ __launch_bounds__(BLOCK) void keyset_flags_kernel(uint8_t* flags0, ui
     flags0[id] |= (uint8_t)KT_KEY_MALFORMED;
     if (flags1) flags1[id] |= (uint8_t)KT_KEY_MALFORMED;
 }
+// The lookup table of a set (keyset_lookup.h): one lane per key enters it at registration (the slots arrive as KL_EMPTY) ...
+__global__ __launch_bounds__(BLOCK) void keyset_lookup_insert_kernel(keyset_lookup T) {
+    const uint32_t id = blockIdx.x * BLOCK + threadIdx.x;
+    if (id < T.n_keys) kl_insert(T, id);
+}
+// ... and one lane per item probes it in a by-key call: the query's 16-byte loads, then the gather of the candidates' 64-byte
+// rows, which L2 serves; no LDS.  `found` feeds the index pass, `idx_out` (nullable) is the caller's copy.
+struct keyset_probe_params {
+    keyset_lookup T;
+    const uint8_t* K[2];      // the query's key column(s): affine n x 64 each, or wire n x 32 / n x 64 in K[0]
+    uint32_t wire;
+    uint64_t n;
+    uint32_t* found;          // nullable
+    uint32_t* idx_out;        // nullable
+};
+__global__ __launch_bounds__(BLOCK) void keyset_probe_kernel(keyset_probe_params Q) {
+    const uint64_t item = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (item >= Q.n) return;
+    const uint32_t idx = kl_find_item(Q.T, Q.wire != 0, Q.K[0], Q.K[1], item);
+    if (Q.found) Q.found[item] = idx;
+    if (Q.idx_out) Q.idx_out[item] = idx;
+}
+// Behind a by-key call's last kernel: an item whose key missed ran with the stand-in of an index beyond the set; its status
+// becomes KL_STATUS_NOT_IN_SET and the tally word that counted it gives it back (one atomic per wave and status).
+__global__ __launch_bounds__(BLOCK) void keyset_miss_kernel(const uint32_t* found, uint64_t n, uint8_t* status, unsigned long long* tally) {
+    const uint64_t item = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    uint32_t st = 0;
+    const bool miss = item < n && kl_take_miss(found, item, status, &st);
+    if (!tally) return;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        const unsigned long long lanes = __ballot(miss && st == k);
+        if (lanes && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)lanes) - 1))
+            atomicAdd(&tally[k], 0ull - (unsigned long long)__popcll(lanes));
+    }
+}
 // Latency variant, phase A: the challenge hash of an item on eight adjacent lanes, in keyed mode (no half-size scalars, no
 // subgroup test of the key: the set has them), and in the blocks behind them the subgroup test of every R point on a lane
 // of its own (r_ok[2 item + j]), beside the hash instead of in a resolve pass behind the equations.  Whole groups of eight

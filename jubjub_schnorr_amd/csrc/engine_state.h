@@ -98,6 +98,7 @@ struct call_slot {
     grow_only<uint8_t> wire{{4096, WIRE_ITEM_BYTES, 0}};      // decoded / normalised points (4 x n x 64), flags, scratch: wire and ext entry points
     grow_only<uint8_t> small;         // latency path: window tables of the chain lanes + per-point verdicts (bytes)
     grow_only<uint8_t> verdict;       // batch verdict (verdict_calls.h): MSM terms, sort, buckets, or the per-item route's tally (bytes)
+    grow_only<uint32_t> found{{4096, sizeof(uint32_t), 0}};   // by-key calls against a key set (keyset_lookup.h): the index the probe found per item
     // key-table path (big and medium slots).  Two arenas, both grow-only: the index (hash tables, key ids, item order:
     // sized by the batch) and the pool of per-key bases and window tables, which is sized by the number of distinct keys
     // the slot's calls have carried -- KEY_POOL_INITIAL_BYTES to begin with, more once a call has shown that it needs more.
@@ -476,18 +477,22 @@ auto copy_for(const Entry& e, const device_state* d) -> decltype(&e.copies[0]) {
     return nullptr;
 }
 // A set's copy: its affine keys (64 B per point, the challenge hash reads them), the flags of its points, their window tables
-// (KEYSET_WINDOW bits) and three device words (n_keys, n_keys, the window width: the counters the grouping kernels read, and
+// (KEYSET_WINDOW bits), the lookup table of the by-key calls and three device words (n_keys, n_keys, the window width: the counters the grouping kernels read, and
 // the key-table flag of verify_params).
 struct keyset_copy : device_copy {
     uint8_t* keys[2] = {};                 // n_keys x 64 affine, per point column
     uint8_t* flags[2] = {};                // n_keys KT_KEY_* flags, per point column
     uint32_t* tables[2] = {};              // n_keys x kt_positions(w) x kt_table_words(w), per point column
     uint32_t* words = nullptr;             // [0], [1] n_keys, [2] the window width
+    uint32_t* lookup = nullptr;            // the lookup table (keyset_lookup.h): lookup_mask + 1 slots ...
+    uint32_t lookup_mask = 0;
+    uint8_t* on_curve = nullptr;           // ... and n_keys bytes: every point of the key is on the curve (what a wire query may hit)
 };
 struct keyset_entry : registered<keyset_copy> {
     int scheme = 0;
     uint32_t n_keys = 0, n_cols = 0, valid = 0;
     uint64_t small_calls = 0, large_calls = 0;
+    uint64_t lookup_seed = 0;              // of the lookup table's hash: one per set, the same on every device
 };
 struct msig_group_copy : device_copy {
     uint8_t* agg_pk = nullptr;             // 64 B affine

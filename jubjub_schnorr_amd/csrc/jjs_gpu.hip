@@ -61,6 +61,7 @@
 #include "small_batch.h"
 #include "key_tables.h"
 #include "keyset.h"
+#include "keyset_lookup.h"
 #include "sign_core.h"
 #include "multisig_core.h"
 #include "msig_group.h"
@@ -736,7 +737,7 @@ int jjs_memory_stats(uint64_t out[JJS_MEMORY_STATS]) {
     for (const call_slot& c : g->slots) {
         pool += c.key_pool.bytes() + c.key_memo.bytes();
         slots += c.pending.reported_bytes() + c.prep.reported_bytes() + c.wire.reported_bytes() + c.small.reported_bytes() + c.keys.reported_bytes() +
-                 c.verdict.reported_bytes();
+                 c.verdict.reported_bytes() + c.found.reported_bytes();
     }
     for (const host_lane& l : g->lanes) lanes += l.dev.reported_bytes() + l.pinned.reported_bytes();
     out[JJS_MEMORY_KEY_POOLS] = pool;

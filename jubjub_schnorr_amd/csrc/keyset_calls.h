@@ -77,6 +77,15 @@ static int build_device_copy(device_copy& c, size_t bytes, size_t tmp_bytes, con
 
 static uint32_t keyset_cols(int scheme) { return scheme == JJS_SCHEME_SINGLE ? 1u : 2u; }
 
+// the lookup table of a set's copy as its kernels take it
+static keyset_lookup keyset_lookup_of(const keyset_entry& k, const keyset_copy& c) {
+    keyset_lookup T{};
+    for (uint32_t i = 0; i < k.n_cols; ++i) { T.keys[i] = c.keys[i]; T.flags[i] = c.flags[i]; }
+    T.on_curve = c.on_curve; T.slots = c.lookup; T.mask = c.lookup_mask;
+    T.n_keys = k.n_keys; T.n_cols = k.n_cols; T.seed = k.lookup_seed;
+    return T;
+}
+
 // One device's copy of a set (g is that device): the keys uploaded and decoded / normalised into the copy, their flags, the
 // chains of bases (freed with the upload area) and the window tables of the valid keys -- the key-table path's own kernels
 // with a key_params whose "distinct keys" are the set's keys in order.  `flags_out` receives the flags of every point column.
@@ -86,6 +95,8 @@ static int keyset_build_copy(keyset_entry& k, keyset_copy& c, int format, const 
     const int w = KEYSET_WINDOW;
     const size_t key_bytes = pad256((size_t)n * 64), flag_bytes = pad256(n);
     const size_t table_bytes = (size_t)n * kt_positions(w) * kt_table_words(w) * 4;
+    const uint32_t lookup_slots = kl_slot_count(n);
+    const size_t lookup_bytes = pad256((size_t)lookup_slots * 4);
     // the build area: the uploaded encodings, the chains of bases, key_item, the valid-key lists, the malformed flags
     const size_t in_width = format == JJS_FORMAT_EXT ? 96 : (format == JJS_FORMAT_WIRE ? 32 : 0);
     const size_t in_bytes = pad256((size_t)n * in_width * cols), base_bytes = pad256((size_t)n * kt_positions(w) * KT_BASE_WORDS * 4);
@@ -96,7 +107,7 @@ static int keyset_build_copy(keyset_entry& k, keyset_copy& c, int format, const 
     for (uint32_t i = 0; i < n; ++i) host[i] = i;
     uint32_t words[64] = {n, n, (uint32_t)w};
     flags_out.assign((size_t)cols * n, 0);
-    return build_device_copy(c, 256 + cols * (key_bytes + flag_bytes + pad256(table_bytes)), tmp_bytes, "key set", s, [&](uint8_t* tmp) -> int {
+    return build_device_copy(c, 256 + cols * (key_bytes + flag_bytes + pad256(table_bytes)) + lookup_bytes + flag_bytes, tmp_bytes, "key set", s, [&](uint8_t* tmp) -> int {
         uint8_t* p = c.mem;
         c.words = reinterpret_cast<uint32_t*>(p); p += 256;
         for (uint32_t i = 0; i < cols; ++i) {
@@ -104,6 +115,9 @@ static int keyset_build_copy(keyset_entry& k, keyset_copy& c, int format, const 
             c.flags[i] = p; p += flag_bytes;
             c.tables[i] = reinterpret_cast<uint32_t*>(p); p += pad256(table_bytes);
         }
+        c.lookup = reinterpret_cast<uint32_t*>(p); p += lookup_bytes;
+        c.lookup_mask = lookup_slots - 1;
+        c.on_curve = p; p += flag_bytes;
         uint8_t* q = tmp;
         uint8_t* in = q; q += in_bytes;
         uint32_t* key_item = reinterpret_cast<uint32_t*>(q); q += item_bytes;
@@ -148,6 +162,9 @@ static int keyset_build_copy(keyset_entry& k, keyset_copy& c, int format, const 
         hipLaunchKernelGGL(keyset_flags_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, c.flags[0], cols > 1 ? c.flags[1] : nullptr,
                            (const uint8_t*)bad, n);
         hipLaunchKernelGGL(key_table_kernel, dim3((unsigned)(((uint64_t)cols * n * KT_MAX_POSITIONS + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, K);
+        // the lookup table of the by-key calls (keyset_lookup.h), behind the flags it reads: part of the set before it is published
+        HIP_TRY(hipMemsetAsync(c.lookup, 0xFF, (size_t)lookup_slots * 4, s));
+        hipLaunchKernelGGL(keyset_lookup_insert_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, keyset_lookup_of(k, c));
         HIP_TRY(hipGetLastError());
         for (uint32_t i = 0; i < cols; ++i)
             HIP_TRY(hipMemcpyAsync(flags_out.data() + (size_t)i * n, c.flags[i], n, hipMemcpyDeviceToHost, s));
@@ -208,13 +225,79 @@ static void keyset_front_launch(const keyset_front& F, bool sort, hipStream_t s)
     hipLaunchKernelGGL(key_scatter_kernel, dim3(item_blocks), dim3(BLOCK), 0, s, F.K);
 }
 
+// The key columns of a by-key call (jjs_keyset_find*, jjs_keyset_verify_keys*) in the call's format: affine or extended
+// K0, K1 (K1 null for a set of one point column), wire K0 alone.  Bytes per item of either column (0: not used):
+struct keyset_by_key {
+    const void *K0, *K1;
+    void* idx_out;            // nullable: the caller's copy of the indices
+};
+static void keyset_key_widths(uint32_t cols, int format, size_t w[2]) {
+    if (format == JJS_FORMAT_WIRE) { w[0] = 32 * cols; w[1] = 0; return; }
+    w[0] = format == JJS_FORMAT_EXT ? 96 : 64;
+    w[1] = cols > 1 ? w[0] : 0;
+}
+static int keyset_check_key_cols(uint32_t cols, int format, const void* K0, const void* K1, bool device) {
+    if (format < 0 || format > 2) return fail(JJS_ERR_ARG, "format out of range");
+    size_t w[2];
+    keyset_key_widths(cols, format, w);
+    if (!K0 || (device && !aligned16(K0))) return fail(JJS_ERR_ARG, "null or misaligned key column");
+    if (w[1] && (!K1 || (device && !aligned16(K1)))) return fail(JJS_ERR_ARG, "null or misaligned second key column");
+    return JJS_OK;
+}
+// The probe of n items on stream s: `found` and `idx_out` (either nullable) receive the index of every item's key or KL_MISS.
+// Extended keys are normalised first, into wire_pts(2) (3) of the call's slot (the caller has picked it, sized its wire area
+// and ordered the stream behind the slot's previous user), in poison mode: an unusable point (U, V or Z >= q, Z = 0) becomes
+// 64 bytes of 0xFF, which no entered key has.
+static int keyset_probe_launch(const keyset_entry& k, const keyset_copy& c, int format, const keyset_by_key& B, size_t n, uint32_t* found,
+                               hipStream_t s) {
+    keyset_probe_params Q{};
+    Q.T = keyset_lookup_of(k, c);
+    Q.K[0] = (const uint8_t*)B.K0; Q.K[1] = (const uint8_t*)B.K1;
+    Q.wire = format == JJS_FORMAT_WIRE ? 1u : 0u;
+    Q.n = n; Q.found = found; Q.idx_out = (uint32_t*)B.idx_out;
+    if (format == JJS_FORMAT_EXT) {
+        normalize_params N{};
+        N.n_src = k.n_cols; N.poison = 1;
+        N.src[0] = fe_src{(const uint8_t*)B.K0, 96, 0}; N.out[0] = wire_pts(2);
+        N.src[1] = fe_src{(const uint8_t*)B.K1, 96, 0}; N.out[1] = wire_pts(3);
+        N.scratch = wire_scratch(1);
+        if (int rc = launch_normalize(N, 0, n, n, s)) return rc;
+        Q.K[0] = wire_pts(2); Q.K[1] = wire_pts(3);
+    }
+    hipLaunchKernelGGL(keyset_probe_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, Q);
+    HIP_TRY(hipGetLastError());
+    return JJS_OK;
+}
+// jjs_keyset_find_dev's launches (g is c's device): only extended keys need a slot.
+static int keyset_find_launch(const keyset_entry& k, const keyset_copy& c, int format, const keyset_by_key& B, size_t n, hipStream_t s) {
+    if (format != JJS_FORMAT_EXT) return keyset_probe_launch(k, c, format, B, n, nullptr, s);
+    pick_slot(n, s);
+    if (int rc = sl->wire.ensure(n)) return rc;
+    if (int rc = begin_shared(s)) return rc;
+    if (int rc = keyset_probe_launch(k, c, format, B, n, nullptr, s)) return rc;
+    return end_shared(s);
+}
+
 // The launches of one call against a set's copy `c` on stream s (g is c's device).  d = key_idx, s0, s1, s2, m (device).
+// A by-key call (B non-null; d[0] is not read) probes the set's lookup table for its indices in front of the index pass, which
+// runs a miss as it runs an index beyond the set -- with a stand-in, so that no lane addresses the set for it -- and turns
+// the status of every miss into KL_STATUS_NOT_IN_SET behind the last kernel (keyset_miss_kernel).
 static int keyset_launch(keyset_entry& k, const keyset_copy& c, int format, const void* const* d, size_t n, void* status, void* tally,
-                         hipStream_t s) {
+                         hipStream_t s, const keyset_by_key* B = nullptr) {
     const int scheme = k.scheme;
     const bool small = n <= KEYSET_SMALL_MAX_ITEMS;
     keyset_front F;
     if (int rc = keyset_front_end(k, c, d[0], n, !small, s, F)) return rc;
+    if (B) {
+        if (int rc = sl->found.ensure(n)) return rc;
+        F.X.key_idx = sl->found;
+    }
+    const auto finish = [&]() -> int {
+        if (B) hipLaunchKernelGGL(keyset_miss_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const uint32_t*)sl->found.get(),
+                                  (uint64_t)n, (uint8_t*)status, (unsigned long long*)tally);
+        HIP_TRY(hipGetLastError());
+        return end_shared(s);
+    };
     const key_params& K = F.K;
     if (int rc = sl->prep.ensure(n)) return rc;
     if (int rc = sl->pending.ensure(n)) return rc;
@@ -258,6 +341,8 @@ static int keyset_launch(keyset_entry& k, const keyset_copy& c, int format, cons
             hipLaunchKernelGGL(decode_kernel, dim3((unsigned)grid_for(8192, n)), dim3(BLOCK), 0, s, D);
         }
     }
+    if (B)
+        if (int rc = keyset_probe_launch(k, c, format, *B, n, sl->found, s)) return rc;
     keyset_front_launch(F, !small, s);
     if (small) {
         ++k.small_calls;
@@ -267,16 +352,14 @@ static int keyset_launch(keyset_entry& k, const keyset_copy& c, int format, cons
         const uint32_t positions = ks_small_positions(n);
         hipLaunchKernelGGL(keyset_small_b_kernel, dim3((unsigned)((n * positions * P.n_eq + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, P, K,
                            positions, (const uint8_t*)sl->small);
-        HIP_TRY(hipGetLastError());
-        return end_shared(s);                  // nothing is left to the resolve pass
+        return finish();                       // nothing is left to the resolve pass
     } else {
         ++k.large_calls;
         hipLaunchKernelGGL(prepare_kernel, dim3(grid_for(g->grid_prepare, n)), dim3(BLOCK), 0, s, P, (int)PREP_ALL, (uint64_t)0, (uint64_t)n);
         hipLaunchKernelGGL(key_verify_kernel, dim3(grid_for(g->grid_key_verify, n)), dim3(BLOCK), 0, s, P, K);
     }
     hipLaunchKernelGGL(resolve_kernel, dim3(grid_for(g->grid_resolve, n * P.resolve_lanes_keyed)), dim3(BLOCK), 0, s, P);
-    HIP_TRY(hipGetLastError());
-    return end_shared(s);
+    return finish();
 }
 
 // bytes per item of the signature columns s0, s1, s2 of a call (0: the column is not used)
@@ -288,12 +371,13 @@ static void keyset_sig_widths(int scheme, int format, size_t w[3]) {
     w[2] = dbl ? w[1] : 0;
 }
 static int keyset_check_cols(int scheme, int format, const void* key_idx, const void* s0, const void* s1, const void* s2, const void* m,
-                             bool device) {
+                             bool device, bool by_key = false) {
     if (format < 0 || format > 2) return fail(JJS_ERR_ARG, "format out of range");
     size_t w[3];
     keyset_sig_widths(scheme, format, w);
     const void* cols[3] = {s0, s1, s2};
-    if (!key_idx || !m || (device && ((reinterpret_cast<uintptr_t>(key_idx) & 3u) || !aligned16(m))))
+    // (a by-key call has no index column: its key columns are keyset_check_key_cols')
+    if ((!by_key && !key_idx) || !m || (device && ((!by_key && (reinterpret_cast<uintptr_t>(key_idx) & 3u)) || !aligned16(m))))
         return fail(JJS_ERR_ARG, "null or misaligned key index or message column");
     for (int i = 0; i < 3; ++i)
         if (w[i] && (!cols[i] || (device && !aligned16(cols[i])))) return fail(JJS_ERR_ARG, "null or misaligned signature column %d", i);
@@ -309,12 +393,12 @@ extern "C++" {
 // used) copied from src[i] on the key-set stream s, then output areas of out_bytes[j] bytes, each part padded to 256 bytes.
 struct keyset_stage {
     const void* d[6];
-    uint8_t* out[2];
+    uint8_t* out[3];
     hipStream_t s;
 };
 static int keyset_stage_in(device_state* dev, const size_t* widths, const void* const* src, size_t cols, size_t n, const size_t* out_bytes,
                            size_t outs, keyset_stage& S) {
-    size_t off[8], total = 0;
+    size_t off[9], total = 0;
     for (size_t i = 0; i < cols; ++i) { off[i] = total; total += pad256(widths[i] * n); }
     for (size_t j = 0; j < outs; ++j) { off[cols + j] = total; total += pad256(out_bytes[j]); }
     if (int rc = dev->ks_stage.ensure(total)) return rc;
@@ -361,6 +445,10 @@ int jjs_keyset_create(int scheme, int format, const uint8_t* keys, const uint8_t
     keyset_entry& k = *call.e;
     const uint32_t cols = keyset_cols(scheme);
     k.scheme = scheme; k.n_keys = (uint32_t)n_keys; k.n_cols = cols;
+    k.lookup_seed = next_seed();
+#if defined(JJS_PROFILING)
+    if (g_pin_hash_seed) k.lookup_seed = 0;
+#endif
     std::vector<uint8_t> flags;            // of the first copy: every device computes the same
     if (int rc = call.build([&](keyset_copy& c, hipStream_t s) {
             std::vector<uint8_t> f;
@@ -466,6 +554,190 @@ int jjs_keyset_verify(jjs_keyset ks, int format, const uint32_t* key_idx, const 
         if (tally) for (int i = 0; i < 4; ++i) tally[i] = t[i];
         return JJS_OK;
     });
+}
+
+// ---- by key (keyset_lookup.h): the key columns of the inline calls in place of the indices --------------------------------
+
+int jjs_keyset_find_dev(jjs_keyset ks, int format, const void* K0, const void* K1, size_t n, void* idx_out, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    keyset_entry* k = g_keysets.find(ks);
+    if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
+    if (n == 0) return format < 0 || format > 2 ? fail(JJS_ERR_ARG, "format out of range") : (int)JJS_OK;
+    if (int rc = keyset_check_key_cols(k->n_cols, format, K0, K1, true)) return rc;
+    if (!idx_out || (reinterpret_cast<uintptr_t>(idx_out) & 3u)) return fail(JJS_ERR_ARG, "null or misaligned index output");
+    const keyset_copy* c = copy_for(*k, g);
+    if (!c) return fail(JJS_ERR_ARG, "the key set has no copy on this device");
+    const keyset_by_key B{K0, K1, idx_out};
+    return no_throw([&] { return keyset_find_launch(*k, *c, format, B, n, (hipStream_t)stream); });
+}
+
+// From host buffers, blocking: the route of jjs_keyset_verify (the device's keyset staging area and stream, under host_mu).
+int jjs_keyset_find(jjs_keyset ks, int format, const uint8_t* K0, const uint8_t* K1, size_t n, uint32_t* idx_out) {
+    device_state* dev = nullptr;
+    uint32_t cols = 0;
+    {
+        std::lock_guard<std::mutex> lock(L.mu);
+        if (int rc = check_ready()) return rc;
+        keyset_entry* k = g_keysets.find(ks);
+        if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
+        if (format < 0 || format > 2) return fail(JJS_ERR_ARG, "format out of range");
+        if (n == 0) return JJS_OK;
+        if (int rc = keyset_check_key_cols(k->n_cols, format, K0, K1, false)) return rc;
+        if (!idx_out) return fail(JJS_ERR_ARG, "null index output");
+        cols = k->n_cols;
+        dev = g;
+        ++g_blocking_calls;
+    }
+    blocking_call_leave leave_on_every_way_out;
+    std::lock_guard<std::mutex> big(dev->host_mu);
+    g = dev;
+    return no_throw([&]() -> int {
+        size_t kw[2];
+        keyset_key_widths(cols, format, kw);
+        const size_t out_bytes[1] = {n * 4};
+        const void* src[2] = {K0, K1};
+        keyset_stage S{};
+        if (int rc = keyset_stage_in(dev, kw, src, 2, n, out_bytes, 1, S)) return rc;
+        if (int rc = keyset_launch_locked(dev, &ks, [&](keyset_entry* k, const keyset_copy* c) {
+                return keyset_find_launch(*k, *c, format, keyset_by_key{S.d[0], S.d[1], S.out[0]}, n, S.s);
+            }))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(idx_out, S.out[0], n * 4, hipMemcpyDeviceToHost, S.s));
+        HIP_TRY(hipStreamSynchronize(S.s));
+        return JJS_OK;
+    });
+}
+
+int jjs_keyset_verify_keys_dev(jjs_keyset ks, int format, const void* K0, const void* K1, const void* s0, const void* s1, const void* s2,
+                               const void* m, size_t n, void* status, void* tally, void* idx_out, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    keyset_entry* k = g_keysets.find(ks);
+    if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
+    hipStream_t s = (hipStream_t)stream;
+    if (status && !aligned16(status)) return fail(JJS_ERR_ARG, "status must be 16-byte aligned");
+    if (n == 0) {
+        if (format < 0 || format > 2) return fail(JJS_ERR_ARG, "format out of range");
+        if (tally) HIP_TRY(hipMemsetAsync(tally, 0, 4 * sizeof(unsigned long long), s));
+        return JJS_OK;
+    }
+    if (int rc = keyset_check_cols(k->scheme, format, nullptr, s0, s1, s2, m, true, true)) return rc;
+    if (int rc = keyset_check_key_cols(k->n_cols, format, K0, K1, true)) return rc;
+    if (reinterpret_cast<uintptr_t>(idx_out) & 3u) return fail(JJS_ERR_ARG, "misaligned index output");
+    const keyset_copy* c = copy_for(*k, g);
+    if (!c) return fail(JJS_ERR_ARG, "the key set has no copy on this device");
+    const void* d[] = {nullptr, s0, s1, s2, m};
+    const keyset_by_key B{K0, K1, idx_out};
+    return no_throw([&] { return keyset_launch(*k, *c, format, d, n, status, tally, s, &B); });
+}
+
+}  // extern "C"
+
+// The inline host entry point of a scheme and format over the columns of a by-key call: col = K0, K1, s0, s1, s2, m.
+static int keyset_inline_host(int scheme, int format, const uint8_t* const* col, size_t n, uint8_t* status, uint64_t tally[4]) {
+    const uint8_t *K0 = col[0], *K1 = col[1], *s0 = col[2], *s1 = col[3], *s2 = col[4], *m = col[5];
+    if (format == JJS_FORMAT_WIRE)
+        return scheme == JJS_SCHEME_SINGLE ? jjs_verify_single_wire(s0, K0, m, n, status, tally)
+             : scheme == JJS_SCHEME_DOUBLE ? jjs_verify_double_wire(s0, K0, m, n, status, tally)
+                                           : jjs_verify_vargen_wire(s0, K0, m, n, status, tally);
+    if (format == JJS_FORMAT_EXT)
+        return scheme == JJS_SCHEME_SINGLE ? jjs_verify_single_ext(s0, s1, K0, m, n, status, tally)
+             : scheme == JJS_SCHEME_DOUBLE ? jjs_verify_double_ext(s0, s1, s2, K0, K1, m, n, status, tally)
+                                           : jjs_verify_vargen_ext(s0, s1, K0, K1, m, n, status, tally);
+    return scheme == JJS_SCHEME_SINGLE ? jjs_verify_single(s0, s1, K0, m, n, status, tally)
+         : scheme == JJS_SCHEME_DOUBLE ? jjs_verify_double(s0, s1, s2, K0, K1, m, n, status, tally)
+                                       : jjs_verify_vargen(s0, s1, K0, K1, m, n, status, tally);
+}
+// The items of a by-key host call whose key is not in the set (status KL_STATUS_NOT_IN_SET in st): their rows gathered, verified
+// by the inline host entry point, their statuses scattered back and their tally added.  Nothing runs when there is none.
+static int keyset_verify_misses_inline(int scheme, uint32_t cols, int format, const uint8_t* const* col, size_t n, uint8_t* st, uint64_t t[4]) {
+    std::vector<size_t> miss;
+    for (size_t i = 0; i < n; ++i)
+        if (st[i] == KL_STATUS_NOT_IN_SET) miss.push_back(i);
+    if (miss.empty()) return JJS_OK;
+    size_t w[6];
+    keyset_key_widths(cols, format, w);
+    keyset_sig_widths(scheme, format, w + 2);
+    w[5] = 32;
+    std::vector<uint8_t> rows[6], out(miss.size());
+    const uint8_t* p[6] = {};
+    for (int c = 0; c < 6; ++c) {
+        if (!w[c]) continue;
+        rows[c].resize(miss.size() * w[c]);
+        for (size_t j = 0; j < miss.size(); ++j) memcpy(rows[c].data() + j * w[c], col[c] + miss[j] * w[c], w[c]);
+        p[c] = rows[c].data();
+    }
+    uint64_t mt[4] = {};
+    if (int rc = keyset_inline_host(scheme, format, p, miss.size(), out.data(), mt)) return rc;
+    for (size_t j = 0; j < miss.size(); ++j) st[miss[j]] = out[j];
+    for (int i = 0; i < 4; ++i) t[i] += mt[i];
+    return JJS_OK;
+}
+
+extern "C" {
+
+// The drop-in of jjs_verify_{single,double,vargen}{,_ext,_wire}: the by-key call on the host route of jjs_keyset_verify, then --
+// only when a key was not in the set, and with host_mu released, because large inline host calls take it -- the inline call
+// over the missed rows.  Statuses and tally are those of the inline call over all n items.
+int jjs_keyset_verify_keys(jjs_keyset ks, int format, const uint8_t* K0, const uint8_t* K1, const uint8_t* s0, const uint8_t* s1,
+                           const uint8_t* s2, const uint8_t* m, size_t n, uint8_t* status, uint64_t tally[4], uint32_t* idx_out) {
+    device_state* dev = nullptr;
+    int scheme = 0;
+    uint32_t cols = 0;
+    {
+        std::lock_guard<std::mutex> lock(L.mu);
+        if (int rc = check_ready()) return rc;
+        keyset_entry* k = g_keysets.find(ks);
+        if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed key set");
+        if (format < 0 || format > 2) return fail(JJS_ERR_ARG, "format out of range");
+        if (n == 0) {
+            if (tally) for (int i = 0; i < 4; ++i) tally[i] = 0;
+            return JJS_OK;
+        }
+        if (int rc = keyset_check_cols(k->scheme, format, nullptr, s0, s1, s2, m, false, true)) return rc;
+        if (int rc = keyset_check_key_cols(k->n_cols, format, K0, K1, false)) return rc;
+        scheme = k->scheme; cols = k->n_cols;
+        dev = g;
+        ++g_blocking_calls;
+    }
+    std::vector<uint8_t> own;              // the statuses when the caller wants none: the misses are read from them
+    uint8_t* st = status;
+    uint64_t t[4] = {};
+    {
+        blocking_call_leave leave_on_every_way_out;
+        std::lock_guard<std::mutex> big(dev->host_mu);
+        g = dev;
+        const int rc = no_throw([&]() -> int {
+            if (!st) { own.resize(n); st = own.data(); }
+            size_t w[6];
+            keyset_key_widths(cols, format, w);
+            keyset_sig_widths(scheme, format, w + 2);
+            w[5] = 32;
+            const size_t out_bytes[3] = {n, 256, n * 4};      // outputs: statuses, tally, indices
+            const void* src[6] = {K0, K1, s0, s1, s2, m};
+            keyset_stage S{};
+            if (int rc = keyset_stage_in(dev, w, src, 6, n, out_bytes, 3, S)) return rc;
+            const void* d[] = {nullptr, S.d[2], S.d[3], S.d[4], S.d[5]};
+            const keyset_by_key B{S.d[0], S.d[1], S.out[2]};
+            if (int rc = keyset_launch_locked(dev, &ks, [&](keyset_entry* k, const keyset_copy* c) {
+                    return keyset_launch(*k, *c, format, d, n, S.out[0], S.out[1], S.s, &B);
+                }))
+                return rc;
+            HIP_TRY(hipMemcpyAsync(st, S.out[0], n, hipMemcpyDeviceToHost, S.s));
+            unsigned long long dt[4] = {};
+            HIP_TRY(hipMemcpyAsync(dt, S.out[1], sizeof(dt), hipMemcpyDeviceToHost, S.s));
+            if (idx_out) HIP_TRY(hipMemcpyAsync(idx_out, S.out[2], n * 4, hipMemcpyDeviceToHost, S.s));
+            HIP_TRY(hipStreamSynchronize(S.s));
+            for (int i = 0; i < 4; ++i) t[i] = dt[i];
+            return JJS_OK;
+        });
+        if (rc) return rc;
+    }
+    const uint8_t* col[6] = {K0, K1, s0, s1, s2, m};
+    if (int rc = no_throw([&] { return keyset_verify_misses_inline(scheme, cols, format, col, n, st, t); })) return rc;
+    if (tally) for (int i = 0; i < 4; ++i) tally[i] = t[i];
+    return JJS_OK;
 }
 
 }  // extern "C"
