@@ -577,6 +577,57 @@ int jjs_multisig_verify_keyset(jjs_keyset ks, int format, const uint32_t* key_id
                                const uint8_t* u, const uint8_t* R, const uint8_t* m, size_t n_transcripts,
                                uint8_t* agg_pk, uint8_t* status, uint64_t tally[4]);
 
+/* ---- multisignature: the signer's half (csrc/msig_sign.h; reference src/multisig.rs sign_round_1 :169-184, sign_round_2
+ * :213-257) ----
+ * GENERATORS OF TEST AND BENCHMARK MATERIAL, as jjs_sign_*: NOT constant time -- table look-ups and branches depend on sk, r
+ * and s.  Never use them with production keys.  A C ABI also cannot enforce the one-shot MultisigNonce of the reference
+ * (src/multisig.rs:131-141, consumed by sign_round_2): using a pair (r, s) in two calls, or in two rows, is the caller's error.
+ * jjs_multisig_round1_dev is sign_round_1 given the two RNG draws: R[i] = r[i] * G, S[i] = s[i] * G (n x 64 affine each; r, s
+ * n x 32).  bad_out (nullable, n bytes) is 1 where r[i] or s[i] is >= the group order, and both output rows are then zero.
+ * Device pointers, 16-byte aligned (bad_out none), asynchronous on `stream`.
+ * jjs_multisig_sign_dev is sign_round_2 over whole ragged batches.  The transcripts (PK, R, S, m, offsets_host,
+ * n_transcripts) are exactly what jjs_multisig_combine_dev takes, with its offsets rules, limits, alignment and asynchrony;
+ * `format` describes PK, R and S and is JJS_FORMAT_AFFINE or JJS_FORMAT_EXT (JJS_FORMAT_WIRE: -1).  Extended points are
+ * normalised in poison mode: an unusable point becomes 64 bytes of 0xFF and its transcript therefore gets status 3, the
+ * multisignature family's rule.  signer_row is n_signing x uint32 (4-byte aligned): the global row (over all transcripts) each
+ * signing row's share belongs to; NULL means n_signing == N and signing row j belongs to row j, the whole-transcript generator
+ * (NULL with n_signing != N: -1).  sk, r, s and z_out are n_signing x 32; sign_status is n_signing bytes and required.
+ * Row search.  sign_round_2 searches pk_vec for the signer's key; these calls are TOLD the row.  A wrong row gives status 5
+ * even when the key stands elsewhere in the transcript (include/jjs_schnorr.hpp and Engine.multisig_sign_round2's callers do
+ * the search on the host).
+ * sign_status[j], with i = signer_row[j] and t the transcript of row i -- the first rule that matches:
+ *   3  i >= N (nothing is addressed through i); sk[j], r[j] or s[j] >= the group order; or an encoding of transcript t is out
+ *      of range: a coordinate of any PK, R or S of the transcript >= q (every signing row of the transcript gets 3), m[t] >= q
+ *   5  (JJS_STATUS_INVALID_TRANSCRIPT) sk[j] * G != PK[i]; PK[i] stands at another row of the transcript as well ("occurs
+ *      exactly once", src/multisig.rs:223-231: both rows get 5); r[j] * G != R[i]; s[j] * G != S[i]
+ *   7  (JJS_STATUS_DUPLICATED_NONCE) two rows of transcript t hold the same R, or the same S (src/multisig.rs:238-246);
+ *      the same point in two DIFFERENT transcripts is not a duplicate
+ *   0  z_out[j] = r + s * a - (c * d_i) * sk mod the group order: byte for byte the reference's share
+ * This is the reference's order of checks with the encoding test in front, as everywhere in this ABI.  Equality of points is
+ * equality of their 64 canonical affine bytes.  For every status other than 0, z_out[j] is 32 zero bytes.
+ * n_transcripts == 0 or n_signing == 0 returns 0 and writes nothing.  -4 before jjs_init, -1 for a bad format, a NULL or
+ * misaligned pointer or unacceptable offsets.  Scratch is the grow-only multisignature scratch, enlarged by the flag words of
+ * the check pass (4 bytes per row, 136 per transcript); no call allocates per call.
+ * jjs_multisig_sign is the same from host buffers, blocking, on the route of jjs_multisig_combine: no alignment is asked of the
+ * pointers, one such call runs at a time per device, and the staged bytes of sk, r and s are cleared on the stream behind the
+ * share pass, before the call returns.
+ * Per transcript of n participants a call runs the five front passes of the combine call, a scan of n^2 / 2 byte compares
+ * spread over n lanes, and per signing row three fixed-base multiplications.  Rates (profiles/r14_msig_sign.jsonl, the record of
+ * tools/msig_sign_rate.py: one MI355X, resident inputs made on the device, signer_row = NULL, 7 rounds, medians; DESIGN.md
+ * 6.6): 0.85-0.99 of the time of jjs_multisig_combine_dev on the same transcripts -- 4.7 / 4.4 / 5.1 ms at B = 1, 64, 4 096
+ * transcripts of 8 participants (6.4 M shares/s at the last), 16 / 16 / 44 ms at 64, 58 / 70 / 465 ms at 256 (2.3 M shares/s);
+ * one transcript of 1 000 participants 224 ms, of whose kernel time the check pass is 0.3 %. */
+#define JJS_STATUS_DUPLICATED_NONCE 7
+int jjs_multisig_round1_dev(const void* r, const void* s, size_t n, void* R_out, void* S_out, void* bad_out, void* stream);
+int jjs_multisig_sign_dev(int format, const void* PK, const void* R, const void* S, const void* m,
+                          const uint32_t* offsets_host, size_t n_transcripts,
+                          const void* signer_row, const void* sk, const void* r, const void* s, size_t n_signing,
+                          void* z_out, void* sign_status, void* stream);
+int jjs_multisig_sign(int format, const uint8_t* PK, const uint8_t* R, const uint8_t* S, const uint8_t* m,
+                      const uint32_t* offsets, size_t n_transcripts,
+                      const uint32_t* signer_row, const uint8_t* sk, const uint8_t* r, const uint8_t* s, size_t n_signing,
+                      uint8_t* z_out, uint8_t* sign_status);
+
 /* ---- transcript parity (debug export): c_out = n x 32 bytes, the 250-bit challenge per item ---- */
 int jjs_challenge_single_dev(const void* R, const void* PK, const void* m, size_t n, void* c_out, void* stream);
 int jjs_challenge_double_dev(const void* R, const void* R_prime, const void* PK, const void* PK_prime, const void* m,

@@ -18,6 +18,7 @@
 #include <stdexcept>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "jjs_gpu.h"
@@ -31,13 +32,16 @@ using BlsScalar = Scalar;
 using JubJubScalar = Scalar;
 
 // reference src/error.rs:13-26 (the variants reachable from verify) + the engine's own failures
-enum class Error { InvalidSignature, InvalidPoint, BytesError, Engine };
+// (InvalidMultisigTranscript and DuplicatedNonce, src/error.rs:23-24 and :27, are what multisig::sign_round_2 answers)
+enum class Error { InvalidSignature, InvalidPoint, BytesError, Engine, InvalidMultisigTranscript, DuplicatedNonce };
 
 inline const char* to_string(Error e) {
     switch (e) {
     case Error::InvalidSignature: return "Invalid Signature";   // src/error.rs:40-42
     case Error::InvalidPoint: return "Invalid Point";           // src/error.rs:43-45
     case Error::BytesError: return "InvalidData";
+    case Error::InvalidMultisigTranscript: return "Invalid Multisig Transcript";
+    case Error::DuplicatedNonce: return "Duplicated Nonce";
     default: return "engine error";
     }
 }
@@ -504,6 +508,12 @@ struct CombineResult {
     std::optional<Signature> signature;      // present exactly when `error` is not
     std::optional<CombineError> error;
     explicit operator bool() const { return signature.has_value(); }
+    // the participant slot of the first failing share -- the index of Error::InvalidMultisigShare(index), src/error.rs:25, and of
+    // the engine's BytesError alike; nothing for a signature and for InvalidMultisigTranscript, which names no share
+    std::optional<size_t> first_failing_slot() const {
+        if (!error || error->kind == CombineError::InvalidMultisigTranscript) return std::nullopt;
+        return error->participant_index;
+    }
 };
 // `combine` (reference src/multisig.rs:326-360) of ONE transcript from the types the Rust side holds -- extended points pass
 // through as get_u / get_v / get_z bytes, nothing is inverted on the host -- through the blocking host form
@@ -587,6 +597,136 @@ inline VerifyResult verify(const std::vector<ExtendedPoint>& pk_vec, const Signa
     const VerifyResult r = verify_batch({VerifyItem{pk_vec, sig, msg}}, &a)[0];
     if (agg) *agg = a[0];
     return r;
+}
+
+// ---- the signer's half (reference src/multisig.rs sign_round_1 :169-184, sign_round_2 :213-257) ----
+// TEST AND BENCHMARK MATERIAL, as the engine's calls behind it (include/jjs_gpu.h jjs_multisig_sign): NOT constant time, here or
+// on the device -- never with production keys.  Nothing enforces the one-shot MultisigNonce of the reference (:131-141): using
+// a pair (r, s) twice is the caller's error.
+// The host arithmetic below (integers mod q, the curve's unified addition, k * G by double-and-add) exists for two things the C
+// ABI has no host form of: the two products of sign_round_1, and sk * G for the row search of sign_round_2.  It is slow
+// (a few milliseconds per product) and plain: bit-serial products, Fermat inversion.
+namespace host {
+struct U256 {
+    uint64_t w[4];
+};
+inline U256 from_bytes(const uint8_t* b) { U256 x; std::memcpy(x.w, b, 32); return x; }     // little-endian hosts, as the C ABI's columns
+inline const U256& modulus() {
+    static const U256 q{{0xFFFFFFFF00000001ull, 0x53BDA402FFFE5BFEull, 0x3339D80809A1D805ull, 0x73EDA753299D7D48ull}};
+    return q;
+}
+inline bool less(const U256& a, const U256& b) {
+    for (int i = 3; i >= 0; --i)
+        if (a.w[i] != b.w[i]) return a.w[i] < b.w[i];
+    return false;
+}
+inline bool equal(const U256& a, const U256& b) { return std::memcmp(a.w, b.w, 32) == 0; }
+inline U256 sub_raw(const U256& a, const U256& b) {
+    U256 r;
+    unsigned __int128 borrow = 0;
+    for (int i = 0; i < 4; ++i) {
+        const unsigned __int128 d = (unsigned __int128)a.w[i] - b.w[i] - (uint64_t)borrow;
+        r.w[i] = (uint64_t)d;
+        borrow = (d >> 64) & 1;
+    }
+    return r;
+}
+inline U256 add(const U256& a, const U256& b) {              // a, b < q < 2^255: the sum fits
+    U256 r;
+    unsigned __int128 carry = 0;
+    for (int i = 0; i < 4; ++i) {
+        carry += (unsigned __int128)a.w[i] + b.w[i];
+        r.w[i] = (uint64_t)carry;
+        carry >>= 64;
+    }
+    return less(r, modulus()) ? r : sub_raw(r, modulus());
+}
+inline U256 sub(const U256& a, const U256& b) { return less(a, b) ? sub_raw(modulus(), sub_raw(b, a)) : sub_raw(a, b); }
+inline U256 mul(const U256& a, const U256& b) {
+    U256 r{{0, 0, 0, 0}};
+    for (int bit = 255; bit >= 0; --bit) {
+        r = add(r, r);
+        if ((b.w[bit >> 6] >> (bit & 63)) & 1) r = add(r, a);
+    }
+    return r;
+}
+inline U256 small(uint64_t x) { return U256{{x, 0, 0, 0}}; }
+inline U256 inverse(const U256& a) {                         // a^(q - 2)
+    const U256 e = sub_raw(modulus(), small(2));
+    U256 r = small(1);
+    for (int bit = 255; bit >= 0; --bit) {
+        r = mul(r, r);
+        if ((e.w[bit >> 6] >> (bit & 63)) & 1) r = mul(r, a);
+    }
+    return r;
+}
+struct Point {
+    U256 x, y, z, t;
+};
+inline Point add(const Point& p, const Point& q) {          // -x^2 + y^2 = 1 + d x^2 y^2, d = -(10240 / 10241): complete
+    static const U256 d2 = [] { const U256 d = sub(small(0), mul(small(10240), inverse(small(10241)))); return add(d, d); }();
+    const U256 a = mul(sub(p.y, p.x), sub(q.y, q.x)), b = mul(add(p.y, p.x), add(q.y, q.x)), c = mul(mul(p.t, d2), q.t);
+    const U256 zz = mul(p.z, q.z), dd = add(zz, zz), e = sub(b, a), f = sub(dd, c), g = add(dd, c), h = add(b, a);
+    return Point{mul(e, f), mul(g, h), mul(f, g), mul(e, h)};
+}
+// k * G as affine canonical bytes, G the generator of the reference (dusk_jubjub::GENERATOR_EXTENDED); k: 32 bytes little-endian
+inline AffinePoint mul_generator(const Scalar& k) {
+    const U256 gx{{0x4DF7B7FFEC7BEACAull, 0x2E3EBB21FD6C54EDull, 0xF1FBF02D0FD6CCE6ull, 0x3FD2814C43AC65A6ull}}, gy = small(0x12);
+    const Point g{gx, gy, small(1), mul(gx, gy)};
+    Point acc{small(0), small(1), small(1), small(0)};
+    for (int bit = 255; bit >= 0; --bit) {
+        acc = add(acc, acc);
+        if ((k[bit >> 3] >> (bit & 7)) & 1) acc = add(acc, g);
+    }
+    const U256 zi = inverse(acc.z), u = mul(acc.x, zi), v = mul(acc.y, zi);
+    AffinePoint out;
+    std::memcpy(out.data(), u.w, 32);
+    std::memcpy(out.data() + 32, v.w, 32);
+    return out;
+}
+// the extended point (U, V, Z) is the affine point a: U = u Z and V = v Z with every coordinate canonical and Z != 0
+inline bool same_point(const ExtendedPoint& e, const AffinePoint& a) {
+    const U256 U = from_bytes(e.data()), V = from_bytes(e.data() + 32), Z = from_bytes(e.data() + 64);
+    if (!less(U, modulus()) || !less(V, modulus()) || !less(Z, modulus()) || equal(Z, small(0))) return false;
+    return equal(U, mul(from_bytes(a.data()), Z)) && equal(V, mul(from_bytes(a.data() + 32), Z));
+}
+}  // namespace host
+
+// `sign_round_1` given the two RNG draws: (R, S) = (r * G, s * G).  Host arithmetic; no engine call.
+inline std::pair<AffinePoint, AffinePoint> sign_round_1(const JubJubScalar& r, const JubJubScalar& s) {
+    return {host::mul_generator(r), host::mul_generator(s)};
+}
+struct SignResult {
+    std::optional<JubJubScalar> share;       // present exactly when `error` is not
+    std::optional<Error> error;              // InvalidMultisigTranscript, DuplicatedNonce, or BytesError (status 3: an encoding the Rust types cannot hold)
+    explicit operator bool() const { return share.has_value(); }
+};
+// `sign_round_2` of ONE transcript from the types the Rust side holds, through the blocking host form jjs_multisig_sign.  The
+// engine's call is told the signer's row; the reference searches pk_vec for the signer's key, and so does this function, on the
+// host: the rows of pk_vec that are the point sk * G.  None, or more than one ("occurs exactly once", :223-231), or vectors of
+// unequal length, or an empty transcript: InvalidMultisigTranscript, without a call.
+inline SignResult sign_round_2(const JubJubScalar& sk, const JubJubScalar& r, const JubJubScalar& s, const std::vector<ExtendedPoint>& pk_vec,
+                               const std::vector<ExtendedPoint>& R_vec, const std::vector<ExtendedPoint>& S_vec, const BlsScalar& msg) {
+    const size_t n = pk_vec.size();
+    if (n == 0 || R_vec.size() != n || S_vec.size() != n || n > 0xFFFFFFFFull) return SignResult{std::nullopt, Error::InvalidMultisigTranscript};
+    const AffinePoint mine = host::mul_generator(sk);
+    size_t found = 0;
+    uint32_t row = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (host::same_point(pk_vec[i], mine)) { row = (uint32_t)i; ++found; }
+    if (found != 1) return SignResult{std::nullopt, Error::InvalidMultisigTranscript};
+    const uint32_t offsets[2] = {0, (uint32_t)n};
+    JubJubScalar z{};
+    uint8_t status = 0;
+    const int rc = jjs_multisig_sign(JJS_FORMAT_EXT, pk_vec[0].data(), R_vec[0].data(), S_vec[0].data(), msg.data(), offsets, 1, &row, sk.data(),
+                                     r.data(), s.data(), 1, z.data(), &status);
+    if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_sign");
+    switch (status) {
+    case JJS_STATUS_OK: return SignResult{z, std::nullopt};
+    case JJS_STATUS_INVALID_TRANSCRIPT: return SignResult{std::nullopt, Error::InvalidMultisigTranscript};
+    case JJS_STATUS_DUPLICATED_NONCE: return SignResult{std::nullopt, Error::DuplicatedNonce};
+    default: return SignResult{std::nullopt, Error::BytesError};
+    }
 }
 
 }  // namespace multisig

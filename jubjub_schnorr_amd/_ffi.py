@@ -97,6 +97,9 @@ SIGNATURES = {
     "jjs_multisig_verify": [_I, _P, _P, _P, _P, _P, _Z, _P, _P, _P],
     "jjs_multisig_verify_keyset_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P],
     "jjs_multisig_verify_keyset": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P],
+    "jjs_multisig_round1_dev": [_P, _P, _Z, _P, _P, _P, _P],
+    "jjs_multisig_sign_dev": [_I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _Z, _P, _P, _P],
+    "jjs_multisig_sign": [_I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_single": [_P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_double": [_P, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_vargen": [_P, _P, _P, _P, _P, _Z, _P, _P],

@@ -412,6 +412,60 @@ class Engine:
                    "jjs_public_keys_dev")
         return (PK, PKp, bad) if double else (PK, bad)
 
+    def multisig_sign_round1(self, r, s):
+        """`sign_round_1` for a batch given the two RNG draws (reference src/multisig.rs:169-184): R = r*G, S = s*G.  torch CUDA
+        tensors (n, 32); NOT constant time.  Returns (R, S, bad): bad[i] = 1 where r[i] or s[i] is not a canonical
+        JubJubScalar, and both rows are then zero."""
+        import torch
+        n = r.shape[0]
+        new = lambda w: torch.empty((max(n, 1), w), dtype=torch.uint8, device=r.device)[:n]  # noqa: E731
+        R, S, bad = new(64), new(64), torch.empty(max(n, 1), dtype=torch.uint8, device=r.device)[:n]
+        o = lambda t: ctypes.c_void_p(t.data_ptr()) if n else None  # noqa: E731
+        _ffi.check(self._lib.jjs_multisig_round1_dev(self._dev_ptr(r, 32, n), self._dev_ptr(s, 32, n), n, o(R), o(S), o(bad), self._stream()),
+                   "jjs_multisig_round1_dev")
+        return R, S, bad
+
+    def multisig_sign_round2(self, PK, R, S, m, offsets, sk, r, s, signer_row=None, fmt: str = "affine"):
+        """`sign_round_2` over many transcripts (reference src/multisig.rs:213-257): a generator of test and benchmark material,
+        NOT constant time, and reusing a pair (r, s) is the caller's error.  The transcripts as `multisig_combine` takes them;
+        sk, r, s (k, 32) the secrets of the k signing rows; signer_row (k,) the global row each belongs to (None: k == N and
+        signing row j is row j).  torch CUDA tensors run asynchronously on the current stream (jjs_multisig_sign_dev), numpy
+        arrays block (jjs_multisig_sign).  Returns (z (k, 32), sign_status (k,)): 0, 3 malformed, 5 the transcript does not
+        hold this signer at this row exactly once, 7 a duplicated nonce; z is zero behind every status other than 0."""
+        w = self._msig_width(fmt)
+        fmt_id = self._FORMAT_IDS[fmt]
+        offs = np.ascontiguousarray(offsets, dtype=np.uint32)
+        B, N, k = len(offs) - 1, PK.shape[0], sk.shape[0]
+        if (B and int(offs[-1]) != N) or (signer_row is None and k != N) or (signer_row is not None and signer_row.shape[0] != k):
+            raise ValueError("the columns do not have the rows the offsets and the signing rows ask for")
+        po = offs.ctypes.data_as(ctypes.c_void_p)
+        if not _is_torch(PK):
+            hpk, hr, hs, hm = self._host(PK, w), self._host(R, w), self._host(S, w), self._host(m, 32)
+            hsk, hrr, hss = self._host(sk, 32), self._host(r, 32), self._host(s, 32)
+            if any(h.shape[0] != N for h in (hr, hs)) or hm.shape[0] != B or any(h.shape[0] != k for h in (hrr, hss)):
+                raise ValueError("the columns do not have the rows the offsets and the signing rows ask for")
+            rows = np.ascontiguousarray(signer_row, dtype=np.uint32) if signer_row is not None else None
+            z, status = np.zeros((k, 32), np.uint8), np.zeros(k, np.uint8)
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+            _ffi.check(self._lib.jjs_multisig_sign(fmt_id, p(hpk), p(hr), p(hs), p(hm), po, B, p(rows), p(hsk), p(hrr), p(hss), k, p(z),
+                                                   p(status)), "jjs_multisig_sign")
+            return z, status
+        import torch
+        dev_ = PK.device
+        rows = None
+        if signer_row is not None:
+            if not (signer_row.is_cuda and signer_row.is_contiguous() and signer_row.dim() == 1
+                    and signer_row.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+                raise ValueError("expected a contiguous 1-d CUDA tensor of int32 / uint32 rows, one per signing row")
+            rows = ctypes.c_void_p(signer_row.data_ptr())
+        z = torch.empty((max(k, 1), 32), dtype=torch.uint8, device=dev_)[:k]
+        status = torch.empty(max(k, 1), dtype=torch.uint8, device=dev_)[:k]
+        o = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        _ffi.check(self._lib.jjs_multisig_sign_dev(fmt_id, self._dev_ptr(PK, w, N), self._dev_ptr(R, w, N), self._dev_ptr(S, w, N),
+                                                   self._dev_ptr(m, 32, B), po, B, rows, self._dev_ptr(sk, 32, k), self._dev_ptr(r, 32, k),
+                                                   self._dev_ptr(s, 32, k), k, o(z), o(status), self._stream()), "jjs_multisig_sign_dev")
+        return z, status
+
     # ---- primitives for parity tests ------------------------------------------------------------
     def debug_fq_mul(self, a, b):
         import torch

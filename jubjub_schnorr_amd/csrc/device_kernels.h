@@ -856,3 +856,28 @@ __global__ __launch_bounds__(BLOCK) void msig_verify_clear_kernel(msig_verify_pa
     const uint64_t total = (uint64_t)gridDim.x * BLOCK;
     for (uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; t < V.M.n_transcripts; t += total) mv_clear_item(V, (uint32_t)t);
 }
+
+// ---- the signer's half of the multisignature scheme (msig_sign.h) ----------------------------------------
+// The check pass behind pass 0 (a lane per participant row), pass 4 without a column of shares (msig_kernel's lane rules: eight
+// lanes per transcript when the call has few), the share pass (a lane per signing row) and sign_round_1 (a lane per row):
+// grid-stride.  NOT constant time: generators of test and benchmark material, as sign_kernel.
+__global__ __launch_bounds__(BLOCK) void msig_sign_check_kernel(msig_sign_params S) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < S.M.n_total; i += total) ms_check_item(S, i);
+}
+__global__ __launch_bounds__(BLOCK) void msig_sign_final_kernel(msig_params P) {
+    const uint64_t gtid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    const uint32_t hl = P.hash_lanes;
+    const int coop = hl > 1 ? (int)(gtid % hl) : -1;
+    for (uint64_t t = gtid / hl; t < P.n_transcripts; t += total / hl) ms_final_item(P, (uint32_t)t, coop);
+}
+__global__ __launch_bounds__(BLOCK) void msig_sign_share_kernel(msig_sign_params S) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; j < S.n_signing; j += total) ms_share_item(S, j);
+}
+__global__ __launch_bounds__(BLOCK) void msig_round1_kernel(const uint8_t* r, const uint8_t* s, uint64_t n, const uint32_t* comb_g, uint8_t* R_out,
+                                                            uint8_t* S_out, uint8_t* bad) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += total) ms_round1_item(r, s, comb_g, i, R_out, S_out, bad);
+}

@@ -23,6 +23,7 @@
 //   msig_host_calls.h  the blocking host-buffer forms of the multisignature calls
 //   msig_keyset_calls.h  the multisignature call against a registered key set, both forms
 //   msig_verify_calls.h  the verifier's half: aggregate_pk, and aggregate_pk followed by the single-scheme verification
+//   msig_sign_calls.h  the signer's half: sign_round_1, and sign_round_2 over whole ragged batches (a generator of test material)
 //   host_lanes.h       the small ones (included among the entry points, behind the table of call shapes): staging lanes
 //                      outside the engine's mutex, calls of several threads in one launch
 //   (here)             the table of call shapes and the staged_call builder it drives; the extern "C" entry points
@@ -67,6 +68,7 @@
 #include "msig_group.h"
 #include "msig_keyset.h"
 #include "msig_verify.h"
+#include "msig_sign.h"
 #include "batch_verdict.h"
 #include "keyset_verdict.h"
 #include "jjs_sponge_tags_long.inc"
@@ -804,18 +806,24 @@ int jjs_compress_dev(const void* affine, size_t n, void* out, void* stream) {
 // rows; affine callers never pay for it): three columns of normalised points (64 bytes per row each) and the 9 words of prefix
 // product per row that normalize_lane keeps.  Behind those, once a key-set call (msig_keyset.h) has asked for it (g->msig_ks_rows
 // rows in g->msig_ks_transcripts transcripts; no other caller pays for it): the gathered key column (64 bytes per row), the
-// table index of every row (4) and the refused word of every transcript (4).
+// table index of every row (4) and the refused word of every transcript (4).  Behind those, once a signing call (msig_sign.h) has
+// asked for it (g->msig_sign_rows rows in g->msig_sign_transcripts transcripts; no other caller pays for it): the flag words of the
+// check pass -- pk_repeats (4) per row, bad_enc and dup_nonce (4 each) per transcript, one run of words that the call clears with
+// one memset -- and the two columns a signing call has no output for, pk_agg and RSa (64 bytes per transcript each).
 struct msig_scratch {
     uint32_t *tr_of, *d_words, *dpk, *e_pt, *a_words, *c_words, *offsets, *long_tags;
     uint8_t* norm[3];
     uint32_t* prefix;
     uint8_t* ks_pk;
     uint32_t *ks_row_key, *ks_refused;
+    uint32_t* sign_flags;                 // pk_repeats [rows], bad_enc [transcripts], dup_nonce [transcripts]
+    uint8_t *sign_agg, *sign_rsa;
 };
 constexpr size_t MSIG_EXT_ROW_BYTES = 3 * 64 + 9 * 4;
-static size_t msig_scratch_bytes(size_t items, size_t transcripts, size_t ext_rows, size_t ks_rows = 0, size_t ks_transcripts = 0) {
+static size_t msig_scratch_bytes(size_t items, size_t transcripts, size_t ext_rows, size_t ks_rows = 0, size_t ks_transcripts = 0,
+                                 size_t sign_rows = 0, size_t sign_transcripts = 0) {
     return items * 4 * (1 + 8 + 2 * EXT_WORDS) + transcripts * 4 * (16 + 1 + 18) + 64 + (ext_rows ? ext_rows * MSIG_EXT_ROW_BYTES + 64 : 0) +
-           (ks_rows ? ks_rows * (64 + 4) + ks_transcripts * 4 + 128 : 0);
+           (ks_rows ? ks_rows * (64 + 4) + ks_transcripts * 4 + 128 : 0) + (sign_rows ? sign_rows * 4 + sign_transcripts * (8 + 128) + 128 : 0);
 }
 static msig_scratch msig_scratch_carve() {
     msig_scratch W{};
@@ -839,12 +847,19 @@ static msig_scratch msig_scratch_carve() {
         W.ks_pk = q; q += 64 * g->msig_ks_rows;
         W.ks_row_key = reinterpret_cast<uint32_t*>(q);
         W.ks_refused = W.ks_row_key + g->msig_ks_rows;
+        w = W.ks_refused + g->msig_ks_transcripts;
+    }
+    if (g->msig_sign_rows) {
+        W.sign_flags = w; w += g->msig_sign_rows + 2 * g->msig_sign_transcripts;
+        W.sign_agg = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(w) + 63) & ~uintptr_t(63));
+        W.sign_rsa = W.sign_agg + 64 * g->msig_sign_transcripts;
     }
     return W;
 }
-static int ensure_msig_scratch(size_t n, size_t n_transcripts, size_t ext_rows = 0, size_t ks_rows = 0, size_t ks_transcripts = 0) {
+static int ensure_msig_scratch(size_t n, size_t n_transcripts, size_t ext_rows = 0, size_t ks_rows = 0, size_t ks_transcripts = 0,
+                               size_t sign_rows = 0, size_t sign_transcripts = 0) {
     if (n <= g->msig_items && n_transcripts <= g->msig_transcripts && ext_rows <= g->msig_ext_rows && ks_rows <= g->msig_ks_rows &&
-        ks_transcripts <= g->msig_ks_transcripts)
+        ks_transcripts <= g->msig_ks_transcripts && sign_rows <= g->msig_sign_rows && sign_transcripts <= g->msig_sign_transcripts)
         return JJS_OK;
     size_t ci = grown(n < 4096 ? 4096 : n), ct = grown(n_transcripts < 1024 ? 1024 : n_transcripts);
     size_t ce = ext_rows ? grown(ext_rows < 4096 ? 4096 : ext_rows) : 0;
@@ -854,11 +869,15 @@ static int ensure_msig_scratch(size_t n, size_t n_transcripts, size_t ext_rows =
     size_t ck = ks_rows ? grown(ks_rows < 4096 ? 4096 : ks_rows) : 0, ckt = ks_rows ? grown(ks_transcripts < 1024 ? 1024 : ks_transcripts) : 0;
     if (ck < g->msig_ks_rows) ck = g->msig_ks_rows;
     if (ckt < g->msig_ks_transcripts) ckt = g->msig_ks_transcripts;
+    size_t cs = sign_rows ? grown(sign_rows < 4096 ? 4096 : sign_rows) : 0, cst = sign_rows ? grown(sign_transcripts < 1024 ? 1024 : sign_transcripts) : 0;
+    if (cs < g->msig_sign_rows) cs = g->msig_sign_rows;
+    if (cst < g->msig_sign_transcripts) cst = g->msig_sign_transcripts;
     device_mem<uint8_t> fresh;
-    HIP_TRY(fresh.alloc(msig_scratch_bytes(ci, ct, ce, ck, ckt)));
+    HIP_TRY(fresh.alloc(msig_scratch_bytes(ci, ct, ce, ck, ckt, cs, cst)));
     g->msig.replace(std::move(fresh));
     g->msig_items = ci; g->msig_transcripts = ct; g->msig_ext_rows = ce;
     g->msig_ks_rows = ck; g->msig_ks_transcripts = ckt;
+    g->msig_sign_rows = cs; g->msig_sign_transcripts = cst;
     return JJS_OK;
 }
 // The normalisation in front of the passes of an extended call: `cols` columns of n rows (96 bytes a point) into the scratch's
@@ -952,6 +971,7 @@ int jjs_multisig_combine_ext_dev(const void* z, const void* PK_ext, const void* 
 #include "msig_host_calls.h"
 #include "msig_keyset_calls.h"
 #include "msig_verify_calls.h"
+#include "msig_sign_calls.h"
 
 // ---- challenge export ---------------------------------------------------------------------------
 static int launch_challenge(challenge_params P, void* stream) {

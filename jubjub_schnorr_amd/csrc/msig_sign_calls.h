@@ -1,0 +1,165 @@
+// Part of jjs_gpu.hip (included among the extern "C" entry points, behind msig_verify_calls.h): the signer's half of the
+// multisignature scheme (msig_sign.h, include/jjs_gpu.h jjs_multisig_round1_dev, jjs_multisig_sign*) -- the front of the combine
+// call (passes 0-3) with the check pass behind pass 0, pass 4 without a column of shares, and the share pass.  Generators of test
+// and benchmark material, NOT constant time.  The passes use the multisignature scratch, which belongs to slot 0; pk_agg and RSa,
+// which a signing call does not return, are columns of that scratch.
+
+extern "C++" {
+struct ms_call {
+    bool ext;
+    const void *PK, *R, *S, *m;
+    const void *signer_row, *sk, *r, *s;
+    size_t n_signing;
+    void *z_out, *status;
+};
+// The call on device columns, queued on st (under the engine's mutex, g the device; n_transcripts > 0, n_signing > 0).
+static int msig_sign_locked(const ms_call& A, const uint32_t* offsets_host, size_t n_transcripts, hipStream_t st) {
+    size_t n = 0;
+    if (int rc = msig_check_offsets(offsets_host, n_transcripts, n)) return rc;
+    if (!A.signer_row && A.n_signing != n)
+        return fail(JJS_ERR_ARG, "without signer_row a call signs every row: %zu signing rows, %zu participant rows", A.n_signing, n);
+    if ((n && !all_ok(A.PK, A.R, A.S)) || !all_ok(A.m, A.sk, A.r, A.s, A.z_out) || !A.status || (reinterpret_cast<uintptr_t>(A.signer_row) & 3u))
+        return fail(JJS_ERR_ARG, "null or misaligned pointer");
+    const size_t B = n_transcripts;
+    if (int rc = ensure_msig_scratch(n, B, A.ext ? n : 0, 0, 0, n ? n : 1, B)) return rc;
+    const msig_scratch W = msig_scratch_carve();
+    const uint8_t* pts[3] = {(const uint8_t*)A.PK, (const uint8_t*)A.R, (const uint8_t*)A.S};
+    msig_sign_params G{};
+    msig_params& P = G.M;
+    P.m = (const uint8_t*)A.m;
+    P.n_transcripts = (uint32_t)B; P.n_total = n;
+    P.agg_pk = W.sign_agg; P.sig_R = W.sign_rsa;
+    P.tr_of = W.tr_of; P.d_words = W.d_words; P.dpk = W.dpk; P.e_pt = W.e_pt;
+    P.a_words = W.a_words; P.c_words = W.c_words; P.offsets = W.offsets;
+    P.tags = g->tags_long; P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
+    P.max_table_participants = JJS_MSIG_MAX_PARTICIPANTS;
+    P.long_tags = W.long_tags;
+    P.hash_lanes = 1;
+    G.pk_repeats = W.sign_flags; G.bad_enc = W.sign_flags + g->msig_sign_rows; G.dup_nonce = G.bad_enc + g->msig_sign_transcripts;
+    G.signer_row = (const uint32_t*)A.signer_row;
+    G.sk = (const uint8_t*)A.sk; G.r = (const uint8_t*)A.r; G.s = (const uint8_t*)A.s;
+    G.n_signing = A.n_signing;
+    G.z_out = (uint8_t*)A.z_out; G.status = (uint8_t*)A.status;
+    big_slot();
+    if (int rc = begin_shared(st)) return rc;
+    auto queue = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(W.offsets, offsets_host, (B + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(W.sign_flags, 0, (g->msig_sign_rows + 2 * g->msig_sign_transcripts) * sizeof(uint32_t), st));
+        if (A.ext && n)
+            if (int rc = msig_normalize(W, pts, 3, n, st)) return rc;
+        P.PK = pts[0]; P.R = pts[1]; P.S = pts[2];
+        const dim3 per_row(grid_for(g->grid_msig, n)), per_transcript(grid_for(g->grid_msig, B));
+        hipLaunchKernelGGL(msig_kernel, per_transcript, dim3(BLOCK), 0, st, P, 0);
+        if (n) {
+            hipLaunchKernelGGL(msig_sign_check_kernel, per_row, dim3(BLOCK), 0, st, G);       // behind the map: it reads tr_of
+            for (int pass = 1; pass < 5; ++pass) {
+                const size_t count = (pass == 2 || pass == 4) ? B : n;
+                // a pass with a hash chain and few items: eight lanes per item (multisig_core.h hash_lanes)
+                P.hash_lanes = pass != 3 ? msig_hash_lanes(count) : 1u;
+                const dim3 grid(grid_for(g->grid_msig, count * P.hash_lanes));
+                if (pass < 4) hipLaunchKernelGGL(msig_kernel, grid, dim3(BLOCK), 0, st, P, pass);
+                else hipLaunchKernelGGL(msig_sign_final_kernel, grid, dim3(BLOCK), 0, st, P);
+            }
+            P.hash_lanes = 1;
+        }
+        hipLaunchKernelGGL(msig_sign_share_kernel, dim3(grid_for(g->grid_msig, A.n_signing)), dim3(BLOCK), 0, st, G);
+        HIP_TRY(hipGetLastError());
+        return JJS_OK;
+    };
+    const int rc = queue();
+    const int rc2 = end_shared(st);             // the slot's event covers whatever was queued, also when a step failed
+    return rc ? rc : rc2;
+}
+}  // extern "C++"
+
+extern "C" {
+
+int jjs_multisig_round1_dev(const void* r, const void* s, size_t n, void* R_out, void* S_out, void* bad_out, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    if (n == 0) return JJS_OK;
+    if (!all_ok(r, s, R_out, S_out)) return fail(JJS_ERR_ARG, "null or misaligned pointer");
+    size_t blocks = (n + BLOCK - 1) / BLOCK;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(msig_round1_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, (hipStream_t)stream, (const uint8_t*)r, (const uint8_t*)s,
+                       (uint64_t)n, g->comb_g, (uint8_t*)R_out, (uint8_t*)S_out, (uint8_t*)bad_out);
+    HIP_TRY(hipGetLastError());
+    return JJS_OK;
+}
+
+int jjs_multisig_sign_dev(int format, const void* PK, const void* R, const void* S, const void* m, const uint32_t* offsets_host,
+                          size_t n_transcripts, const void* signer_row, const void* sk, const void* r, const void* s, size_t n_signing,
+                          void* z_out, void* sign_status, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    ms_call A{};
+    if (int rc = msig_format(format, A.ext)) return rc;
+    if (n_transcripts == 0 || n_signing == 0) return JJS_OK;
+    A.PK = PK; A.R = R; A.S = S; A.m = m; A.signer_row = signer_row; A.sk = sk; A.r = r; A.s = s; A.n_signing = n_signing;
+    A.z_out = z_out; A.status = sign_status;
+    return no_throw([&] { return msig_sign_locked(A, offsets_host, n_transcripts, (hipStream_t)stream); });
+}
+
+// The same from host buffers, blocking, on the route of jjs_multisig_combine (msig_host_calls.h): the columns go whole into the
+// device's multisignature staging area, one such call at a time per device.  The staged sk, r and s are cleared on the stream
+// behind the share pass, before the call returns.
+int jjs_multisig_sign(int format, const uint8_t* PK, const uint8_t* R, const uint8_t* S, const uint8_t* m, const uint32_t* offsets,
+                      size_t n_transcripts, const uint32_t* signer_row, const uint8_t* sk, const uint8_t* r, const uint8_t* s, size_t n_signing,
+                      uint8_t* z_out, uint8_t* sign_status) {
+    device_state* dev = nullptr;
+    bool ext = false;
+    size_t n = 0;
+    {
+        std::lock_guard<std::mutex> lock(L.mu);
+        if (int rc = check_ready()) return rc;
+        if (int rc = msig_format(format, ext)) return rc;
+        if (n_transcripts == 0 || n_signing == 0) return JJS_OK;
+        if (int rc = msig_check_offsets(offsets, n_transcripts, n)) return rc;
+        if (!signer_row && n_signing != n)
+            return fail(JJS_ERR_ARG, "without signer_row a call signs every row: %zu signing rows, %zu participant rows", n_signing, n);
+        if ((n && (!PK || !R || !S)) || !m || !sk || !r || !s || !z_out || !sign_status) return fail(JJS_ERR_ARG, "null pointer");
+        dev = g;
+        ++g_blocking_calls;              // jjs_shutdown does not free `dev` before this call has left
+    }
+    blocking_call_leave leave_on_every_way_out;
+    std::lock_guard<std::mutex> big(dev->host_mu);
+    g = dev;
+    return no_throw([&]() -> int {
+        const size_t B = n_transcripts, w = ext ? 96 : 64, k = n_signing;
+        // two rounds of the five-column staging would overlap: one area, laid out here (parts padded to 256 bytes, as msig_stage_in's)
+        const void* src[8] = {PK, R, S, m, signer_row, sk, r, s};
+        const size_t bytes[10] = {n * w, n * w, n * w, B * 32, signer_row ? k * 4 : 0, k * 32, k * 32, k * 32, k * 32, k};
+        size_t off[10], total = 0;
+        for (int i = 0; i < 10; ++i) { off[i] = total; total += pad256(bytes[i] ? bytes[i] : 1); }
+        HIP_TRY(hipSetDevice(dev->device));
+        if (dev->msig_stage.capacity() < total) {
+            std::lock_guard<std::mutex> lock(L.mu);
+            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
+            if (int rc = dev->msig_stage.ensure(total)) return rc;
+        }
+        hipStream_t st = dev->ks_stream;
+        uint8_t* part[10];
+        for (int i = 0; i < 10; ++i) part[i] = dev->msig_stage + off[i];
+        // whatever happens behind this point, the staged secrets (parts 5-7, adjacent) are cleared before the call returns
+        struct wipe {
+            uint8_t* at; size_t bytes; hipStream_t st;
+            ~wipe() { (void)hipMemsetAsync(at, 0, bytes, st); (void)hipStreamSynchronize(st); }
+        } wipe_secrets{part[5], off[8] - off[5], st};
+        for (int i = 0; i < 8; ++i)
+            if (bytes[i]) HIP_TRY(hipMemcpyAsync(part[i], src[i], bytes[i], hipMemcpyHostToDevice, st));
+        {
+            std::lock_guard<std::mutex> lock(L.mu);
+            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
+            ms_call A{};
+            A.ext = ext; A.PK = part[0]; A.R = part[1]; A.S = part[2]; A.m = part[3]; A.signer_row = signer_row ? part[4] : nullptr;
+            A.sk = part[5]; A.r = part[6]; A.s = part[7]; A.n_signing = k; A.z_out = part[8]; A.status = part[9];
+            if (int rc = msig_sign_locked(A, offsets, B, st)) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(z_out, part[8], k * 32, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(sign_status, part[9], k, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return JJS_OK;
+    });
+}
+
+}  // extern "C"
