@@ -15,7 +15,7 @@ using fe_t = fe<1, 5>;  // a cached-addend coordinate (normalised limbs, value <
 struct ext_pt {   // (X : Y : Z : T), x = X/Z, y = Y/Z, T = XY/Z
     fe_n x, y, z, t;
 };
-struct niels_pt {  // cached addend (Y+X, Y-X, Z, 2dT); Z = R' for affine entries
+struct niels_pt {  // cached addend (Y+X, Y-X, Z, 2dT); Z = R' (one) for affine entries: the key tables, whose z nobody reads
     fe_t ypx, ymx, z, t2d;
 };
 
@@ -93,12 +93,16 @@ JJS_HD ext_pt ext_add_niels(const ext_pt& p, const niels_pt& n, bool neg, bool n
     if (need_t) r.t = fq_mul_hot(h, e); else r.t = fe_n_zero();
     return r;
 }
-// P + N where N is affine (Z2 = 1): 7M (6M without T)
-JJS_HD ext_pt ext_add_affine_niels(const ext_pt& p, const fe_t& n_ypx, const fe_t& n_ymx, const fe_t& n_t2d,
-                                   bool need_t) {
-    fe_n a = fq_mul_hot(fq_sub(p.y, p.x), n_ymx);
-    fe_n b = fq_mul_hot(fq_add(p.y, p.x), n_ypx);
-    fe_n c = fq_mul_hot(p.t, n_t2d);
+// P + N or, with neg, P - N where N is affine (Z2 = 1): 7M (6M without T).  The sign swaps the two sums and negates 2dT, as in
+// ext_add_niels.
+JJS_HD ext_pt ext_add_affine_niels_signed(const ext_pt& p, const fe_t& n_ypx, const fe_t& n_ymx, const fe_t& n_t2d, bool neg,
+                                          bool need_t) {
+    fe_t s_ymx = fq_select(neg, n_ypx, n_ymx);
+    fe_t s_ypx = fq_select(neg, n_ymx, n_ypx);
+    auto s_t2d = fq_select(neg, fq_neg(n_t2d), fq_as<2, 6>(n_t2d));   // <2,6>
+    fe_n a = fq_mul_hot(fq_sub(p.y, p.x), s_ymx);
+    fe_n b = fq_mul_hot(fq_add(p.y, p.x), s_ypx);
+    fe_n c = fq_mul_hot(p.t, s_t2d);
     auto d = fq_dbl(p.z);                          // <2,4>
     auto e = fq_sub(b, a);
     auto f = fq_norm(fq_sub(d, c));
@@ -110,6 +114,12 @@ JJS_HD ext_pt ext_add_affine_niels(const ext_pt& p, const fe_t& n_ypx, const fe_
     r.y = fq_mul_hot(g, h);
     if (need_t) r.t = fq_mul_hot(h, e); else r.t = fe_n_zero();
     return r;
+}
+
+// the same for a known sign (the selects fold away)
+JJS_HD ext_pt ext_add_affine_niels(const ext_pt& p, const fe_t& n_ypx, const fe_t& n_ymx, const fe_t& n_t2d,
+                                   bool need_t) {
+    return ext_add_affine_niels_signed(p, n_ypx, n_ymx, n_t2d, false, need_t);
 }
 
 JJS_HD bool ext_is_identity(const ext_pt& p) { return fq_is_zero(p.x) && fq_eq(p.y, p.z); }

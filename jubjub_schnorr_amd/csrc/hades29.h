@@ -67,7 +67,12 @@ __device__ __forceinline__ void hades_gather5(fe_n (&out)[5], const fe_n& mine, 
     }
 }
 #endif
-JJS_HD void hades_permute(hades_state& st, int coop = -1) {
+// digest_only (the last permutation of a digest, not on the cooperative path): the caller reads st.s[1] alone, so only that
+// element gets its product with lambda_end; the other four come back as zero.  The last
+// round still applies the whole matrix: a second way through the loop's body for row 1 alone (74 instructions instead of the
+// block's 365) cost every round the register copies that join the two ways, and as a round of its own behind the loop it
+// made prepare_kernel spill vector registers.
+JJS_HD void hades_permute(hades_state& st, int coop = -1, bool digest_only = false) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const int cj = coop < 4 ? coop : 4, cbase = (int)(__lane_id() & ~7u);
     uint32_t crow[5] = {0, 0, 0, 0, 0};         // this lane's row of the matrix: S[cj][k] = JJS_HS_HANKEL[cj + k]
@@ -123,6 +128,11 @@ JJS_HD void hades_permute(hades_state& st, int coop = -1) {
         }
         hades_matrix(st, t);
     }
+    if (digest_only) {
+        st.s[1] = fq_mul(st.s[1], fe_from_const<1, 1>(JJS_HS_LAMBDA_END));
+        st.s[0] = st.s[2] = st.s[3] = st.s[4] = fq_as<1, 2>(fq_zero());       // dead for the register allocator too
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < 5; ++i) st.s[i] = fq_mul(st.s[i], fe_from_const<1, 1>(JJS_HS_LAMBDA_END));
 }
@@ -143,7 +153,7 @@ JJS_HD fe_n poseidon_digest_tagged(int n_inputs, const fe_n& tag, Fetch fetch, i
             int e = 4 * blk + k;
             if (e < n_inputs) st.s[1 + k] = fq_reduce(fq_norm(fq_add(st.s[1 + k], fetch(e))));
         }
-        hades_permute(st, coop);
+        hades_permute(st, coop, coop < 0 && blk == n_blocks - 1);
     }
     return st.s[1];
 }

@@ -18,7 +18,8 @@
 //                 not the identity, torsion-free by the pairing test), the chain B_i = 2^(w i) * P and the tables
 //                 {0 .. 2^(w-1)} * B_i for signed w-bit digits (w = 5 or 6, chosen with the decision).
 //   4. per item   challenge hash as before (prepare_item in keyed mode: no half-size scalars, no combined test);
-//                 then  acc = sum_i digit_i(c) * B_i  (51 or 43 additions, no doubling) + u*G from the fixed-base comb
+//                 then  acc = sum_i digit_i(c) * B_i  (51 or 42 additions of affine entries, 7 products each, no doubling:
+//                 kt_add_challenge) + u*G from the fixed-base comb
 //                 (16 additions), compared with R projectively: the reference's own equation u*G + c*PK == R
 //                 (src/keys/public.rs:128-130), computed exactly by the complete addition law.
 //   5. memo      a slot's pool outlives the call, and so do the keys of real callers (the validator set of the next block): the
@@ -84,7 +85,7 @@ struct key_column {
     uint32_t* valid_ids;     // [max_keys] the ids of the keys whose point is valid, in the order the chain kernel found them (their
                              // number: key_params::counters[5 + column]): only these get window tables
     uint32_t* bases;         // [pool index][positions][36]: 2^(w i) * P in extended coordinates (w = the window width of this batch)
-    uint32_t* tables;        // [pool index][positions][table words]: {0 .. 2^(w-1)} * base, cached-addend form
+    uint32_t* tables;        // [pool index][positions][table words]: {0 .. 2^(w-1)} * base, affine cached addends (kt_build_table)
     uint32_t* pool_of;       // [max_keys] the pool index of a key id; null = the identity (registered key sets: keyset.h)
 };
 // What a slot remembers of its last key-table call, per key column (device memory, allocated beside the pool and sized by its
@@ -354,16 +355,45 @@ JJS_HD void kt_memo_flags(const key_column& C, const key_memo& M, uint32_t id) {
     if (M.flags) M.flags[kt_pool(C, id)] = C.key_flags[id];
 }
 
-// table[j] = j * P for j = 0 .. entries-1, P in extended coordinates (the cached-addend entries keep their Z)
+// table[j] = j * P for j = 0 .. entries-1, P in extended coordinates, as AFFINE cached addends (v+u, v-u, 1, 2d u v): a table
+// outlives the call that built it (step 5, registered key sets, signer groups), so the normalisation is paid once per key
+// and every addition from the table is the 7-product one (kt_add_digit) instead of the 8-product one.  ONE inversion per
+// table (Montgomery's trick): the first pass leaves (X, Y, Z, Z_1 ... Z_{j-1}) of j * P in entry j -- the fourth slot is free
+// until the entry is normalised --, the second walks back from 1 / (Z_1 ... Z_last).  The z slot ends as the Montgomery form
+// of one; nothing reads it on the way to a verdict.  A Z of zero (a base that is not on the curve: the table of a key that is
+// not valid, which no verdict reads) makes every entry zero.
+JJS_HD void kt_put_projective(uint32_t* dst, const ext_pt& p, const fe_n& prefix) {
+    niels_pt n;
+    n.ypx = fq_as<1, 5>(p.x); n.ymx = fq_as<1, 5>(p.y); n.z = fq_as<1, 5>(p.z); n.t2d = fq_as<1, 5>(prefix);
+    store_niels(dst, n);
+}
 JJS_HD void kt_build_table(uint32_t* tab, const ext_pt& p1, int entries) {
     const niels_pt n1 = to_niels(p1);
     store_niels(tab, niels_identity());
-    store_niels(tab + ENTRY_WORDS, n1);
+    fe_n run = fe_n_one();
+    kt_put_projective(tab + ENTRY_WORDS, p1, run);
+    run = p1.z;
     ext_pt acc = ext_double(p1, true);
-    store_niels(tab + 2 * ENTRY_WORDS, to_niels(acc));
-    for (int j = 3; j < entries; ++j) {
-        acc = ext_add_niels(acc, n1, false, true);
-        store_niels(tab + j * ENTRY_WORDS, to_niels(acc));
+    for (int j = 2; j < entries; ++j) {
+        if (j > 2) acc = ext_add_niels(acc, n1, false, true);
+        kt_put_projective(tab + j * ENTRY_WORDS, acc, run);
+        run = fq_mul_hot(run, acc.z);
+    }
+    fe_n inv = fq_inverse(run);
+    niels_pt e = load_niels(tab + (entries - 1) * ENTRY_WORDS);      // (X, Y, Z, prefix) as the first pass left them
+    for (int j = entries - 1; j >= 1; --j) {
+        niels_pt below = e;
+        if (j > 1) below = load_niels(tab + (j - 1) * ENTRY_WORDS);  // on its way while this entry is normalised
+        const fe_n zi = fq_mul_hot(inv, e.t2d);
+        inv = fq_mul_hot(inv, e.z);
+        const fe_n u = fq_mul_hot(e.ypx, zi), v = fq_mul_hot(e.ymx, zi);
+        niels_pt n;
+        n.ypx = fq_as<1, 5>(fq_norm(fq_add(v, u)));
+        n.ymx = fq_norm(fq_sub(v, u));
+        n.z = fq_as<1, 5>(fq_one());
+        n.t2d = fq_as<1, 5>(fq_mul_hot(fq_mul_hot(u, v), fe_from_const<1, 1>(JJS_D2)));
+        store_niels(tab + j * ENTRY_WORDS, n);
+        e = below;
     }
 }
 JJS_HD void kt_table_lane(const key_column& C, uint32_t id, uint32_t pos, int w) {
@@ -399,6 +429,19 @@ JJS_HD words8 kt_recode(const words8& s, int w) {
     }
     return r;
 }
+// (v+u, v-u, 2d u v) of a table entry: words 0..17 and 27..35 of its 36, eight 16-byte loads; the z slot (one) is not read
+JJS_HD void kt_load_affine(const uint32_t* src, fe_t& ypx, fe_t& ymx, fe_t& t2d) {
+    const u32x4* p = reinterpret_cast<const u32x4*>(src);
+    uint32_t w[ENTRY_WORDS];
+#pragma unroll
+    for (int i = 0; i < ENTRY_WORDS / 4; ++i) {
+        if (i == 5) continue;                       // words 20..23: z only
+        const u32x4 v = p[i];
+        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { ypx.l[i] = w[i]; ymx.l[i] = w[9 + i]; t2d.l[i] = w[27 + i]; }
+}
 // acc + (digit `pos` of the recoded scalar) * base_pos; pos and w are wave-uniform, the digit is per lane
 JJS_HD ext_pt kt_add_digit(const ext_pt& acc, const uint32_t* tab, const words8& sc, int pos, int w) {
     const int bit = w * pos, wi = bit >> 5, sh = bit & 31;
@@ -410,13 +453,29 @@ JJS_HD ext_pt kt_add_digit(const ext_pt& acc, const uint32_t* tab, const words8&
     const bool neg = d < 0;
     uint32_t idx = (uint32_t)(neg ? -d : d);
     idx = idx >= (uint32_t)kt_entries(w) ? (uint32_t)kt_entries(w) - 1u : idx;     // out-of-range (malformed) scalars only
-    return ext_add_niels(acc, load_niels(tab + idx * ENTRY_WORDS), neg, true);
+    fe_t ypx, ymx, t2d;
+    kt_load_affine(tab + idx * ENTRY_WORDS, ypx, ymx, t2d);
+    return ext_add_affine_niels_signed(acc, ypx, ymx, t2d, neg, true);
 }
 // acc + s * P for the key `id` of column C, s < 2^252: one addition per position, no doubling.  T of the result is valid.
 JJS_HD ext_pt kt_add_scalar(ext_pt acc, const key_column& C, uint32_t id, const words8& s, int w) {
     const words8 sc = kt_recode(s, w);
     const uint32_t pi = kt_pool(C, id);            // one 4-byte load per item and column; the items are grouped by key
     for (int pos = kt_positions(w) - 1; pos >= 0; --pos) acc = kt_add_digit(acc, kt_table(C, pi, (uint32_t)pos, w), sc, pos, w);
+    return acc;
+}
+// The same for a challenge, c < 2^250 (truncate250).  With wide windows the recoded c is below 2^250 + 32 (2^252 - 1) / 63 <
+// 0.76 * 2^252, and the top position starts at bit 252: its digit is zero whatever c is, and the position below it -- bits
+// 246 .. 251, at most 32 + 17 -- reads as the signed digit it is.  With narrow windows the top position starts at bit 250 and its digit can be 1.
+// (The profiling build's JJS_SKIP bit 2 puts u, up to 252 bits, in c's place: its dropped top digit is then not zero, and the
+// verdicts of that ablation, which mean nothing anyway, differ from a full sum's.)
+JJS_HD constexpr int kt_challenge_positions(int w) { return kt_positions(w) - (w == KT_WINDOW_WIDE ? 1 : 0); }
+static_assert(KT_WINDOW_WIDE * (kt_positions(KT_WINDOW_WIDE) - 1) >= 252 && KT_WINDOW_NARROW * (kt_positions(KT_WINDOW_NARROW) - 1) <= 250,
+              "which top positions a 250-bit scalar leaves empty");
+JJS_HD ext_pt kt_add_challenge(ext_pt acc, const key_column& C, uint32_t id, const words8& c, int w) {
+    const words8 sc = kt_recode(c, w);
+    const uint32_t pi = kt_pool(C, id);
+    for (int pos = kt_challenge_positions(w) - 1; pos >= 0; --pos) acc = kt_add_digit(acc, kt_table(C, pi, (uint32_t)pos, w), sc, pos, w);
     return acc;
 }
 
@@ -437,7 +496,7 @@ JJS_HD uint32_t kt_finish_item(const verify_params& P, const key_params& K, uint
             const uint32_t id = C.keyid[item], f = C.key_flags[id];
             keys_valid = keys_valid && (f & KT_KEY_VALID) != 0;
             keys_malformed = keys_malformed || (f & KT_KEY_MALFORMED) != 0;
-            acc = kt_add_scalar(acc, C, id, r.c, w);                          // c * PK
+            acc = kt_add_challenge(acc, C, id, r.c, w);                       // c * PK
         }
         if (E.comb) {
             // JJS_SKIP bit 4 (profiling build only, constant false in the product): 256 entries per comb row, a

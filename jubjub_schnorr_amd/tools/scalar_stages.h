@@ -1,6 +1,6 @@
 // The scalar multiplications of csrc/*.h, one stage per function group, with caller-chosen scalars and points: the comb
 // (comb_mul), the per-lane window table (build_point_table + table_mul), the two equations of check_equation, the key tables
-// (kt_chain_key, kt_build_table, kt_add_scalar), the latency path (sb_chain_lane, sb_piece and the sum in the order of the
+// (kt_chain_key, kt_build_table, kt_add_scalar, kt_add_challenge), the latency path (sb_chain_lane, sb_piece and the sum in the order of the
 // shuffle tree) and, on the device only, the quad chains (kt_chain_key_quad, sb_chain_lane_quad).  ONE copy of the stage
 // bodies and of the record format, compiled into tests/hostbuild/host_harness.cpp (CPU build) and tools/scalarcheck.hip
 // (device): the two cannot drift.  The stages only execute; tests/scalar_mul_cases.py writes the inputs and checks every
@@ -21,7 +21,7 @@ namespace jjs {
 namespace sc {
 
 // the test reads this enum
-enum Kind : uint32_t { K_COMB = 1, K_TABLE, K_EQ, K_KT, K_KT_DUMP, K_SB, K_SB_TABLES, K_KT_BASES_QUAD, K_SB_TABLES_QUAD };
+enum Kind : uint32_t { K_COMB = 1, K_TABLE, K_EQ, K_KT, K_KT_DUMP, K_SB, K_SB_TABLES, K_KT_BASES_QUAD, K_SB_TABLES_QUAD, K_KT_CHALLENGE };
 constexpr uint32_t code(uint32_t kind, uint32_t param = 0) { return kind << 24 | param; }
 
 struct ctx {
@@ -114,6 +114,17 @@ struct Kt {
         out[37] = valid ? 1u : 0u;
     }
 };
+// P (16) | c (8), c < 2^250  ->  c * P as kt_finish_item adds a challenge (kt_add_challenge: 36, T valid)
+template <int W>
+struct KtChallenge {
+    static constexpr int LANES = 1, IN = 24, OUT = 36, SCRATCH = 4 + KtSizes<W>::BASES + KtSizes<W>::TABLES;
+    JJS_HD static void run(const ctx&, const uint32_t* in, uint32_t* out, uint32_t* scratch, uint32_t) {
+        const key_column K = one_key(in, scratch, scratch + 4, scratch + 4 + KtSizes<W>::BASES);
+        kt_chain_key(K, 0, W);
+        for (uint32_t pos = 0; pos < (uint32_t)kt_positions(W); ++pos) kt_table_lane(K, 0, pos, W);
+        st_pt(out, kt_add_challenge(ext_identity(), K, 0, ld8(in + 16), W));
+    }
+};
 // P (16) | pad (8)  ->  the bases 2^(W i) P (positions x 36) | the tables j * base (positions x entries x 36)
 template <int W>
 struct KtDump {
@@ -197,6 +208,8 @@ int dispatch(X& x, uint32_t c, uint32_t n) {
     case code(K_KT, 6): return x.template step<Kt<6>>(n);
     case code(K_KT_DUMP, 5): return x.template step<KtDump<5>>(n);
     case code(K_KT_DUMP, 6): return x.template step<KtDump<6>>(n);
+    case code(K_KT_CHALLENGE, 5): return x.template step<KtChallenge<5>>(n);
+    case code(K_KT_CHALLENGE, 6): return x.template step<KtChallenge<6>>(n);
     case code(K_SB, 4): return x.template step<Sb<4>>(n);
     case code(K_SB, 8): return x.template step<Sb<8>>(n);
     case code(K_SB, 16): return x.template step<Sb<16>>(n);
