@@ -472,6 +472,71 @@ int jjs_multisig_combine(int format, const uint8_t* z, const uint8_t* PK, const 
 int jjs_msig_group_combine(jjs_msig_group g, int format, const uint8_t* z, const uint8_t* R, const uint8_t* S, const uint8_t* m,
                            size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status, uint8_t* sig_u, uint8_t* sig_R);
 
+/* ---- multisignature from wire encodings ------------------------------------------------------------------------
+ * What the parties of the protocol hold when they first touch the data: a verifier receives PublicKey::to_bytes() (32 bytes a
+ * key) and Signature::to_bytes() (64 bytes = u || R); a combiner receives every signer's key, its two nonce commitments and its
+ * share over the network, 32 bytes a point.  The *_wire calls are the multisignature calls of the other sections -- inline, by
+ * signer group, by key set, combine and the verifier's two -- with every point column as N x 32 = JubJubAffine::to_bytes, decoded
+ * on the device (msig_decode_kernel in front of the first pass, on the caller's stream, one lane per point).  The `format`
+ * argument of the calls that have one keeps refusing JJS_FORMAT_WIRE with -1: these entry points are the wire form.
+ * Layouts.  Points: N x 32 (the key-set forms: R_w and S_w; jjs_msig_group_create_wire: the n keys).  z, m, offsets, key_idx
+ * and every output: unchanged -- agg_pk and sig_R stay 64-byte affine as in the extended form (jjs_compress_dev turns them into
+ * wire bytes).  The aggregate signature of the verifier's calls is ONE column sig_w, B x 64 = u || R, the layout of
+ * jjs_verify_single_wire, where the other forms take u and R.
+ * Contract.  An encoding is UNDECODABLE by the rules of jjs_decompress_dev, unchanged: v >= q, (v^2 - 1) / (1 + d v^2) not a
+ * square, or u = 0 with the sign bit set.  The outputs of a wire call are, byte for byte, the outputs of the affine call of the
+ * same shape on derived columns in which every decodable encoding is the point jjs_decompress_dev writes for it and every
+ * undecodable encoding is 64 bytes of 0xFF.  A share, key or signature with an undecodable point therefore gets status 3 from
+ * the range test of its coordinates -- the family's rule, and the status jjs_verify_single_wire gives -- and its transcript or
+ * vector gets no signature or aggregate; whatever the affine call does with the rest of it, the wire call does too.  Decodable
+ * points are on the curve but need not be in the prime-order subgroup: they pass through unvalidated, as everywhere in this
+ * family.  Alignment (16 bytes for the _dev forms, none for the host forms), asynchrony, n_transcripts == 0, limits and return
+ * codes are those of the affine call of the same shape; -4 before jjs_init, before any argument is looked at.
+ * jjs_msig_group_create_wire refuses a vector with an undecodable key with -1, as jjs_msig_group_create_ext refuses an unusable
+ * one; a group registered from wire keys is the group registered from the affine keys they decode to (the same aggregate_pk,
+ * the same bytes out of every call, whatever the format of the call).
+ * The signer's half (jjs_multisig_round1_dev, jjs_multisig_sign*) has no wire form: it takes values its caller made.
+ * Measured (profiles/r15_msig_wire.jsonl, tools/msig_wire_rate.py: one MI355X, resident all-decodable inputs, 8 / 64 / 256
+ * participants at 1 / 64 / 4 096 transcripts, 7 rounds, medians; (a) the wire call, (b) one jjs_decompress_dev per point column
+ * then the affine call, (c) the affine call alone).  The decode is a small share of a call: (a)/(c) is 0.97-1.04 for combine,
+ * 1.00-1.07 by group (two shapes aside, below), 1.00-1.17 for the verifier's calls, largest where the call is shortest.  Against
+ * (b) the wire call wins beyond the spreads at 12 of 36 shapes, all combine and group calls (0.92-0.99 of b's time; 0.81 at one group call of 256 participants, B = 1), loses at 4
+ * and is level at 20: the verifier's calls are level everywhere but three shapes lost by 0.04-0.23 ms (1.005-1.012), and one
+ * group call of 64 participants, B = 1, is lost by 1.75 ms (12.4 against 10.7, 1.164).  What the wire form buys a caller is the
+ * contract (one call, statuses folded), not time. */
+int jjs_multisig_combine_wire_dev(const void* z, const void* PK_w, const void* R_w, const void* S_w, const void* m,
+                                  const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
+                                  void* agg_pk, void* sig_u, void* sig_R, void* stream);
+int jjs_multisig_combine_wire(const uint8_t* z, const uint8_t* PK_w, const uint8_t* R_w, const uint8_t* S_w, const uint8_t* m,
+                              const uint32_t* offsets, size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status,
+                              uint8_t* agg_pk, uint8_t* sig_u, uint8_t* sig_R);
+int jjs_msig_group_create_wire(const uint8_t* PK_w, size_t n, jjs_msig_group* out);
+int jjs_msig_group_combine_wire_dev(jjs_msig_group g, const void* z, const void* R_w, const void* S_w, const void* m,
+                                    size_t n_transcripts, void* share_status, void* transcript_status, void* sig_u, void* sig_R,
+                                    void* stream);
+int jjs_msig_group_combine_wire(jjs_msig_group g, const uint8_t* z, const uint8_t* R_w, const uint8_t* S_w, const uint8_t* m,
+                                size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status, uint8_t* sig_u,
+                                uint8_t* sig_R);
+int jjs_multisig_combine_keyset_wire_dev(jjs_keyset ks, const void* key_idx, const void* z, const void* R_w, const void* S_w,
+                                         const void* m, const uint32_t* offsets_host, size_t n_transcripts, void* share_status,
+                                         void* transcript_status, void* agg_pk, void* sig_u, void* sig_R, void* stream);
+int jjs_multisig_combine_keyset_wire(jjs_keyset ks, const uint32_t* key_idx, const uint8_t* z, const uint8_t* R_w,
+                                     const uint8_t* S_w, const uint8_t* m, const uint32_t* offsets, size_t n_transcripts,
+                                     uint8_t* share_status, uint8_t* transcript_status, uint8_t* agg_pk, uint8_t* sig_u,
+                                     uint8_t* sig_R);
+int jjs_multisig_aggregate_pk_wire_dev(const void* PK_w, const uint32_t* offsets_host, size_t n_transcripts, void* agg_pk,
+                                       void* vec_status, void* stream);
+int jjs_multisig_aggregate_pk_wire(const uint8_t* PK_w, const uint32_t* offsets, size_t n_transcripts, uint8_t* agg_pk,
+                                   uint8_t* vec_status);
+int jjs_multisig_verify_wire_dev(const void* PK_w, const uint32_t* offsets_host, const void* sig_w, const void* m,
+                                 size_t n_transcripts, void* agg_pk, void* status, void* tally, void* stream);
+int jjs_multisig_verify_wire(const uint8_t* PK_w, const uint32_t* offsets, const uint8_t* sig_w, const uint8_t* m,
+                             size_t n_transcripts, uint8_t* agg_pk, uint8_t* status, uint64_t tally[4]);
+int jjs_multisig_verify_keyset_wire_dev(jjs_keyset ks, const void* key_idx, const uint32_t* offsets_host, const void* sig_w,
+                                        const void* m, size_t n_transcripts, void* agg_pk, void* status, void* tally, void* stream);
+int jjs_multisig_verify_keyset_wire(jjs_keyset ks, const uint32_t* key_idx, const uint32_t* offsets, const uint8_t* sig_w,
+                                    const uint8_t* m, size_t n_transcripts, uint8_t* agg_pk, uint8_t* status, uint64_t tally[4]);
+
 /* ---- multisignature for committees drawn from a registered key set ----------------------------------------------
  * A validator set registered once (jjs_keyset_create, JJS_SCHEME_SINGLE, any key format) of which every message is signed by
  * another ordered subset: d_i = H(pk_i, pk_1 .. pk_n) changes with the subset, so a signer group does not fit, and the inline

@@ -28,6 +28,8 @@ namespace jjs {
 using Scalar = std::array<uint8_t, 32>;     // JubJubScalar / BlsScalar: canonical little-endian
 using AffinePoint = std::array<uint8_t, 64>;  // u || v
 using ExtendedPoint = std::array<uint8_t, 96>;  // U || V || Z, affine point (U/Z, V/Z): get_u / get_v / get_z of JubJubExtended
+using PointBytes = std::array<uint8_t, 32>;       // JubJubAffine::to_bytes / PublicKey::to_bytes: v with the parity of u in bit 255
+using SignatureBytes = std::array<uint8_t, 64>;   // Signature::to_bytes: u || R
 using BlsScalar = Scalar;
 using JubJubScalar = Scalar;
 
@@ -599,6 +601,87 @@ inline VerifyResult verify(const std::vector<ExtendedPoint>& pk_vec, const Signa
     return r;
 }
 
+// ---- from wire bytes (include/jjs_gpu.h "multisignature from wire encodings") ----
+// What a combiner or a verifier holds when the data first reaches it: `to_bytes` forms, decoded on the device.  An encoding that
+// `from_bytes` would reject is BytesError for its share (combine), for its vector (aggregate_pk: nothing) or its item (verify).
+// (These overloads are templates that only vectors of PointBytes / VerifyItemBytes instantiate: a braced `{}` argument deduces
+// nothing, so calls such as combine({}, {}, {}, {}, m) keep meaning the forms above.)
+template <class P>
+using if_point_bytes = std::enable_if_t<std::is_same<P, PointBytes>::value>;
+// `combine` of ONE transcript from PublicKey::to_bytes keys and JubJubAffine::to_bytes nonce commitments (jjs_multisig_combine_wire).
+template <class P, class = if_point_bytes<P>>
+inline CombineResult combine(const std::vector<JubJubScalar>& z_vec, const std::vector<P>& pk_vec, const std::vector<P>& R_vec,
+                             const std::vector<P>& S_vec, const BlsScalar& msg) {
+    const size_t n = pk_vec.size();
+    if (n == 0 || z_vec.size() != n || R_vec.size() != n || S_vec.size() != n || n > 0xFFFFFFFFull)
+        return CombineResult{std::nullopt, CombineError{CombineError::InvalidMultisigTranscript, 0}};
+    const uint32_t offsets[2] = {0, (uint32_t)n};
+    std::vector<uint8_t> status(n);
+    uint8_t tstatus = 0;
+    AffinePoint agg{}, R{};
+    Scalar u{};
+    const int rc = jjs_multisig_combine_wire(z_vec[0].data(), pk_vec[0].data(), R_vec[0].data(), S_vec[0].data(), msg.data(), offsets, 1,
+                                             status.data(), &tstatus, agg.data(), u.data(), R.data());
+    if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_combine_wire");
+    for (size_t i = 0; i < n; ++i)
+        if (status[i])
+            return CombineResult{std::nullopt, CombineError{status[i] == JJS_STATUS_INVALID_SHARE ? CombineError::InvalidMultisigShare : CombineError::BytesError, i}};
+    return CombineResult{Signature{u, R}, std::nullopt};
+}
+// `aggregate_pk` from PublicKey::to_bytes keys (jjs_multisig_aggregate_pk_wire): nothing for a vector with an undecodable key
+template <class P, class = if_point_bytes<P>>
+inline std::optional<AffinePoint> aggregate_pk(const std::vector<P>& pk_vec) {
+    if (pk_vec.size() > 0xFFFFFFFFull) throw std::invalid_argument("a key vector is indexed with 32 bits");
+    const uint32_t offsets[2] = {0, (uint32_t)pk_vec.size()};
+    AffinePoint agg{};
+    uint8_t vst = 0;
+    const int rc = jjs_multisig_aggregate_pk_wire(pk_vec.empty() ? nullptr : pk_vec[0].data(), offsets, 1, agg.data(), &vst);
+    if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_aggregate_pk_wire");
+    return vst ? std::nullopt : std::optional<AffinePoint>(agg);
+}
+// (key vector, aggregate signature, message) as bytes
+struct VerifyItemBytes {
+    std::vector<PointBytes> pk_vec;
+    SignatureBytes sig;
+    BlsScalar message;
+};
+template <class I, class = std::enable_if_t<std::is_same<I, VerifyItemBytes>::value>>
+inline std::vector<VerifyResult> verify_batch(const std::vector<I>& items, std::vector<AffinePoint>* agg = nullptr, uint64_t tally[4] = nullptr) {
+    const size_t B = items.size();
+    std::vector<uint32_t> offsets(B + 1, 0);
+    size_t n = 0;
+    for (size_t t = 0; t < B; ++t) {
+        n += items[t].pk_vec.size();
+        if (n > 0xFFFFFFFFull) throw std::invalid_argument("the key rows of a call are indexed with 32 bits");
+        offsets[t + 1] = (uint32_t)n;
+    }
+    std::vector<PointBytes> pk(n);
+    std::vector<SignatureBytes> sig(B);
+    std::vector<Scalar> m(B);
+    std::vector<AffinePoint> a(B);
+    std::vector<uint8_t> status(B);
+    for (size_t t = 0, at = 0; t < B; ++t) {
+        for (const PointBytes& p : items[t].pk_vec) pk[at++] = p;
+        sig[t] = items[t].sig; m[t] = items[t].message;
+    }
+    if (B) {
+        const int rc = jjs_multisig_verify_wire(n ? pk[0].data() : nullptr, offsets.data(), sig[0].data(), m[0].data(), B, a[0].data(), status.data(),
+                                                tally);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_verify_wire");
+    } else if (tally) {
+        for (int k = 0; k < 4; ++k) tally[k] = 0;
+    }
+    if (agg) *agg = a;
+    return detail::results(status);
+}
+template <class P, class = if_point_bytes<P>>
+inline VerifyResult verify(const std::vector<P>& pk_vec, const SignatureBytes& sig, const BlsScalar& msg, AffinePoint* agg = nullptr) {
+    std::vector<AffinePoint> a;
+    const VerifyResult r = verify_batch(std::vector<VerifyItemBytes>{VerifyItemBytes{pk_vec, sig, msg}}, &a)[0];
+    if (agg) *agg = a[0];
+    return r;
+}
+
 // ---- the signer's half (reference src/multisig.rs sign_round_1 :169-184, sign_round_2 :213-257) ----
 // TEST AND BENCHMARK MATERIAL, as the engine's calls behind it (include/jjs_gpu.h jjs_multisig_sign): NOT constant time, here or
 // on the device -- never with production keys.  Nothing enforces the one-shot MultisigNonce of the reference (:131-141): using
@@ -772,6 +855,13 @@ class SignerGroup {
         rc = jjs_msig_group_aggregate_pk(handle_, aggregate_pk_.data());
         if (rc != JJS_OK) { reset(); throw EngineError(rc, "jjs_msig_group_aggregate_pk"); }
     }
+    // ... and as PublicKey::to_bytes (jjs_msig_group_create_wire): the group of the keys they decode to
+    explicit SignerGroup(const std::vector<PointBytes>& keys) : participants_(keys.size()) {
+        int rc = jjs_msig_group_create_wire(keys.empty() ? nullptr : keys[0].data(), keys.size(), &handle_);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_create_wire");
+        rc = jjs_msig_group_aggregate_pk(handle_, aggregate_pk_.data());
+        if (rc != JJS_OK) { reset(); throw EngineError(rc, "jjs_msig_group_aggregate_pk"); }
+    }
     SignerGroup(SignerGroup&& o) noexcept : handle_(o.handle_), participants_(o.participants_), aggregate_pk_(o.aggregate_pk_) { o.handle_ = 0; }
     SignerGroup& operator=(SignerGroup&& o) noexcept {
         if (this != &o) { reset(); handle_ = o.handle_; participants_ = o.participants_; aggregate_pk_ = o.aggregate_pk_; o.handle_ = 0; }
@@ -803,6 +893,17 @@ class SignerGroup {
                          void* transcript_status, void* sig_u, void* sig_R, void* stream = nullptr) const {
         int rc = jjs_msig_group_combine_ext_dev(handle_, z, R_ext, S_ext, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, stream);
         if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_combine_ext_dev");
+    }
+    // the same with R and S as B n x 32 wire encodings (jjs_msig_group_combine_wire_dev), and from host buffers, blocking
+    void combine_wire_dev(const void* z, const void* R_w, const void* S_w, const void* m, size_t n_transcripts, void* share_status,
+                          void* transcript_status, void* sig_u, void* sig_R, void* stream = nullptr) const {
+        int rc = jjs_msig_group_combine_wire_dev(handle_, z, R_w, S_w, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, stream);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_combine_wire_dev");
+    }
+    void combine_wire(const uint8_t* z, const uint8_t* R_w, const uint8_t* S_w, const uint8_t* m, size_t n_transcripts, uint8_t* share_status,
+                      uint8_t* transcript_status, uint8_t* sig_u, uint8_t* sig_R) const {
+        int rc = jjs_msig_group_combine_wire(handle_, z, R_w, S_w, m, n_transcripts, share_status, transcript_status, sig_u, sig_R);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_combine_wire");
     }
     // host buffers, blocking (jjs_msig_group_combine): format JJS_FORMAT_AFFINE (R, S: B n x 64) or JJS_FORMAT_EXT (B n x 96)
     void combine(int format, const uint8_t* z, const uint8_t* R, const uint8_t* S, const uint8_t* m, size_t n_transcripts, uint8_t* share_status,

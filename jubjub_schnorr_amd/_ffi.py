@@ -97,6 +97,20 @@ SIGNATURES = {
     "jjs_multisig_verify": [_I, _P, _P, _P, _P, _P, _Z, _P, _P, _P],
     "jjs_multisig_verify_keyset_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P],
     "jjs_multisig_verify_keyset": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P],
+    # the wire forms: the argument list of the affine twin, without `format`, with the one sig_w column where the twin has u, R
+    "jjs_multisig_combine_wire_dev": [_P, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P, _P],
+    "jjs_multisig_combine_wire": [_P, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P],
+    "jjs_msig_group_create_wire": [_P, _Z, _P],
+    "jjs_msig_group_combine_wire_dev": [ctypes.c_uint64, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P],
+    "jjs_msig_group_combine_wire": [ctypes.c_uint64, _P, _P, _P, _P, _Z, _P, _P, _P, _P],
+    "jjs_multisig_combine_keyset_wire_dev": [ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P, _P],
+    "jjs_multisig_combine_keyset_wire": [ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P],
+    "jjs_multisig_aggregate_pk_wire_dev": [_P, _P, _Z, _P, _P, _P],
+    "jjs_multisig_aggregate_pk_wire": [_P, _P, _Z, _P, _P],
+    "jjs_multisig_verify_wire_dev": [_P, _P, _P, _P, _Z, _P, _P, _P, _P],
+    "jjs_multisig_verify_wire": [_P, _P, _P, _P, _Z, _P, _P, _P],
+    "jjs_multisig_verify_keyset_wire_dev": [ctypes.c_uint64, _P, _P, _P, _P, _Z, _P, _P, _P, _P],
+    "jjs_multisig_verify_keyset_wire": [ctypes.c_uint64, _P, _P, _P, _P, _Z, _P, _P, _P],
     "jjs_multisig_round1_dev": [_P, _P, _Z, _P, _P, _P, _P],
     "jjs_multisig_sign_dev": [_I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _Z, _P, _P, _P],
     "jjs_multisig_sign": [_I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _Z, _P, _P],

@@ -257,7 +257,11 @@ class Engine:
         (jjs_multisig_combine[_ext]_dev), numpy arrays block (jjs_multisig_combine).  Returns
         (share_status (N,), agg_pk (B, 64), sig_u (B, 32), sig_R (B, 64), transcript_status (B,)); statuses 0 ok / 3 / 4;
         sig_u / sig_R are zero for a transcript whose status is not 0 (`combine` returns an error, not a signature)."""
-        w = self._msig_width(fmt)
+        return self._msig_combine(z, PK, R, S, m, offsets, fmt, False)
+
+    def _msig_combine(self, z, PK, R, S, m, offsets, fmt, _wire):
+        """`multisig_combine` (fmt) and `multisig_combine_wire` (_wire: the point columns are (N, 32))."""
+        w = 32 if _wire else self._msig_width(fmt)
         offs = np.ascontiguousarray(offsets, dtype=np.uint32)
         B, N = len(offs) - 1, z.shape[0]
         if not _is_torch(z):
@@ -267,8 +271,9 @@ class Engine:
             status, tstatus = np.zeros(N, np.uint8), np.zeros(B, np.uint8)
             agg, su, sr = np.zeros((B, 64), np.uint8), np.zeros((B, 32), np.uint8), np.zeros((B, 64), np.uint8)
             p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-            _ffi.check(self._lib.jjs_multisig_combine(self._FORMAT_IDS[fmt], p(hz), p(hpk), p(hr), p(hs), p(hm), p(offs), B, p(status),
-                                                      p(tstatus), p(agg), p(su), p(sr)), "jjs_multisig_combine")
+            name, head = ("jjs_multisig_combine_wire", []) if _wire else ("jjs_multisig_combine", [self._FORMAT_IDS[fmt]])
+            _ffi.check(getattr(self._lib, name)(*head, p(hz), p(hpk), p(hr), p(hs), p(hm), p(offs), B, p(status),
+                                                p(tstatus), p(agg), p(su), p(sr)), name)
             return status, agg, su, sr, tstatus
         import torch
         dev_ = z.device
@@ -277,26 +282,35 @@ class Engine:
         tstatus = torch.empty(max(B, 1), dtype=torch.uint8, device=dev_)[:B]
         agg, su, sr = new(B, 64), new(B, 32), new(B, 64)
         o = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        name = "jjs_multisig_combine_ext_dev" if fmt == "ext" else "jjs_multisig_combine_dev"
+        name = "jjs_multisig_combine_wire_dev" if _wire else "jjs_multisig_combine_ext_dev" if fmt == "ext" else "jjs_multisig_combine_dev"
         _ffi.check(getattr(self._lib, name)(self._dev_ptr(z, 32, N), self._dev_ptr(PK, w, N), self._dev_ptr(R, w, N),
                                             self._dev_ptr(S, w, N), self._dev_ptr(m, 32, B),
                                             offs.ctypes.data_as(ctypes.c_void_p), B, o(status), o(tstatus), o(agg), o(su),
                                             o(sr), self._stream()), name)
         return status, agg, su, sr, tstatus
 
-    def _msig_verifier(self, handle, keys, offsets, sig, fmt, want_status):
+    def multisig_combine_wire(self, z, PK_w, R_w, S_w, m, offsets):
+        """`multisig_combine` from the reference's wire bytes: PK_w / R_w / S_w (N, 32) = JubJubAffine::to_bytes, decoded on the
+        device (jjs_multisig_combine_wire_dev for torch CUDA tensors, the blocking jjs_multisig_combine_wire for numpy arrays).
+        The tuple of `multisig_combine` on the decoded columns, byte for byte; a share with an undecodable point gets status 3
+        and its transcript no signature.  agg_pk and sig_R are 64-byte affine (`compress` gives their wire bytes)."""
+        return self._msig_combine(z, PK_w, R_w, S_w, m, offsets, "affine", True)
+
+    def _msig_verifier(self, handle, keys, offsets, sig, fmt, want_status, _wire: bool = False):
         """The four verifier's calls (include/jjs_gpu.h "verifying aggregate multisignatures"): handle None for inline keys
-        (`keys` a PK column in `fmt`), a key-set handle for indices; sig None for aggregation alone, else (u, R, m)."""
-        w = self._msig_width(fmt)
-        fmt_id = self._FORMAT_IDS[fmt]
+        (`keys` a PK column in `fmt`), a key-set handle for indices; sig None for aggregation alone, else (u, R, m).  _wire: their
+        wire forms ("multisignature from wire encodings"): keys (N, 32), sig = (sig_w (B, 64) = u || R, m)."""
+        w = 32 if _wire else self._msig_width(fmt)
+        widths = (64, 32) if _wire else (32, w, 32)               # of the columns of `sig`
         offs = np.ascontiguousarray(offsets, dtype=np.uint32)
         B, N = len(offs) - 1, keys.shape[0]
         if B and int(offs[-1]) != N:
             raise ValueError("the key column does not have the rows the offsets ask for")
-        name = "jjs_multisig_" + ("verify" if sig is not None else "aggregate_pk") + ("_keyset" if handle is not None else "")
+        name = "jjs_multisig_" + ("verify" if sig is not None else "aggregate_pk") + ("_keyset" if handle is not None else "") + \
+            ("_wire" if _wire else "")
         head = [] if handle is None else [handle]
-        if handle is None or sig is not None:
-            head.append(fmt_id)
+        if not _wire and (handle is None or sig is not None):
+            head.append(self._FORMAT_IDS[fmt])
         po = offs.ctypes.data_as(ctypes.c_void_p)
         if not _is_torch(keys):
             p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
@@ -312,12 +326,12 @@ class Engine:
                 vst = np.zeros(B, np.uint8)
                 _ffi.check(getattr(self._lib, name)(*head, p(hk), po, B, p(agg), p(vst)), name)
                 return agg, vst
-            hu, hr, hm = self._host(sig[0], 32), self._host(sig[1], w), self._host(sig[2], 32)
-            if any(h.shape[0] != B for h in (hu, hr, hm)):
-                raise ValueError("u, R and m take one row per key vector")
+            hsig = [self._host(c, cw) for c, cw in zip(sig, widths)]
+            if any(h.shape[0] != B for h in hsig):
+                raise ValueError("the signature columns and m take one row per key vector")
             status = np.zeros(B, np.uint8) if want_status else None
             tally = np.zeros(4, np.uint64)
-            _ffi.check(getattr(self._lib, name)(*head, p(hk), po, p(hu), p(hr), p(hm), B, p(agg), p(status), p(tally)), name)
+            _ffi.check(getattr(self._lib, name)(*head, p(hk), po, *[p(h) for h in hsig], B, p(agg), p(status), p(tally)), name)
             return status, tally, agg
         import torch
         name += "_dev"
@@ -337,9 +351,25 @@ class Engine:
             return agg, vst
         status = torch.empty(max(B, 1), dtype=torch.uint8, device=dev_)[:B] if want_status else None
         tally = torch.zeros(4, dtype=torch.int64, device=dev_)
-        _ffi.check(getattr(self._lib, name)(*head, pk, po, self._dev_ptr(sig[0], 32, B), self._dev_ptr(sig[1], w, B),
-                                            self._dev_ptr(sig[2], 32, B), B, o(agg), o(status), o(tally), self._stream()), name)
+        _ffi.check(getattr(self._lib, name)(*head, pk, po, *[self._dev_ptr(c, cw, B) for c, cw in zip(sig, widths)], B, o(agg), o(status),
+                                            o(tally), self._stream()), name)
         return status, tally, agg
+
+    def multisig_aggregate_pk_wire(self, PK_w, offsets):
+        """`multisig_aggregate_pk` from wire keys: PK_w (N, 32) = PublicKey::to_bytes (jjs_multisig_aggregate_pk_wire[_dev]).
+        Returns (agg_pk (B, 64), vec_status (B,)); a vector with an undecodable key gets 3 and a zero aggregate."""
+        return self._msig_verifier(None, PK_w, offsets, None, "affine", True, _wire=True)
+
+    def multisig_verify_wire(self, PK_w, offsets, sig_w, m, want_status: bool = True):
+        """`multisig_verify` from wire bytes: PK_w (N, 32), sig_w (B, 64) = Signature::to_bytes = u || R, m (B, 32)
+        (jjs_multisig_verify_wire[_dev]).  Returns (status, tally, agg_pk): the statuses of `verify_wire("single", ...)` against
+        the aggregate, 3 for an undecodable R or an unusable key vector."""
+        return self._msig_verifier(None, PK_w, offsets, (sig_w, m), "affine", want_status, _wire=True)
+
+    def multisig_group_wire(self, PK_w) -> "SignerGroup":
+        """`multisig_group` from wire keys, (n, 32) = PublicKey::to_bytes (jjs_msig_group_create_wire): the group of the keys they
+        decode to; an undecodable key is refused."""
+        return SignerGroup(self, PK_w, _wire=True)
 
     def multisig_aggregate_pk(self, PK, offsets, fmt: str = "affine"):
         """Batch `aggregate_pk` (reference src/multisig.rs:154-156) over many key vectors: PK (N, 64) -- or (N, 96) with
@@ -914,10 +944,15 @@ class KeySet:
         `Engine.multisig_combine`, byte for byte what it gives with the registered keys in the PK column -- except that a
         transcript naming an index outside the set or a key whose `key_status` is not 0 is refused: status 3 on all its
         shares and on the transcript, agg_pk / sig_u / sig_R zero."""
+        return self._msig_combine(key_idx, z, R, S, m, offsets, fmt, False)
+
+    def _msig_combine(self, key_idx, z, R, S, m, offsets, fmt, _wire):
+        """`multisig_combine` (fmt) and `multisig_combine_wire` (_wire: R and S are (N, 32))."""
         if self.handle == 0:
             raise _ffi.JjsError("the key set is closed")
-        w = Engine._msig_width(fmt)
-        fmt_id = Engine._FORMAT_IDS[fmt]
+        w = 32 if _wire else Engine._msig_width(fmt)
+        head = [self.handle] if _wire else [self.handle, Engine._FORMAT_IDS[fmt]]
+        name = "jjs_multisig_combine_keyset_wire" if _wire else "jjs_multisig_combine_keyset"
         offs = np.ascontiguousarray(offsets, dtype=np.uint32)
         B, N = len(offs) - 1, z.shape[0]
         if not _is_torch(z):
@@ -932,8 +967,8 @@ class KeySet:
             status, tstatus = np.zeros(N, np.uint8), np.zeros(B, np.uint8)
             agg, su, sr = np.zeros((B, 64), np.uint8), np.zeros((B, 32), np.uint8), np.zeros((B, 64), np.uint8)
             p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-            _ffi.check(self._lib.jjs_multisig_combine_keyset(self.handle, fmt_id, p(hidx), p(hz), p(hr), p(hs), p(hm), p(offs), B, p(status),
-                                                             p(tstatus), p(agg), p(su), p(sr)), "jjs_multisig_combine_keyset")
+            _ffi.check(getattr(self._lib, name)(*head, p(hidx), p(hz), p(hr), p(hs), p(hm), p(offs), B, p(status),
+                                                p(tstatus), p(agg), p(su), p(sr)), name)
             return status, agg, su, sr, tstatus
         import torch
         if not (_is_torch(key_idx) and key_idx.is_cuda and key_idx.is_contiguous() and key_idx.shape == (N,)
@@ -946,10 +981,22 @@ class KeySet:
         agg, su, sr = new(B, 64), new(B, 32), new(B, 64)
         o = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         d = Engine._dev_ptr
-        _ffi.check(self._lib.jjs_multisig_combine_keyset_dev(self.handle, fmt_id, o(key_idx), d(z, 32, N), d(R, w, N), d(S, w, N),
-                                                             d(m, 32, B), offs.ctypes.data_as(ctypes.c_void_p), B, o(status), o(tstatus),
-                                                             o(agg), o(su), o(sr), Engine._stream()), "jjs_multisig_combine_keyset_dev")
+        _ffi.check(getattr(self._lib, name + "_dev")(*head, o(key_idx), d(z, 32, N), d(R, w, N), d(S, w, N),
+                                                     d(m, 32, B), offs.ctypes.data_as(ctypes.c_void_p), B, o(status), o(tstatus),
+                                                     o(agg), o(su), o(sr), Engine._stream()), name + "_dev")
         return status, agg, su, sr, tstatus
+
+    def multisig_combine_wire(self, key_idx, z, R_w, S_w, m, offsets):
+        """`multisig_combine` with R_w / S_w (N, 32) in the wire encoding, decoded on the device
+        (jjs_multisig_combine_keyset_wire[_dev]); a share with an undecodable point gets status 3."""
+        return self._msig_combine(key_idx, z, R_w, S_w, m, offsets, "affine", True)
+
+    def multisig_verify_wire(self, key_idx, offsets, sig_w, m, want_status: bool = True):
+        """`multisig_verify` with the aggregate signature as sig_w (B, 64) = u || R (jjs_multisig_verify_keyset_wire[_dev]).
+        Returns (status, tally, agg_pk)."""
+        if self.handle == 0:
+            raise _ffi.JjsError("the key set is closed")
+        return self._eng._msig_verifier(self.handle, key_idx, offsets, (sig_w, m), "affine", want_status, _wire=True)
 
     def multisig_aggregate_pk(self, key_idx, offsets):
         """`Engine.multisig_aggregate_pk` with the keys named by index into this set (scheme "single"): key_idx (N,) uint32.  A
@@ -990,11 +1037,11 @@ class SignerGroup:
     `close()` destroys the group (queued device calls still complete)."""
     INFO_NAMES = ("participants", "window_bits", "device_bytes", "calls")
 
-    def __init__(self, eng: Engine, PK, fmt: str = "affine"):
+    def __init__(self, eng: Engine, PK, fmt: str = "affine", _wire: bool = False):
         self._eng, self._lib = eng, eng._lib
-        pk = eng._host(PK, Engine._msig_width(fmt))
+        pk = eng._host(PK, 32 if _wire else Engine._msig_width(fmt))
         h = ctypes.c_uint64(0)
-        name = "jjs_msig_group_create_ext" if fmt == "ext" else "jjs_msig_group_create"
+        name = "jjs_msig_group_create_wire" if _wire else "jjs_msig_group_create_ext" if fmt == "ext" else "jjs_msig_group_create"
         _ffi.check(getattr(self._lib, name)(pk.ctypes.data_as(ctypes.c_void_p) if len(pk) else None, len(pk), ctypes.byref(h)), name)
         self.handle = h.value
         self.participants = len(pk)
@@ -1002,12 +1049,21 @@ class SignerGroup:
         _ffi.check(self._lib.jjs_msig_group_aggregate_pk(self.handle, self.aggregate_pk.ctypes.data_as(ctypes.c_void_p)),
                    "jjs_msig_group_aggregate_pk")
 
+    def combine_wire(self, z, R_w, S_w, m):
+        """`combine` with R_w / S_w (B n, 32) in the wire encoding, decoded on the device (jjs_msig_group_combine_wire[_dev]); a
+        share with an undecodable point gets status 3."""
+        return self._combine(z, R_w, S_w, m, "affine", True)
+
     def combine(self, z, R, S, m, fmt: str = "affine"):
         """Batch `verify_share` + `combine` over B transcripts of the group's n participants: z (B n, 32), R / S (B n, 64) -- or
         (B n, 96) = U || V || Z with fmt="ext" -- m (B, 32), share (t, i) at row t n + i.  torch CUDA uint8 tensors run
         asynchronously on the current stream, numpy arrays block (jjs_msig_group_combine).  Returns (share_status (B n,),
         sig_u (B, 32), sig_R (B, 64), transcript_status (B,)): the tuple of `Engine.multisig_combine` without agg_pk, byte for byte."""
-        w = Engine._msig_width(fmt)
+        return self._combine(z, R, S, m, fmt, False)
+
+    def _combine(self, z, R, S, m, fmt, _wire):
+        """`combine` (fmt) and `combine_wire` (_wire: R and S are (B n, 32))."""
+        w = 32 if _wire else Engine._msig_width(fmt)
         B = m.shape[0]
         N = B * self.participants
         if not _is_torch(z):
@@ -1018,8 +1074,9 @@ class SignerGroup:
             status, tstatus = np.zeros(N, np.uint8), np.zeros(B, np.uint8)
             su, sr = np.zeros((B, 32), np.uint8), np.zeros((B, 64), np.uint8)
             p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-            _ffi.check(self._lib.jjs_msig_group_combine(self.handle, Engine._FORMAT_IDS[fmt], p(hz), p(hr), p(hs), p(hm), B, p(status),
-                                                        p(tstatus), p(su), p(sr)), "jjs_msig_group_combine")
+            name, head = ("jjs_msig_group_combine_wire", []) if _wire else ("jjs_msig_group_combine", [Engine._FORMAT_IDS[fmt]])
+            _ffi.check(getattr(self._lib, name)(self.handle, *head, p(hz), p(hr), p(hs), p(hm), B, p(status),
+                                                p(tstatus), p(su), p(sr)), name)
             return status, su, sr, tstatus
         import torch
         dev_ = z.device
@@ -1029,7 +1086,7 @@ class SignerGroup:
         su, sr = new(B, 32), new(B, 64)
         o = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         d = Engine._dev_ptr
-        name = "jjs_msig_group_combine_ext_dev" if fmt == "ext" else "jjs_msig_group_combine_dev"
+        name = "jjs_msig_group_combine_wire_dev" if _wire else "jjs_msig_group_combine_ext_dev" if fmt == "ext" else "jjs_msig_group_combine_dev"
         _ffi.check(getattr(self._lib, name)(self.handle, d(z, 32, N), d(R, w, N), d(S, w, N), d(m, 32, B), B, o(status),
                                             o(tstatus), o(su), o(sr), Engine._stream()), name)
         return status, su, sr, tstatus

@@ -15,7 +15,7 @@
 // exponentiation y^((t-1)/2) plus the 2-adic correction, done a byte at a time with table lookups
 // (48 squarings and ~14 products instead of the ~500 squarings of the textbook loop).
 #pragma once
-#include "ed29.h"
+#include "verify_core.h"
 
 namespace jjs {
 
@@ -145,6 +145,48 @@ JJS_HD decoded_point decompress_point(const words8& bytes, const dlog_tables& T)
     }
     out.ok = ok;
     return out;
+}
+
+// Poison mode (the multisignature calls from wire encodings, the twin of normalize.h's): the consumer validates no points and has
+// no flag column, only a range test of every coordinate (msig_share_item).  An encoding that does not decode -- by the rules of
+// decompress_point, unchanged -- comes out as 64 bytes of 0xFF, which that range test turns into status 3; a decodable one as
+// the canonical affine u || v of decompress_point.
+struct msig_decode_params {
+    uint32_t n_src, pad_;
+    fe_src src[3];        // compressed points: 32 bytes at base + i*stride + off (stride 64, off 32: the R half of u || R rows)
+    uint8_t* out[3];      // affine u || v or the poison, n x 64 each
+    uint64_t n;           // rows
+    dlog_tables dlog;
+};
+JJS_HD void decompress_point_poison(const words8& bytes, const dlog_tables& T, words8& u, words8& v) {
+    const decoded_point d = decompress_point(bytes, T);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        u.w[i] = d.ok ? d.u.w[i] : ~0u;
+        v.w[i] = d.ok ? d.v.w[i] : ~0u;
+    }
+}
+// All points of one lane: point j = lane, lane + lanes, ... of the n * n_src points of the call, point j being source j % n_src
+// of row j / n_src -- one lane per (row, column), so that a call of few rows waits for one square root and not for n_src.
+JJS_HD void msig_decode_lane(const msig_decode_params& P, uint64_t lane, uint64_t lanes) {
+    for (uint64_t j = lane; j < P.n * P.n_src; j += lanes) {
+        const uint64_t item = j / P.n_src;
+        const uint32_t k = (uint32_t)(j % P.n_src);
+        // source and destination chosen field by field: indexing the kernel-argument struct with a run-time index would
+        // make the compiler copy it to scratch memory
+        fe_src src = P.src[0];
+        uint8_t* out = P.out[0];
+#pragma unroll
+        for (uint32_t c = 1; c < 3; ++c) {
+            const bool me = k == c;
+            src.base = me ? P.src[c].base : src.base; src.stride = me ? P.src[c].stride : src.stride; src.off = me ? P.src[c].off : src.off;
+            out = me ? P.out[c] : out;
+        }
+        words8 u, v;
+        decompress_point_poison(load_words(src, item), P.dlog, u, v);
+        store_words(out, 2 * item, u);
+        store_words(out, 2 * item + 1, v);
+    }
 }
 
 // affine canonical (u, v) -> 32-byte compressed form

@@ -576,6 +576,13 @@ __global__ __launch_bounds__(BLOCK) void msig_normalize_kernel(normalize_params 
     __builtin_amdgcn_s_setprio(3);            // as above: every pass of the call waits for these few waves
     normalize_lane<true>(P, (uint64_t)blockIdx.x * BLOCK + threadIdx.x, (uint64_t)gridDim.x * BLOCK);
 }
+// Wire encodings for the multisignature calls, in poison mode (decode.h msig_decode_lane): one lane per (row, column); an
+// encoding that does not decode comes out as 64 bytes of 0xFF and no flag is written.  A kernel of its own: the decoders and the
+// normalisation kernels keep their code and their registers.
+__global__ __launch_bounds__(BLOCK) void msig_decode_kernel(msig_decode_params P) {
+    __builtin_amdgcn_s_setprio(3);            // as msig_normalize_kernel: every pass of the call waits for these waves
+    msig_decode_lane(P, (uint64_t)blockIdx.x * BLOCK + threadIdx.x, (uint64_t)gridDim.x * BLOCK);
+}
 __global__ __launch_bounds__(BLOCK) void compress_kernel(const uint8_t* affine, uint64_t n, uint8_t* out) {
     uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;

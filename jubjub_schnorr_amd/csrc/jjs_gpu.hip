@@ -802,9 +802,9 @@ int jjs_compress_dev(const void* affine, size_t n, void* out, void* stream) {
 // ---- multisig: batch verify_share / combine -------------------------------------------
 // The device's multisignature scratch (g->msig, grow-only; sized for g->msig_items shares in g->msig_transcripts transcripts),
 // in words: tr_of (1), d_words (8), dpk and e_pt (EXT_WORDS each) per share, then a_words and c_words (8 each), the offsets
-// (1, and one more) and the long tags (18) per transcript.  Behind them, once an *_ext call has asked for it (g->msig_ext_rows
-// rows; affine callers never pay for it): three columns of normalised points (64 bytes per row each) and the 9 words of prefix
-// product per row that normalize_lane keeps.  Behind those, once a key-set call (msig_keyset.h) has asked for it (g->msig_ks_rows
+// (1, and one more) and the long tags (18) per transcript.  Behind them, once an *_ext or *_wire call has asked for it (g->msig_ext_rows
+// rows; affine callers never pay for it): three columns of normalised or decoded points (64 bytes per row each) and the 9 words
+// of prefix product per row that normalize_lane keeps.  Behind those, once a key-set call (msig_keyset.h) has asked for it (g->msig_ks_rows
 // rows in g->msig_ks_transcripts transcripts; no other caller pays for it): the gathered key column (64 bytes per row), the
 // table index of every row (4) and the refused word of every transcript (4).  Behind those, once a signing call (msig_sign.h) has
 // asked for it (g->msig_sign_rows rows in g->msig_sign_transcripts transcripts; no other caller pays for it): the flag words of the
@@ -892,6 +892,33 @@ static int msig_normalize(const msig_scratch& W, const uint8_t** col, uint32_t c
     }
     return launch_normalize(N, 0, n, n, s);
 }
+// The decoding in front of the passes of a wire call: `cols` columns of n rows (32 bytes a point, column k at src[k]) into out[k],
+// one lane per (row, column), in poison mode (decode.h).
+static int launch_msig_decode(msig_decode_params D, size_t n, hipStream_t s) {
+    if (!D.n_src || !n) return JJS_OK;
+    D.n = n;
+    D.dlog = dlog_tables{g->dlog_pow, g->dlog_hash};
+    hipLaunchKernelGGL(msig_decode_kernel, dim3((unsigned)grid_for(8192, n * D.n_src)), dim3(BLOCK), 0, s, D);
+    HIP_TRY(hipGetLastError());
+    return JJS_OK;
+}
+// ... of packed columns into the scratch's normalised columns; col[] is re-aimed at them (the contract of msig_normalize).
+static int msig_decode(const msig_scratch& W, const uint8_t** col, uint32_t cols, size_t n, hipStream_t s) {
+    msig_decode_params D{};
+    D.n_src = cols;
+    for (uint32_t k = 0; k < cols; ++k) {
+        D.src[k] = fe_src{col[k], 32, 0};
+        D.out[k] = W.norm[k];
+        col[k] = W.norm[k];
+    }
+    return launch_msig_decode(D, n, s);
+}
+// the point columns of a call in format fmt (JJS_FORMAT_*) made affine in the scratch; an affine call keeps its columns
+static int msig_ingest(int fmt, const msig_scratch& W, const uint8_t** col, uint32_t cols, size_t n, hipStream_t s) {
+    if (fmt == JJS_FORMAT_EXT) return msig_normalize(W, col, cols, n, s);
+    if (fmt == JJS_FORMAT_WIRE) return msig_decode(W, col, cols, n, s);
+    return JJS_OK;
+}
 // n = the shares of a call whose host offsets are acceptable
 static int msig_check_offsets(const uint32_t* offsets_host, size_t n_transcripts, size_t& n) {
     if (!offsets_host || offsets_host[0] != 0) return fail(JJS_ERR_ARG, "offsets must start at 0");
@@ -908,14 +935,15 @@ static int msig_check_offsets(const uint32_t* offsets_host, size_t n_transcripts
     n = offsets_host[n_transcripts];
     return JJS_OK;
 }
-// The call on device columns, queued on s (under the engine's mutex, g the device; n_transcripts > 0).  ext: PK, R, S are N x 96.
-static int msig_combine_locked(bool ext, const void* z, const void* PK, const void* R, const void* S, const void* m,
+// The call on device columns, queued on s (under the engine's mutex, g the device; n_transcripts > 0).  fmt (JJS_FORMAT_*): PK, R, S are
+// N x 64, N x 96 or N x 32.
+static int msig_combine_locked(int fmt, const void* z, const void* PK, const void* R, const void* S, const void* m,
                                const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
                                void* agg_pk, void* sig_u, void* sig_R, hipStream_t s) {
     size_t n = 0;
     if (int rc = msig_check_offsets(offsets_host, n_transcripts, n)) return rc;
     if ((n && !all_ok(z, PK, R, S)) || !all_ok(m, agg_pk, sig_u, sig_R) || (n && !share_status)) return fail(JJS_ERR_ARG, "null or misaligned pointer");
-    if (int rc = ensure_msig_scratch(n, n_transcripts, ext ? n : 0)) return rc;
+    if (int rc = ensure_msig_scratch(n, n_transcripts, fmt != JJS_FORMAT_AFFINE ? n : 0)) return rc;
     const msig_scratch W = msig_scratch_carve();
     const uint8_t* pts[3] = {(const uint8_t*)PK, (const uint8_t*)R, (const uint8_t*)S};
     msig_params P{};
@@ -932,8 +960,7 @@ static int msig_combine_locked(bool ext, const void* z, const void* PK, const vo
     if (int rc = begin_shared(s)) return rc;
     auto queue = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(W.offsets, offsets_host, (n_transcripts + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        if (ext)
-            if (int rc = msig_normalize(W, pts, 3, n, s)) return rc;
+        if (int rc = msig_ingest(fmt, W, pts, 3, n, s)) return rc;
         P.PK = pts[0]; P.R = pts[1]; P.S = pts[2];
         for (int pass = 0; pass < 7; ++pass) {
             const size_t count = (pass == 0 || pass == 2 || pass == 4 || pass == 6) ? n_transcripts : n;
@@ -954,7 +981,7 @@ int jjs_multisig_combine_dev(const void* z, const void* PK, const void* R, const
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
     if (n_transcripts == 0) return JJS_OK;
-    return msig_combine_locked(false, z, PK, R, S, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk, sig_u, sig_R,
+    return msig_combine_locked(JJS_FORMAT_AFFINE, z, PK, R, S, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk, sig_u, sig_R,
                                (hipStream_t)stream);
 }
 int jjs_multisig_combine_ext_dev(const void* z, const void* PK_ext, const void* R_ext, const void* S_ext, const void* m,
@@ -963,8 +990,34 @@ int jjs_multisig_combine_ext_dev(const void* z, const void* PK_ext, const void* 
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
     if (n_transcripts == 0) return JJS_OK;
-    return msig_combine_locked(true, z, PK_ext, R_ext, S_ext, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk, sig_u,
-                               sig_R, (hipStream_t)stream);
+    return msig_combine_locked(JJS_FORMAT_EXT, z, PK_ext, R_ext, S_ext, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk,
+                               sig_u, sig_R, (hipStream_t)stream);
+}
+int jjs_multisig_combine_wire_dev(const void* z, const void* PK_w, const void* R_w, const void* S_w, const void* m,
+                                  const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
+                                  void* agg_pk, void* sig_u, void* sig_R, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    if (n_transcripts == 0) return JJS_OK;
+    return msig_combine_locked(JJS_FORMAT_WIRE, z, PK_w, R_w, S_w, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk,
+                               sig_u, sig_R, (hipStream_t)stream);
+}
+
+// The square-root tables of decode.h on the host, built once by dlog_table_entry after a cleared hash, as the device builds its
+// own: jjs_msig_group_create_wire decodes the keys of a group before it registers them.
+static const dlog_tables& host_dlog_tables() {
+    struct built {
+        std::vector<uint32_t> pow;
+        std::vector<uint8_t> hash;
+        dlog_tables T;
+        built() : pow(DLOG_POW_WORDS, 0u), hash(65536, 0) {
+            for (int i = 0; i < 7; ++i)
+                for (int j = 0; j < 256; ++j) dlog_table_entry(pow.data(), hash.data(), i, j);
+            T = dlog_tables{pow.data(), hash.data()};
+        }
+    };
+    static const built b;
+    return b.T;
 }
 
 #include "msig_group_calls.h"

@@ -66,6 +66,20 @@ JJS_HD bool mg_ext_keys_usable(const uint8_t* PK_ext, uint64_t n) {
     }
     return ok;
 }
+// the same for keys in the wire encoding (n x 32): every key decodes (decode.h decompress_point, on the host with tables built
+// there); out receives the n x 64 affine keys, which jjs_msig_group_create_wire registers
+JJS_HD bool mg_wire_keys_decode(const uint8_t* PK_w, uint64_t n, const dlog_tables& T, uint8_t* out) {
+    if (!PK_w || n == 0) return false;
+    const fe_src pk{PK_w, 32, 0};
+    bool ok = true;
+    for (uint64_t i = 0; i < n; ++i) {
+        const decoded_point d = decompress_point(load_words(pk, i), T);
+        ok = ok && d.ok;
+        store_words(out, 2 * i, d.u);
+        store_words(out, 2 * i + 1, d.v);
+    }
+    return ok;
+}
 
 // ---- registration ------------------------------------------------------------------------------------------------------------
 // (d_j and D_j = d_j * PK_j: msig_delin_item on a one-transcript msig_params; agg_pk: sum_points_affine over the D_j)

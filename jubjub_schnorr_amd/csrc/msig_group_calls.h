@@ -63,8 +63,11 @@ static int msig_group_build_copy(msig_group_entry& k, msig_group_copy& c, const 
     });
 }
 
-// jjs_msig_group_create / _ext: PK is n x 64 affine, or n x 96 extended
-static int msig_group_create(const uint8_t* PK, bool ext, size_t n, jjs_msig_group* out) {
+// jjs_msig_group_create / _ext / _wire: PK is n x 64 affine, n x 96 extended, or n x 32 compressed.  Wire keys are decoded here, on
+// the host (mg_wire_keys_decode: the refusal of an undecodable key comes before anything is built), and registered as the affine
+// keys they decode to.
+static int msig_group_create(const uint8_t* PK, int fmt, size_t n, jjs_msig_group* out) {
+    const bool ext = fmt == JJS_FORMAT_EXT, wire = fmt == JJS_FORMAT_WIRE;
     registration<msig_group_entry> call;
     if (int rc = call.enter([&] {
             if (!out || !PK || n == 0) return fail(JJS_ERR_ARG, "a signer group needs at least one key and an output handle");
@@ -73,15 +76,22 @@ static int msig_group_create(const uint8_t* PK, bool ext, size_t n, jjs_msig_gro
         }))
         return rc;
     msig_group_entry& k = *call.e;
-    const size_t width = ext ? 96 : 64;
-    std::vector<u32x4> keys;                // the caller's bytes, aligned for the range test
+    const size_t width = ext ? 96 : (wire ? 32 : 64);
+    std::vector<u32x4> keys, decoded;       // the caller's bytes, aligned for the range test; the affine keys of a wire vector
+    bool wire_ok = true;
     if (int rc = no_throw([&]() -> int {
             keys.resize(n * width / 16);
             memcpy(keys.data(), PK, n * width);
+            if (wire) {
+                decoded.resize(n * 4);
+                wire_ok = mg_wire_keys_decode(reinterpret_cast<const uint8_t*>(keys.data()), n, host_dlog_tables(),
+                                              reinterpret_cast<uint8_t*>(decoded.data()));
+            }
             return JJS_OK;
         }))
         return rc;
-    const uint8_t* pk = reinterpret_cast<const uint8_t*>(keys.data());
+    const uint8_t* pk = reinterpret_cast<const uint8_t*>(wire ? decoded.data() : keys.data());
+    if (!wire_ok) return fail(JJS_ERR_ARG, "the encoding of a key does not decode");
     if (ext ? !mg_ext_keys_usable(pk, n) : !mg_keys_acceptable(pk, n))
         return fail(JJS_ERR_ARG, ext ? "a key is unusable: a coordinate is not below q, or Z is zero" : "a coordinate of a key is not below q");
     k.participants = (uint32_t)n;
@@ -97,8 +107,9 @@ static int msig_group_create(const uint8_t* PK, bool ext, size_t n, jjs_msig_gro
 
 extern "C" {
 
-int jjs_msig_group_create(const uint8_t* PK, size_t n, jjs_msig_group* out) { return msig_group_create(PK, false, n, out); }
-int jjs_msig_group_create_ext(const uint8_t* PK_ext, size_t n, jjs_msig_group* out) { return msig_group_create(PK_ext, true, n, out); }
+int jjs_msig_group_create(const uint8_t* PK, size_t n, jjs_msig_group* out) { return msig_group_create(PK, JJS_FORMAT_AFFINE, n, out); }
+int jjs_msig_group_create_ext(const uint8_t* PK_ext, size_t n, jjs_msig_group* out) { return msig_group_create(PK_ext, JJS_FORMAT_EXT, n, out); }
+int jjs_msig_group_create_wire(const uint8_t* PK_w, size_t n, jjs_msig_group* out) { return msig_group_create(PK_w, JJS_FORMAT_WIRE, n, out); }
 
 int jjs_msig_group_destroy(jjs_msig_group h) {
     std::lock_guard<std::mutex> lock(L.mu);
@@ -130,8 +141,9 @@ int jjs_msig_group_aggregate_pk(jjs_msig_group h, uint8_t out[64]) {
     return JJS_OK;
 }
 
-// The call against group h on device columns, queued on s (under the engine's mutex, g the device).  ext: R, S are B n x 96.
-static int msig_group_combine_locked(jjs_msig_group h, bool ext, const void* z, const void* R, const void* S, const void* m, size_t n_transcripts,
+// The call against group h on device columns, queued on s (under the engine's mutex, g the device).  fmt (JJS_FORMAT_*): R, S are
+// B n x 64, B n x 96 or B n x 32.
+static int msig_group_combine_locked(jjs_msig_group h, int fmt, const void* z, const void* R, const void* S, const void* m, size_t n_transcripts,
                                      void* share_status, void* transcript_status, void* sig_u, void* sig_R, hipStream_t s) {
     msig_group_entry* k = g_msig_groups.find(h);
     if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed signer group");
@@ -143,7 +155,7 @@ static int msig_group_combine_locked(jjs_msig_group h, bool ext, const void* z, 
     if (!all_ok(z, R, S, m, sig_u, sig_R) || !share_status) return fail(JJS_ERR_ARG, "null or misaligned pointer");
     const msig_group_copy* c = copy_for(*k, g);
     if (!c) return fail(JJS_ERR_ARG, "the signer group has no copy on this device");
-    if (int rc = ensure_msig_scratch(n, n_transcripts, ext ? n : 0)) return rc;
+    if (int rc = ensure_msig_scratch(n, n_transcripts, fmt != JJS_FORMAT_AFFINE ? n : 0)) return rc;
     const uint8_t* pts[2] = {(const uint8_t*)R, (const uint8_t*)S};
     msig_group_params G{};
     msig_params& P = G.M;
@@ -164,8 +176,7 @@ static int msig_group_combine_locked(jjs_msig_group h, bool ext, const void* z, 
     ++k->calls;
     big_slot();
     if (int rc = begin_shared(s)) return rc;
-    int rc_norm = JJS_OK;
-    if (ext) rc_norm = msig_normalize(W, pts, 2, n, s);
+    const int rc_norm = msig_ingest(fmt, W, pts, 2, n, s);
     P.R = pts[0]; P.S = pts[1];
     for (int pass = 0; pass < 5 && !rc_norm; ++pass) {
         if (pass == 3) {
@@ -188,13 +199,21 @@ int jjs_msig_group_combine_dev(jjs_msig_group h, const void* z, const void* R, c
                                void* share_status, void* transcript_status, void* sig_u, void* sig_R, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
-    return msig_group_combine_locked(h, false, z, R, S, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, (hipStream_t)stream);
+    return msig_group_combine_locked(h, JJS_FORMAT_AFFINE, z, R, S, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, (hipStream_t)stream);
 }
 int jjs_msig_group_combine_ext_dev(jjs_msig_group h, const void* z, const void* R_ext, const void* S_ext, const void* m, size_t n_transcripts,
                                    void* share_status, void* transcript_status, void* sig_u, void* sig_R, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
-    return msig_group_combine_locked(h, true, z, R_ext, S_ext, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, (hipStream_t)stream);
+    return msig_group_combine_locked(h, JJS_FORMAT_EXT, z, R_ext, S_ext, m, n_transcripts, share_status, transcript_status, sig_u, sig_R,
+                                     (hipStream_t)stream);
+}
+int jjs_msig_group_combine_wire_dev(jjs_msig_group h, const void* z, const void* R_w, const void* S_w, const void* m, size_t n_transcripts,
+                                    void* share_status, void* transcript_status, void* sig_u, void* sig_R, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    return msig_group_combine_locked(h, JJS_FORMAT_WIRE, z, R_w, S_w, m, n_transcripts, share_status, transcript_status, sig_u, sig_R,
+                                     (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -45,20 +45,28 @@ static int msig_format(int format, bool& ext) {
     ext = format == JJS_FORMAT_EXT;
     return JJS_OK;
 }
-}  // extern "C++"
+// bytes of a point in the columns of a call in format fmt (JJS_FORMAT_*)
+static size_t msig_point_bytes(int fmt) { return fmt == JJS_FORMAT_EXT ? 96 : (fmt == JJS_FORMAT_WIRE ? 32 : 64); }
+// the format of a call: that of a *_wire entry point (wire), which has no format argument to refuse, or the one `format` names
+static int msig_call_format(int format, bool wire, int& fmt) {
+    bool ext = false;
+    fmt = JJS_FORMAT_WIRE;
+    if (wire) return JJS_OK;
+    if (int rc = msig_format(format, ext)) return rc;
+    fmt = ext ? JJS_FORMAT_EXT : JJS_FORMAT_AFFINE;
+    return JJS_OK;
+}
 
-extern "C" {
-
-int jjs_multisig_combine(int format, const uint8_t* z, const uint8_t* PK, const uint8_t* R, const uint8_t* S, const uint8_t* m,
+static int msig_combine_host(int format, bool wire, const uint8_t* z, const uint8_t* PK, const uint8_t* R, const uint8_t* S, const uint8_t* m,
                          const uint32_t* offsets, size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status,
                          uint8_t* agg_pk, uint8_t* sig_u, uint8_t* sig_R) {
     device_state* dev = nullptr;
-    bool ext = false;
+    int fmt = JJS_FORMAT_AFFINE;
     size_t n = 0;
     {
         std::lock_guard<std::mutex> lock(L.mu);
         if (int rc = check_ready()) return rc;
-        if (int rc = msig_format(format, ext)) return rc;
+        if (int rc = msig_call_format(format, wire, fmt)) return rc;
         if (n_transcripts == 0) return JJS_OK;
         if (int rc = msig_check_offsets(offsets, n_transcripts, n)) return rc;
         if ((n && (!z || !PK || !R || !S || !share_status)) || !m || !agg_pk || !sig_u || !sig_R) return fail(JJS_ERR_ARG, "null pointer");
@@ -69,7 +77,7 @@ int jjs_multisig_combine(int format, const uint8_t* z, const uint8_t* PK, const 
     std::lock_guard<std::mutex> big(dev->host_mu);
     g = dev;
     return no_throw([&]() -> int {
-        const size_t B = n_transcripts, w = ext ? 96 : 64;
+        const size_t B = n_transcripts, w = msig_point_bytes(fmt);
         const void* src[5] = {z, PK, R, S, m};
         const size_t in_bytes[5] = {n * 32, n * w, n * w, n * w, B * 32}, out_bytes[5] = {n, B, B * 64, B * 32, B * 64};
         msig_stage St{};
@@ -77,7 +85,7 @@ int jjs_multisig_combine(int format, const uint8_t* z, const uint8_t* PK, const 
         {
             std::lock_guard<std::mutex> lock(L.mu);
             if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
-            if (int rc = msig_combine_locked(ext, St.in[0], St.in[1], St.in[2], St.in[3], St.in[4], offsets, B, St.out[0],
+            if (int rc = msig_combine_locked(fmt, St.in[0], St.in[1], St.in[2], St.in[3], St.in[4], offsets, B, St.out[0],
                                              transcript_status ? St.out[1] : nullptr, St.out[2], St.out[3], St.out[4], St.s))
                 return rc;
         }
@@ -86,17 +94,17 @@ int jjs_multisig_combine(int format, const uint8_t* z, const uint8_t* PK, const 
     });
 }
 
-int jjs_msig_group_combine(jjs_msig_group h, int format, const uint8_t* z, const uint8_t* R, const uint8_t* S, const uint8_t* m,
+static int msig_group_combine_host(jjs_msig_group h, int format, bool wire, const uint8_t* z, const uint8_t* R, const uint8_t* S, const uint8_t* m,
                            size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status, uint8_t* sig_u, uint8_t* sig_R) {
     device_state* dev = nullptr;
-    bool ext = false;
+    int fmt = JJS_FORMAT_AFFINE;
     size_t n = 0;
     {
         std::lock_guard<std::mutex> lock(L.mu);
         if (int rc = check_ready()) return rc;
         msig_group_entry* k = g_msig_groups.find(h);
         if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed signer group");
-        if (int rc = msig_format(format, ext)) return rc;
+        if (int rc = msig_call_format(format, wire, fmt)) return rc;
         if (n_transcripts == 0) return JJS_OK;
         const uint64_t per = k->participants;
         if (n_transcripts >= (1ull << 32) / per + ((1ull << 32) % per ? 1u : 0u))
@@ -110,7 +118,7 @@ int jjs_msig_group_combine(jjs_msig_group h, int format, const uint8_t* z, const
     std::lock_guard<std::mutex> big(dev->host_mu);
     g = dev;
     return no_throw([&]() -> int {
-        const size_t B = n_transcripts, w = ext ? 96 : 64;
+        const size_t B = n_transcripts, w = msig_point_bytes(fmt);
         const void* src[5] = {z, nullptr, R, S, m};
         const size_t in_bytes[5] = {n * 32, 0, n * w, n * w, B * 32}, out_bytes[5] = {n, B, 0, B * 32, B * 64};
         msig_stage St{};
@@ -121,13 +129,37 @@ int jjs_msig_group_combine(jjs_msig_group h, int format, const uint8_t* z, const
             // (the group is looked up again: it may have been destroyed, or registered with other participants, meanwhile)
             msig_group_entry* k = g_msig_groups.find(h);
             if (!k || (size_t)k->participants * B != n) return fail(JJS_ERR_ARG, "the signer group was destroyed during the call");
-            if (int rc = msig_group_combine_locked(h, ext, St.in[0], St.in[2], St.in[3], St.in[4], B, St.out[0],
+            if (int rc = msig_group_combine_locked(h, fmt, St.in[0], St.in[2], St.in[3], St.in[4], B, St.out[0],
                                                    transcript_status ? St.out[1] : nullptr, St.out[3], St.out[4], St.s))
                 return rc;
         }
         uint8_t* const dst[5] = {share_status, transcript_status, nullptr, sig_u, sig_R};
         return msig_stage_out(St, dst, out_bytes);
     });
+}
+
+}  // extern "C++"
+
+extern "C" {
+
+int jjs_multisig_combine(int format, const uint8_t* z, const uint8_t* PK, const uint8_t* R, const uint8_t* S, const uint8_t* m,
+                         const uint32_t* offsets, size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status,
+                         uint8_t* agg_pk, uint8_t* sig_u, uint8_t* sig_R) {
+    return msig_combine_host(format, false, z, PK, R, S, m, offsets, n_transcripts, share_status, transcript_status, agg_pk, sig_u, sig_R);
+}
+int jjs_multisig_combine_wire(const uint8_t* z, const uint8_t* PK_w, const uint8_t* R_w, const uint8_t* S_w, const uint8_t* m,
+                              const uint32_t* offsets, size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status,
+                              uint8_t* agg_pk, uint8_t* sig_u, uint8_t* sig_R) {
+    return msig_combine_host(JJS_FORMAT_WIRE, true, z, PK_w, R_w, S_w, m, offsets, n_transcripts, share_status, transcript_status, agg_pk, sig_u,
+                             sig_R);
+}
+int jjs_msig_group_combine(jjs_msig_group h, int format, const uint8_t* z, const uint8_t* R, const uint8_t* S, const uint8_t* m,
+                           size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status, uint8_t* sig_u, uint8_t* sig_R) {
+    return msig_group_combine_host(h, format, false, z, R, S, m, n_transcripts, share_status, transcript_status, sig_u, sig_R);
+}
+int jjs_msig_group_combine_wire(jjs_msig_group h, const uint8_t* z, const uint8_t* R_w, const uint8_t* S_w, const uint8_t* m,
+                                size_t n_transcripts, uint8_t* share_status, uint8_t* transcript_status, uint8_t* sig_u, uint8_t* sig_R) {
+    return msig_group_combine_host(h, JJS_FORMAT_WIRE, true, z, R_w, S_w, m, n_transcripts, share_status, transcript_status, sig_u, sig_R);
 }
 
 }  // extern "C"

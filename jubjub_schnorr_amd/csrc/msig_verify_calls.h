@@ -6,18 +6,31 @@
 // own choosing and reads the aggregate from the caller's memory, but in the extended format its R column is the normalised
 // one in that scratch.  So slot 0's event is recorded only after the verification's launches and the clear pass have been
 // queued: the scratch's next user, on whatever stream, waits for all of them.
+// The wire format: the keys and R are decoded into those columns (msig_decode_kernel), R out of the R half of the u || R rows;
+// the resident single-scheme call reads packed columns, so u is copied out of its half of the rows into the column behind R's.
 
 extern "C++" {
 struct mv_call {
-    bool keyset, ext, verify;             // ext: the inline form's PK and R, the key-set form's R
+    bool keyset, verify;
+    int fmt;                              // JJS_FORMAT_*: of the inline form's PK and R, of the key-set form's R.  Wire: u and R are
+                                          // the two halves of the B x 64 signature rows (u = sig_w, R = sig_w + 32, stride 64)
     const keyset_entry* k;                // the key-set form: the set and its copy on the device
     const keyset_copy* c;
-    const void *keys;                     // PK (N x 64 / N x 96) or key_idx (N x uint32)
+    const void *keys;                     // PK (N x 64 / N x 96 / N x 32) or key_idx (N x uint32)
     const void *u, *R, *m;                // a verification call
     void *agg_pk, *vec_status, *status, *tally;
 };
-// one column of `rows` extended points into normalised column `slot` of the scratch, in poison mode; col is re-aimed at it
-static int mv_normalize(const msig_scratch& W, const uint8_t*& col, int slot, size_t rows, hipStream_t s) {
+// one column of `rows` points in format fmt (extended, or wire at `wire_stride` bytes a row) into normalised column `slot` of the
+// scratch, in poison mode; col is re-aimed at it
+static int mv_ingest(int fmt, const msig_scratch& W, const uint8_t*& col, int slot, size_t rows, uint32_t wire_stride, hipStream_t s) {
+    if (fmt == JJS_FORMAT_WIRE) {
+        msig_decode_params D{};
+        D.n_src = 1;
+        D.src[0] = fe_src{col, wire_stride, 0};
+        D.out[0] = W.norm[slot];
+        col = W.norm[slot];
+        return launch_msig_decode(D, rows, s);
+    }
     normalize_params N{};
     N.n_src = 1; N.poison = 1; N.scratch = W.prefix;
     N.src[0] = fe_src{col, 96, 0};
@@ -34,7 +47,8 @@ static int msig_verify_locked(const mv_call& A, const uint32_t* offsets_host, si
     if (A.verify && (!all_ok(A.u, A.R, A.m) || (A.status && !aligned16(A.status)) || (reinterpret_cast<uintptr_t>(A.tally) & 7u)))
         return fail(JJS_ERR_ARG, "null or misaligned pointer");
     const size_t B = n_transcripts;
-    const size_t ext_rows = !A.ext ? 0 : (A.keyset ? (A.verify ? B : 0) : (A.verify && B > n ? B : n));
+    const bool ingest = A.fmt != JJS_FORMAT_AFFINE, wire = A.fmt == JJS_FORMAT_WIRE;
+    const size_t ext_rows = !ingest ? 0 : (A.keyset ? (A.verify ? B : 0) : (A.verify && B > n ? B : n));
     if (int rc = A.keyset ? ensure_msig_scratch(n, B, ext_rows, n ? n : 1, B) : ensure_msig_scratch(n, B, ext_rows)) return rc;
     const msig_scratch W = msig_scratch_carve();
     msig_verify_keyset_params VK{};
@@ -56,16 +70,21 @@ static int msig_verify_locked(const mv_call& A, const uint32_t* offsets_host, si
     } else {
         VK.K.refused = W.a_words;          // the inline form: a verifier's call computes no `a`, its words hold the refused flags
     }
-    const uint8_t *pk = A.keyset ? nullptr : (const uint8_t*)A.keys, *r = (const uint8_t*)A.R;
+    const uint8_t *pk = A.keyset ? nullptr : (const uint8_t*)A.keys, *r = (const uint8_t*)A.R, *u = (const uint8_t*)A.u;
     big_slot();
     if (int rc = begin_shared(s)) return rc;
     auto queue = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(W.offsets, offsets_host, (B + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(VK.K.refused, 0, B * sizeof(uint32_t), s));
-        if (A.ext && !A.keyset)
-            if (int rc = mv_normalize(W, pk, 0, n, s)) return rc;
-        if (A.ext && A.verify)
-            if (int rc = mv_normalize(W, r, A.keyset ? 0 : 1, B, s)) return rc;
+        if (ingest && !A.keyset)
+            if (int rc = mv_ingest(A.fmt, W, pk, 0, n, 32, s)) return rc;
+        if (ingest && A.verify)
+            if (int rc = mv_ingest(A.fmt, W, r, A.keyset ? 0 : 1, B, 64, s)) return rc;
+        if (wire && A.verify) {
+            uint8_t* packed = W.norm[A.keyset ? 1 : 2];              // B x 32 in a column of at least B rows of 64
+            HIP_TRY(hipMemcpy2DAsync(packed, 32, u, 64, 32, B, hipMemcpyDeviceToDevice, s));
+            u = packed;
+        }
         if (!A.keyset) P.PK = pk;
         const dim3 per_row(grid_for(g->grid_msig, n)), per_vector(grid_for(g->grid_msig, B));
         hipLaunchKernelGGL(msig_kernel, per_vector, dim3(BLOCK), 0, s, P, 0);
@@ -85,7 +104,7 @@ static int msig_verify_locked(const mv_call& A, const uint32_t* offsets_host, si
         if (!A.verify) return JJS_OK;
         // the verification stage: the resident single-scheme affine call on (u, R, agg_pk, m), in a slot of its own (build_call
         // moves sl), on the same stream, under this hold of the mutex
-        const void* d[4] = {A.u, r, A.agg_pk, A.m};
+        const void* d[4] = {u, r, A.agg_pk, A.m};
         staged_call C;
         if (int rc = build_call(SHAPES[JJS_SCHEME_SINGLE][JJS_FORMAT_AFFINE], d, B, A.status, A.tally, s, C)) return rc;
         if (int rc = launch_staged(C, s)) return rc;
@@ -100,7 +119,7 @@ static int msig_verify_locked(const mv_call& A, const uint32_t* offsets_host, si
 }
 
 // a _dev entry point: the checks in front of the call, under the engine's mutex
-static int msig_verify_dev(mv_call A, const jjs_keyset* ks, int format, const uint32_t* offsets_host, size_t n_transcripts, void* stream) {
+static int msig_verify_dev(mv_call A, const jjs_keyset* ks, int format, bool wire, const uint32_t* offsets_host, size_t n_transcripts, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
     if (ks) {
@@ -108,7 +127,7 @@ static int msig_verify_dev(mv_call A, const jjs_keyset* ks, int format, const ui
         if (int rc = msig_keyset_find(*ks, g, k, A.c)) return rc;
         A.k = k;
     }
-    if (int rc = msig_format(format, A.ext)) return rc;
+    if (int rc = msig_call_format(format, wire, A.fmt)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (n_transcripts == 0) {
         if (A.verify && A.tally) HIP_TRY(hipMemsetAsync(A.tally, 0, 4 * sizeof(unsigned long long), s));
@@ -118,7 +137,7 @@ static int msig_verify_dev(mv_call A, const jjs_keyset* ks, int format, const ui
 }
 
 // a host-buffer entry point: blocking, as jjs_multisig_combine (msig_host_calls.h).  A's pointers are the caller's host buffers.
-static int msig_verify_host(mv_call A, const jjs_keyset* ks, int format, const uint32_t* offsets, size_t n_transcripts, uint64_t* tally) {
+static int msig_verify_host(mv_call A, const jjs_keyset* ks, int format, bool wire, const uint32_t* offsets, size_t n_transcripts, uint64_t* tally) {
     device_state* dev = nullptr;
     size_t n = 0;
     {
@@ -128,7 +147,7 @@ static int msig_verify_host(mv_call A, const jjs_keyset* ks, int format, const u
             keyset_entry* k = nullptr;
             if (int rc = msig_keyset_find(*ks, g, k, A.c)) return rc;
         }
-        if (int rc = msig_format(format, A.ext)) return rc;
+        if (int rc = msig_call_format(format, wire, A.fmt)) return rc;
         if (n_transcripts == 0) {
             if (A.verify && tally) for (int k = 0; k < 4; ++k) tally[k] = 0;
             return JJS_OK;
@@ -142,9 +161,9 @@ static int msig_verify_host(mv_call A, const jjs_keyset* ks, int format, const u
     std::lock_guard<std::mutex> big(dev->host_mu);
     g = dev;
     return no_throw([&]() -> int {
-        const size_t B = n_transcripts, w = A.ext ? 96 : 64, v = A.verify ? 1 : 0;
-        const void* src[5] = {A.keys, A.u, A.R, A.m, nullptr};
-        const size_t in_bytes[5] = {n * (A.keyset ? 4 : w), v * B * 32, v * B * w, v * B * 32, 0};
+        const size_t B = n_transcripts, w = msig_point_bytes(A.fmt), v = A.verify ? 1 : 0;
+        const void* src[5] = {A.keys, A.u, A.R, A.m, nullptr};                   // wire: A.u is the u || R rows, uploaded as one column
+        const size_t in_bytes[5] = {n * (A.keyset ? 4 : w), v * B * (wire ? 64 : 32), wire ? 0 : v * B * w, v * B * 32, 0};
         const size_t out_bytes[5] = {B * 64, v * B, v * 32, (1 - v) * B, 0};
         msig_stage St{};
         if (int rc = msig_stage_in(dev, src, in_bytes, out_bytes, St)) return rc;
@@ -157,7 +176,7 @@ static int msig_verify_host(mv_call A, const jjs_keyset* ks, int format, const u
                 if (int rc = msig_keyset_find(*ks, dev, k, D.c)) return rc;
                 D.k = k;
             }
-            D.keys = St.in[0]; D.u = St.in[1]; D.R = St.in[2]; D.m = St.in[3];
+            D.keys = St.in[0]; D.u = St.in[1]; D.R = wire ? (const uint8_t*)St.in[1] + 32 : St.in[2]; D.m = St.in[3];
             D.agg_pk = St.out[0];
             D.status = A.status ? St.out[1] : nullptr;
             D.tally = tally ? St.out[2] : nullptr;
@@ -176,52 +195,92 @@ int jjs_multisig_aggregate_pk_dev(int format, const void* PK, const uint32_t* of
                                   void* vec_status, void* stream) {
     mv_call A{};
     A.keys = PK; A.agg_pk = agg_pk; A.vec_status = vec_status;
-    return msig_verify_dev(A, nullptr, format, offsets_host, n_transcripts, stream);
+    return msig_verify_dev(A, nullptr, format, false, offsets_host, n_transcripts, stream);
 }
 int jjs_multisig_aggregate_pk(int format, const uint8_t* PK, const uint32_t* offsets, size_t n_transcripts, uint8_t* agg_pk,
                               uint8_t* vec_status) {
     mv_call A{};
     A.keys = PK; A.agg_pk = agg_pk; A.vec_status = vec_status;
-    return msig_verify_host(A, nullptr, format, offsets, n_transcripts, nullptr);
+    return msig_verify_host(A, nullptr, format, false, offsets, n_transcripts, nullptr);
 }
 int jjs_multisig_aggregate_pk_keyset_dev(jjs_keyset ks, const void* key_idx, const uint32_t* offsets_host, size_t n_transcripts,
                                          void* agg_pk, void* vec_status, void* stream) {
     mv_call A{};
     A.keyset = true; A.keys = key_idx; A.agg_pk = agg_pk; A.vec_status = vec_status;
-    return msig_verify_dev(A, &ks, JJS_FORMAT_AFFINE, offsets_host, n_transcripts, stream);
+    return msig_verify_dev(A, &ks, JJS_FORMAT_AFFINE, false, offsets_host, n_transcripts, stream);
 }
 int jjs_multisig_aggregate_pk_keyset(jjs_keyset ks, const uint32_t* key_idx, const uint32_t* offsets, size_t n_transcripts,
                                      uint8_t* agg_pk, uint8_t* vec_status) {
     mv_call A{};
     A.keyset = true; A.keys = key_idx; A.agg_pk = agg_pk; A.vec_status = vec_status;
-    return msig_verify_host(A, &ks, JJS_FORMAT_AFFINE, offsets, n_transcripts, nullptr);
+    return msig_verify_host(A, &ks, JJS_FORMAT_AFFINE, false, offsets, n_transcripts, nullptr);
 }
 
 int jjs_multisig_verify_dev(int format, const void* PK, const uint32_t* offsets_host, const void* u, const void* R, const void* m,
                             size_t n_transcripts, void* agg_pk, void* status, void* tally, void* stream) {
     mv_call A{};
     A.verify = true; A.keys = PK; A.u = u; A.R = R; A.m = m; A.agg_pk = agg_pk; A.status = status; A.tally = tally;
-    return msig_verify_dev(A, nullptr, format, offsets_host, n_transcripts, stream);
+    return msig_verify_dev(A, nullptr, format, false, offsets_host, n_transcripts, stream);
 }
 int jjs_multisig_verify(int format, const uint8_t* PK, const uint32_t* offsets, const uint8_t* u, const uint8_t* R, const uint8_t* m,
                         size_t n_transcripts, uint8_t* agg_pk, uint8_t* status, uint64_t tally[4]) {
     mv_call A{};
     A.verify = true; A.keys = PK; A.u = u; A.R = R; A.m = m; A.agg_pk = agg_pk; A.status = status;
-    return msig_verify_host(A, nullptr, format, offsets, n_transcripts, tally);
+    return msig_verify_host(A, nullptr, format, false, offsets, n_transcripts, tally);
 }
 int jjs_multisig_verify_keyset_dev(jjs_keyset ks, int format, const void* key_idx, const uint32_t* offsets_host, const void* u,
                                    const void* R, const void* m, size_t n_transcripts, void* agg_pk, void* status, void* tally,
                                    void* stream) {
     mv_call A{};
     A.keyset = true; A.verify = true; A.keys = key_idx; A.u = u; A.R = R; A.m = m; A.agg_pk = agg_pk; A.status = status; A.tally = tally;
-    return msig_verify_dev(A, &ks, format, offsets_host, n_transcripts, stream);
+    return msig_verify_dev(A, &ks, format, false, offsets_host, n_transcripts, stream);
 }
 int jjs_multisig_verify_keyset(jjs_keyset ks, int format, const uint32_t* key_idx, const uint32_t* offsets, const uint8_t* u,
                                const uint8_t* R, const uint8_t* m, size_t n_transcripts, uint8_t* agg_pk, uint8_t* status,
                                uint64_t tally[4]) {
     mv_call A{};
     A.keyset = true; A.verify = true; A.keys = key_idx; A.u = u; A.R = R; A.m = m; A.agg_pk = agg_pk; A.status = status;
-    return msig_verify_host(A, &ks, format, offsets, n_transcripts, tally);
+    return msig_verify_host(A, &ks, format, false, offsets, n_transcripts, tally);
+}
+
+// the wire forms: PK_w is N x 32, sig_w is B x 64 = u || R (the layout of jjs_verify_single_wire)
+static mv_call mv_verify_wire_call(bool keyset, const void* keys, const void* sig_w, const void* m, void* agg_pk, void* status, void* tally) {
+    mv_call A{};
+    A.keyset = keyset; A.verify = true; A.keys = keys; A.m = m;
+    A.u = sig_w; A.R = sig_w ? (const uint8_t*)sig_w + 32 : nullptr;
+    A.agg_pk = agg_pk; A.status = status; A.tally = tally;
+    return A;
+}
+int jjs_multisig_aggregate_pk_wire_dev(const void* PK_w, const uint32_t* offsets_host, size_t n_transcripts, void* agg_pk, void* vec_status,
+                                       void* stream) {
+    mv_call A{};
+    A.keys = PK_w; A.agg_pk = agg_pk; A.vec_status = vec_status;
+    return msig_verify_dev(A, nullptr, JJS_FORMAT_WIRE, true, offsets_host, n_transcripts, stream);
+}
+int jjs_multisig_aggregate_pk_wire(const uint8_t* PK_w, const uint32_t* offsets, size_t n_transcripts, uint8_t* agg_pk, uint8_t* vec_status) {
+    mv_call A{};
+    A.keys = PK_w; A.agg_pk = agg_pk; A.vec_status = vec_status;
+    return msig_verify_host(A, nullptr, JJS_FORMAT_WIRE, true, offsets, n_transcripts, nullptr);
+}
+int jjs_multisig_verify_wire_dev(const void* PK_w, const uint32_t* offsets_host, const void* sig_w, const void* m, size_t n_transcripts,
+                                 void* agg_pk, void* status, void* tally, void* stream) {
+    mv_call A = mv_verify_wire_call(false, PK_w, sig_w, m, agg_pk, status, tally);
+    return msig_verify_dev(A, nullptr, JJS_FORMAT_WIRE, true, offsets_host, n_transcripts, stream);
+}
+int jjs_multisig_verify_wire(const uint8_t* PK_w, const uint32_t* offsets, const uint8_t* sig_w, const uint8_t* m, size_t n_transcripts,
+                             uint8_t* agg_pk, uint8_t* status, uint64_t tally[4]) {
+    mv_call A = mv_verify_wire_call(false, PK_w, sig_w, m, agg_pk, status, nullptr);
+    return msig_verify_host(A, nullptr, JJS_FORMAT_WIRE, true, offsets, n_transcripts, tally);
+}
+int jjs_multisig_verify_keyset_wire_dev(jjs_keyset ks, const void* key_idx, const uint32_t* offsets_host, const void* sig_w, const void* m,
+                                        size_t n_transcripts, void* agg_pk, void* status, void* tally, void* stream) {
+    mv_call A = mv_verify_wire_call(true, key_idx, sig_w, m, agg_pk, status, tally);
+    return msig_verify_dev(A, &ks, JJS_FORMAT_WIRE, true, offsets_host, n_transcripts, stream);
+}
+int jjs_multisig_verify_keyset_wire(jjs_keyset ks, const uint32_t* key_idx, const uint32_t* offsets, const uint8_t* sig_w, const uint8_t* m,
+                                    size_t n_transcripts, uint8_t* agg_pk, uint8_t* status, uint64_t tally[4]) {
+    mv_call A = mv_verify_wire_call(true, key_idx, sig_w, m, agg_pk, status, nullptr);
+    return msig_verify_host(A, &ks, JJS_FORMAT_WIRE, true, offsets, n_transcripts, tally);
 }
 
 }  // extern "C"
