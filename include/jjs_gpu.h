@@ -269,6 +269,48 @@ int jjs_keyset_verify_keys_dev(jjs_keyset ks, int format, const void* K0, const 
 int jjs_keyset_verify_keys(jjs_keyset ks, int format, const uint8_t* K0, const uint8_t* K1, const uint8_t* s0, const uint8_t* s1,
                            const uint8_t* s2, const uint8_t* m, size_t n, uint8_t* status, uint64_t tally[4], uint32_t* idx_out);
 
+/* ---- `is_valid` alone: keys and signatures checked without verifying anything --------------------
+ * The reference's six validity predicates -- PublicKey / PublicKeyDouble / PublicKeyVarGen::is_valid, Signature /
+ * SignatureDouble / SignatureVarGen::is_valid -- and the `from_bytes` of those types, in bulk: what a caller runs when a key or
+ * a signature arrives from outside and nothing is to be verified yet.  scheme JJS_SCHEME_*, format JJS_FORMAT_*.
+ * Columns: the ones of the verification calls.
+ *   keys        K0, K1 of jjs_keyset_verify_keys: affine / extended K0 = PK, K1 = PK' (double) or Gen (var-gen), n x 64 /
+ *               n x 96, K1 = NULL for single; wire K0 = the `pk` column of the _wire calls (n x 32, or n x 64), K1 = NULL;
+ *   signatures  s0, s1, s2 of jjs_keyset_verify: affine / extended s0 = u (n x 32), s1 = R, s2 = R' (double only), n x 64 /
+ *               n x 96; wire s0 = n x 64 (u || R) or n x 96 (u || R || R'), s1 = s2 = NULL.
+ * status[i] (nullable, n bytes) is 0, 1 or 3, never 2:
+ *   3  a coordinate >= q (extended: also Z >= q); a wire encoding jjs_decompress_dev refuses (v >= q, no square root, u = 0
+ *      with the sign bit set); a signature's scalar u >= r;
+ *   1  not 3, and some point is not on the curve, is the identity, is not torsion-free, or has Z = 0: `is_valid` is false;
+ *   0  every point `is_valid`.
+ * An item with two points has the status of the worse one (3 > 1 > 0).  For keys these are, byte for byte, the key_status
+ * jjs_keyset_create reports for the same keys in the same format -- without the 204 KB of tables per key.
+ * tally (nullable): tally[k] = the items with status k, tally[2] = 0; on the device 4 x uint64.
+ * Outputs, all nullable: A0_out, A1_out, R_out, Rp_out n x 64, the canonical affine point of the column (for wire input what
+ * jjs_decompress_dev writes for a decodable encoding, for extended input U/Z, V/Z reduced, for affine input the input);
+ * u_out n x 32, the scalar copied.  Every output row of an item with status 3 is zero bytes, and so is the row of a point with
+ * Z = 0; an item with status 1 that has its points gets its points.  An output of a column the scheme does not have (A1_out
+ * for single keys, Rp_out unless double) must be NULL.
+ *   _dev: device pointers, 16-byte aligned (the tally 8), asynchronous on `stream`, on the calling thread's current device.
+ *     One lane per point.  Extended input without point outputs runs no inversion (the tests are projective); with A0_out,
+ *     A1_out, R_out or Rp_out it is normalised first, one shared inversion per lane's items, in a call slot's wire area.
+ *   Host buffers: blocking, on the calling thread's current device, through the device's key-set staging area and stream under
+ *     the device's host-call lock, as jjs_keyset_find: one such call at a time per device.  No alignment is asked.
+ * n == 0 returns 0 and writes only a zero tally.  -4 before jjs_init; -1 for a scheme or format out of range, a NULL column
+ * the format needs, a non-NULL column or output it does not take, a misaligned device pointer.
+ * Measured resident against jjs_verify_single_dev of as many signatures (profiles/r16_points_check.jsonl): never
+ * slower at any of 48 shapes; one key 0.49-0.53x (affine, ext), 0.66-0.72x (ext with outputs), 0.89-0.93x (wire: one square root and
+ * one residue test in a row); 2^20 keys 0.09-0.10x, wire 0.18-0.19x; two points per item cost twice one.  The host form against
+ * jjs_keyset_create + jjs_keyset_destroy of the same keys: 0.18-0.28x at one key, 0.02-0.04x at 2^15. */
+int jjs_keys_check_dev(int scheme, int format, const void* K0, const void* K1, size_t n, void* status, void* tally, void* A0_out,
+                       void* A1_out, void* stream);
+int jjs_keys_check(int scheme, int format, const uint8_t* K0, const uint8_t* K1, size_t n, uint8_t* status, uint64_t tally[4],
+                   uint8_t* A0_out, uint8_t* A1_out);
+int jjs_signatures_check_dev(int scheme, int format, const void* s0, const void* s1, const void* s2, size_t n, void* status,
+                             void* tally, void* u_out, void* R_out, void* Rp_out, void* stream);
+int jjs_signatures_check(int scheme, int format, const uint8_t* s0, const uint8_t* s1, const uint8_t* s2, size_t n,
+                         uint8_t* status, uint64_t tally[4], uint8_t* u_out, uint8_t* R_out, uint8_t* Rp_out);
+
 /* ---- one verdict per batch: randomized batch verification -------------------------------------
  * Affine columns in the layouts of jjs_verify_*.  The verdict is 1 (accepted) or 0.
  *   * It never rejects a valid batch: when every item would get status 0 from jjs_verify_* of the same scheme, the

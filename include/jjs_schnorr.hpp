@@ -151,16 +151,19 @@ inline std::string to_base58(const std::array<uint8_t, N>& bytes) {
 struct Signature {
     JubJubScalar u;
     AffinePoint R;
+    bool is_valid() const;                 // Signature::is_valid (reference src/signatures.rs); see is_valid_batch below
 };
 // `SignatureDouble { u, R, R_prime }` (reference src/signatures/double.rs:66-70)
 struct SignatureDouble {
     JubJubScalar u;
     AffinePoint R, R_prime;
+    bool is_valid() const;                 // SignatureDouble::is_valid
 };
 // `SignatureVarGen { u, R }` (reference src/signatures/var_gen.rs)
 struct SignatureVarGen {
     JubJubScalar u;
     AffinePoint R;
+    bool is_valid() const;                 // SignatureVarGen::is_valid
 };
 
 // `PublicKey(JubJubExtended)` (reference src/keys/public.rs:52)
@@ -168,6 +171,7 @@ class PublicKey {
   public:
     explicit PublicKey(const AffinePoint& p) : point_(p) {}
     const AffinePoint& as_ref() const { return point_; }
+    bool is_valid() const;                 // PublicKey::is_valid (reference src/keys/public.rs:159-164); see is_valid_batch below
 
     struct Item { AffinePoint pk; Signature sig; BlsScalar message; };   // (key point, signature, message)
     // PublicKey::verify (reference src/keys/public.rs:114-135)
@@ -225,6 +229,7 @@ class PublicKeyDouble {
     PublicKeyDouble(const AffinePoint& pk, const AffinePoint& pk_prime) : pk_(pk), pk_prime_(pk_prime) {}
     const AffinePoint& pk() const { return pk_; }
     const AffinePoint& pk_prime() const { return pk_prime_; }
+    bool is_valid() const;                 // PublicKeyDouble::is_valid
 
     struct Item { AffinePoint pk, pk_prime; SignatureDouble sig; BlsScalar message; };
     // PublicKeyDouble::verify (reference src/keys/public/double.rs:86-117)
@@ -253,6 +258,7 @@ class PublicKeyVarGen {
     PublicKeyVarGen(const AffinePoint& pk, const AffinePoint& generator) : pk_(pk), generator_(generator) {}
     const AffinePoint& public_key() const { return pk_; }
     const AffinePoint& generator() const { return generator_; }
+    bool is_valid() const;                 // PublicKeyVarGen::is_valid
 
     struct Item { AffinePoint pk, generator; SignatureVarGen sig; BlsScalar message; };
     // PublicKeyVarGen::verify (reference src/keys/public/var_gen.rs:107-133)
@@ -274,6 +280,93 @@ class PublicKeyVarGen {
   private:
     AffinePoint pk_, generator_;
 };
+
+// `is_valid` alone (include/jjs_gpu.h jjs_keys_check / jjs_signatures_check): one bool per key or signature -- every point on
+// the curve, not the identity and torsion-free -- without verifying anything; a malformed encoding (a coordinate >= q, a scalar
+// >= r, bytes `from_bytes` refuses) is not valid.  Blocking host-buffer calls.  The ExtendedPoint and PointBytes forms take
+// single-point keys as the Rust types hold them (`JubJubExtended`) and as they travel (`PublicKey::to_bytes`); `affine_out`
+// (optional) receives the canonical affine points, zero bytes for a malformed one: the bulk `to_hash_inputs` / `from_bytes`.
+namespace detail {
+inline std::vector<bool> valid_of(int rc, const std::vector<uint8_t>& status, const char* what) {
+    if (rc != JJS_OK) throw EngineError(rc, what);
+    std::vector<bool> out(status.size());
+    for (size_t i = 0; i < status.size(); ++i) out[i] = status[i] == JJS_STATUS_OK;
+    return out;
+}
+template <size_t W>
+inline std::vector<bool> keys_valid(int format, const std::vector<std::array<uint8_t, W>>& keys, std::vector<AffinePoint>* affine_out) {
+    const size_t n = keys.size();
+    Soa k(n, W), a(affine_out ? n : 0, 64);
+    for (size_t i = 0; i < n; ++i) k.put(i, 0, keys[i]);
+    std::vector<uint8_t> status(n);
+    const int rc = jjs_keys_check(JJS_SCHEME_SINGLE, format, k.data(), nullptr, n, status.data(), nullptr, affine_out ? a.data() : nullptr, nullptr);
+    if (affine_out && rc == JJS_OK) {
+        affine_out->resize(n);
+        for (size_t i = 0; i < n; ++i) std::memcpy((*affine_out)[i].data(), a.data() + 64 * i, 64);
+    }
+    return valid_of(rc, status, "jjs_keys_check");
+}
+}  // namespace detail
+inline std::vector<bool> is_valid_batch(const std::vector<PublicKey>& keys) {
+    const size_t n = keys.size();
+    detail::Soa k(n, 64);
+    for (size_t i = 0; i < n; ++i) k.put(i, 0, keys[i].as_ref());
+    std::vector<uint8_t> status(n);
+    return detail::valid_of(jjs_keys_check(JJS_SCHEME_SINGLE, JJS_FORMAT_AFFINE, k.data(), nullptr, n, status.data(), nullptr, nullptr, nullptr),
+                            status, "jjs_keys_check");
+}
+inline std::vector<bool> is_valid_batch(const std::vector<PublicKeyDouble>& keys) {
+    const size_t n = keys.size();
+    detail::Soa k(n, 64), kp(n, 64);
+    for (size_t i = 0; i < n; ++i) { k.put(i, 0, keys[i].pk()); kp.put(i, 0, keys[i].pk_prime()); }
+    std::vector<uint8_t> status(n);
+    return detail::valid_of(jjs_keys_check(JJS_SCHEME_DOUBLE, JJS_FORMAT_AFFINE, k.data(), kp.data(), n, status.data(), nullptr, nullptr, nullptr),
+                            status, "jjs_keys_check");
+}
+inline std::vector<bool> is_valid_batch(const std::vector<PublicKeyVarGen>& keys) {
+    const size_t n = keys.size();
+    detail::Soa k(n, 64), gen(n, 64);
+    for (size_t i = 0; i < n; ++i) { k.put(i, 0, keys[i].public_key()); gen.put(i, 0, keys[i].generator()); }
+    std::vector<uint8_t> status(n);
+    return detail::valid_of(jjs_keys_check(JJS_SCHEME_VARGEN, JJS_FORMAT_AFFINE, k.data(), gen.data(), n, status.data(), nullptr, nullptr, nullptr),
+                            status, "jjs_keys_check");
+}
+inline std::vector<bool> is_valid_batch(const std::vector<ExtendedPoint>& keys, std::vector<AffinePoint>* affine_out = nullptr) {
+    return detail::keys_valid<96>(JJS_FORMAT_EXT, keys, affine_out);
+}
+inline std::vector<bool> is_valid_batch(const std::vector<PointBytes>& keys, std::vector<AffinePoint>* affine_out = nullptr) {
+    return detail::keys_valid<32>(JJS_FORMAT_WIRE, keys, affine_out);
+}
+inline std::vector<bool> is_valid_batch(const std::vector<Signature>& sigs) {
+    const size_t n = sigs.size();
+    detail::Soa u(n, 32), r(n, 64);
+    for (size_t i = 0; i < n; ++i) { u.put(i, 0, sigs[i].u); r.put(i, 0, sigs[i].R); }
+    std::vector<uint8_t> status(n);
+    return detail::valid_of(jjs_signatures_check(JJS_SCHEME_SINGLE, JJS_FORMAT_AFFINE, u.data(), r.data(), nullptr, n, status.data(), nullptr,
+                                                 nullptr, nullptr, nullptr), status, "jjs_signatures_check");
+}
+inline std::vector<bool> is_valid_batch(const std::vector<SignatureDouble>& sigs) {
+    const size_t n = sigs.size();
+    detail::Soa u(n, 32), r(n, 64), rp(n, 64);
+    for (size_t i = 0; i < n; ++i) { u.put(i, 0, sigs[i].u); r.put(i, 0, sigs[i].R); rp.put(i, 0, sigs[i].R_prime); }
+    std::vector<uint8_t> status(n);
+    return detail::valid_of(jjs_signatures_check(JJS_SCHEME_DOUBLE, JJS_FORMAT_AFFINE, u.data(), r.data(), rp.data(), n, status.data(), nullptr,
+                                                 nullptr, nullptr, nullptr), status, "jjs_signatures_check");
+}
+inline std::vector<bool> is_valid_batch(const std::vector<SignatureVarGen>& sigs) {
+    const size_t n = sigs.size();
+    detail::Soa u(n, 32), r(n, 64);
+    for (size_t i = 0; i < n; ++i) { u.put(i, 0, sigs[i].u); r.put(i, 0, sigs[i].R); }
+    std::vector<uint8_t> status(n);
+    return detail::valid_of(jjs_signatures_check(JJS_SCHEME_VARGEN, JJS_FORMAT_AFFINE, u.data(), r.data(), nullptr, n, status.data(), nullptr,
+                                                 nullptr, nullptr, nullptr), status, "jjs_signatures_check");
+}
+inline bool Signature::is_valid() const { return is_valid_batch(std::vector<Signature>{*this})[0]; }
+inline bool SignatureDouble::is_valid() const { return is_valid_batch(std::vector<SignatureDouble>{*this})[0]; }
+inline bool SignatureVarGen::is_valid() const { return is_valid_batch(std::vector<SignatureVarGen>{*this})[0]; }
+inline bool PublicKey::is_valid() const { return is_valid_batch(std::vector<PublicKey>{*this})[0]; }
+inline bool PublicKeyDouble::is_valid() const { return is_valid_batch(std::vector<PublicKeyDouble>{*this})[0]; }
+inline bool PublicKeyVarGen::is_valid() const { return is_valid_batch(std::vector<PublicKeyVarGen>{*this})[0]; }
 
 // One verdict per batch (include/jjs_gpu.h jjs_verify_all_*): true when every item would verify.  `status` (optional)
 // receives the statuses of verify_batch when the verdict is false.

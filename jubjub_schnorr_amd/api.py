@@ -200,6 +200,58 @@ class Engine:
         double, the generator for vargen); wire: `keys` in the layout of `verify_wire`'s pk, `keys2` None."""
         return KeySet(self, scheme, keys, keys2, fmt)
 
+    # ---- `is_valid` alone (include/jjs_gpu.h jjs_keys_check / jjs_signatures_check) ----------------------------------
+    def _points_check(self, kind: str, scheme: str, cols, fmt: str, want_points: bool):
+        two = (scheme != "single") if kind == "keys" else (scheme == "double")
+        if kind == "keys":
+            widths = [64 if two else 32] if fmt == "wire" else [96 if fmt == "ext" else 64] * (2 if two else 1)
+            slots, out_widths = 2, [64] + ([64] if two else [])
+        else:
+            widths = [96 if two else 64] if fmt == "wire" else [32] + [96 if fmt == "ext" else 64] * (2 if two else 1)
+            slots, out_widths = 3, [32, 64] + ([64] if two else [])
+        if len(cols) != len(widths):
+            raise ValueError(f"{scheme} {fmt} {kind} come in {len(widths)} column(s)")
+        n_outs = slots                         # keys: A0, A1; signatures: u, R, R'
+        ids = (self._SCHEME_IDS[scheme], self._FORMAT_IDS[fmt])
+        n = cols[0].shape[0]
+        if _is_torch(cols[0]):
+            import torch
+            dev = cols[0].device
+            ptrs = [self._dev_ptr(c, w, n) for c, w in zip(cols, widths)] + [None] * (slots - len(cols))
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[:n]
+            tally = torch.empty(4, dtype=torch.int64, device=dev)
+            outs = [torch.empty((max(n, 1), w), dtype=torch.uint8, device=dev)[:n] for w in out_widths] if want_points else []
+            optrs = [ctypes.c_void_p(a.data_ptr()) if n else None for a in outs] + [None] * (n_outs - len(outs))
+            name = f"jjs_{kind}_check_dev"
+            _ffi.check(getattr(self._lib, name)(*ids, *ptrs, n, ctypes.c_void_p(status.data_ptr()) if n else None,
+                                                ctypes.c_void_p(tally.data_ptr()), *optrs, self._stream()), name)
+        else:
+            host = [self._host(c, w) for c, w in zip(cols, widths)]
+            if any(h.shape[0] != n for h in host):
+                raise ValueError("all columns must have the same number of items")
+            ptrs = [h.ctypes.data_as(ctypes.c_void_p) for h in host] + [None] * (slots - len(cols))
+            status, tally = np.empty(n, np.uint8), np.zeros(4, np.uint64)
+            outs = [np.empty((n, w), np.uint8) for w in out_widths] if want_points else []
+            optrs = [a.ctypes.data_as(ctypes.c_void_p) for a in outs] + [None] * (n_outs - len(outs))
+            name = f"jjs_{kind}_check"
+            _ffi.check(getattr(self._lib, name)(*ids, *ptrs, n, status.ctypes.data_as(ctypes.c_void_p),
+                                                tally.ctypes.data_as(ctypes.c_void_p), *optrs), name)
+        return (status, tally, tuple(outs)) if want_points else (status, tally)
+
+    def keys_check(self, scheme: str, *cols, fmt: str = "affine", want_points: bool = False):
+        """`is_valid` of n public keys without verifying anything (`PublicKey::is_valid` & co., and their `from_bytes` with
+        `want_points`).  cols: affine / ext (PK[, PK' | Gen]), wire (pk).  Returns (status, tally): status 0 valid, 1 not
+        `is_valid`, 3 malformed -- the `key_status` of a key set of these keys; with `want_points` also the tuple of canonical
+        affine columns (n, 64), zero rows for malformed items.  Torch CUDA tensors: asynchronous on the current stream;
+        numpy arrays: blocking."""
+        return self._points_check("keys", scheme, cols, fmt, want_points)
+
+    def signatures_check(self, scheme: str, *cols, fmt: str = "affine", want_points: bool = False):
+        """`is_valid` of n signatures (`Signature::is_valid` & co.): cols affine / ext (u, R[, R']), wire (sig).  As
+        `keys_check`; a scalar u >= r is malformed.  With `want_points` the third value is (u, R[, R']): the scalar copied and
+        the canonical affine points."""
+        return self._points_check("signatures", scheme, cols, fmt, want_points)
+
     def verify_wire(self, scheme: str, sig, pk, m, want_status: bool = True):
         """Batch verify from the reference's wire formats (torch CUDA uint8 tensors): sig (n, 64|96|64) =
         u || R [|| R'], pk (n, 32|64|64) compressed, m (n, 32).  Points are decoded on the device; an
@@ -578,6 +630,18 @@ class Signature:
     u: bytes
     R: bytes
 
+    def is_valid(self) -> bool:
+        """`Signature::is_valid`: every point on the curve, not the identity and torsion-free."""
+        return bool(self.is_valid_batch([self])[0])
+
+    @staticmethod
+    def is_valid_batch(items: Sequence) -> np.ndarray:
+        """One bool per item (jjs_signatures_check); a malformed encoding is not valid."""
+        if not items:
+            return np.zeros(0, bool)
+        st, _ = engine().signatures_check("single", _rows([s.u for s in items], 32), _rows([s.R for s in items], 64))
+        return st == 0
+
 
 @dataclass(frozen=True)
 class SignatureDouble:
@@ -586,12 +650,37 @@ class SignatureDouble:
     R: bytes
     R_prime: bytes
 
+    def is_valid(self) -> bool:
+        """`SignatureDouble::is_valid`: every point on the curve, not the identity and torsion-free."""
+        return bool(self.is_valid_batch([self])[0])
+
+    @staticmethod
+    def is_valid_batch(items: Sequence) -> np.ndarray:
+        """One bool per item (jjs_signatures_check); a malformed encoding is not valid."""
+        if not items:
+            return np.zeros(0, bool)
+        st, _ = engine().signatures_check("double", _rows([s.u for s in items], 32), _rows([s.R for s in items], 64),
+                                        _rows([s.R_prime for s in items], 64))
+        return st == 0
+
 
 @dataclass(frozen=True)
 class SignatureVarGen:
     """`SignatureVarGen { u, R }` (reference src/signatures/var_gen.rs)."""
     u: bytes
     R: bytes
+
+    def is_valid(self) -> bool:
+        """`SignatureVarGen::is_valid`: every point on the curve, not the identity and torsion-free."""
+        return bool(self.is_valid_batch([self])[0])
+
+    @staticmethod
+    def is_valid_batch(items: Sequence) -> np.ndarray:
+        """One bool per item (jjs_signatures_check); a malformed encoding is not valid."""
+        if not items:
+            return np.zeros(0, bool)
+        st, _ = engine().signatures_check("vargen", _rows([s.u for s in items], 32), _rows([s.R for s in items], 64))
+        return st == 0
 
 
 def _rows(items, width):
@@ -608,6 +697,18 @@ def _raise_first(status):
 class PublicKey:
     """`PublicKey(JubJubExtended)` (reference src/keys/public.rs:52); the point as affine u || v."""
     point: bytes
+
+    def is_valid(self) -> bool:
+        """`PublicKey::is_valid`: every point on the curve, not the identity and torsion-free."""
+        return bool(self.is_valid_batch([self])[0])
+
+    @staticmethod
+    def is_valid_batch(items: Sequence) -> np.ndarray:
+        """One bool per key (jjs_keys_check); a malformed encoding is not valid."""
+        if not items:
+            return np.zeros(0, bool)
+        st, _ = engine().keys_check("single", _rows([k.point for k in items], 64))
+        return st == 0
 
     def verify(self, sig: Signature, message: bytes) -> None:
         """`PublicKey::verify` (reference src/keys/public.rs:114-135): returns None or raises."""
@@ -638,6 +739,18 @@ class PublicKeyDouble:
     """`PublicKeyDouble(pk, pk_prime)` (reference src/keys/public/double.rs:45)."""
     pk: bytes
     pk_prime: bytes
+
+    def is_valid(self) -> bool:
+        """`PublicKeyDouble::is_valid`: every point on the curve, not the identity and torsion-free."""
+        return bool(self.is_valid_batch([self])[0])
+
+    @staticmethod
+    def is_valid_batch(items: Sequence) -> np.ndarray:
+        """One bool per key (jjs_keys_check); a malformed encoding is not valid."""
+        if not items:
+            return np.zeros(0, bool)
+        st, _ = engine().keys_check("double", _rows([k.pk for k in items], 64), _rows([k.pk_prime for k in items], 64))
+        return st == 0
 
     def verify(self, sig: SignatureDouble, message: bytes) -> None:
         """`PublicKeyDouble::verify` (reference src/keys/public/double.rs:86-117)."""
@@ -670,6 +783,18 @@ class PublicKeyVarGen:
     """`PublicKeyVarGen { pk, generator }` (reference src/keys/public/var_gen.rs:40-43)."""
     pk: bytes
     generator: bytes
+
+    def is_valid(self) -> bool:
+        """`PublicKeyVarGen::is_valid`: every point on the curve, not the identity and torsion-free."""
+        return bool(self.is_valid_batch([self])[0])
+
+    @staticmethod
+    def is_valid_batch(items: Sequence) -> np.ndarray:
+        """One bool per key (jjs_keys_check); a malformed encoding is not valid."""
+        if not items:
+            return np.zeros(0, bool)
+        st, _ = engine().keys_check("vargen", _rows([k.pk for k in items], 64), _rows([k.generator for k in items], 64))
+        return st == 0
 
     def verify(self, sig: SignatureVarGen, message: bytes) -> None:
         """`PublicKeyVarGen::verify` (reference src/keys/public/var_gen.rs:107-133)."""

@@ -888,3 +888,32 @@ __global__ __launch_bounds__(BLOCK) void msig_round1_kernel(const uint8_t* r, co
     const uint64_t total = (uint64_t)gridDim.x * BLOCK;
     for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += total) ms_round1_item(r, s, comb_g, i, R_out, S_out, bad);
 }
+
+// ---- `is_valid` alone (points_check.h) ---------------------------------------------------------------------
+// One lane per point; the two lanes of a two-point item are the lanes 2j and 2j + 1 of one wave (the grid's lane count is a
+// multiple of the block), so one exchange with lane ^ 1 gives both the item's status; each then writes its own output row and
+// lane 0 of the item the status.  The tally: wave ballots over those writers and one atomic per wave and status, as
+// publish_status.  The grid covers the points once, and a lane beyond the end redoes the last point and writes nothing (the
+// exchange and the ballots want whole waves).  No grid-stride loop: around the loop the compiler kept the field constants of
+// every iteration in scalar registers and spilled 78-94 of them; without it none (scripts/kernel_resources.sh).  A kernel per
+// format (MODE): each keeps the registers of its own arithmetic.
+template <uint32_t MODE>
+__global__ __launch_bounds__(BLOCK) void points_check_kernel(points_check_params C) {
+    const uint64_t lanes = C.n * C.n_pts, t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool active = t < lanes;
+    const uint64_t p = active ? t : lanes - 1;
+    const uint64_t item = C.n_pts == 2 ? p >> 1 : p;
+    const uint32_t k = C.n_pts == 2 ? (uint32_t)p & 1u : 0u;
+    uint32_t st = pc_point_lane<MODE>(C, item, k, active);
+    if (C.n_pts == 2) st = pc_item_status(st, (uint32_t)__shfl_xor((int)st, 1));
+    if (active) pc_finish_lane(C, item, k, st);
+    const bool writer = active && k == 0;
+    if (writer && C.status) C.status[item] = (uint8_t)st;
+    if (C.tally) {
+#pragma unroll
+        for (uint32_t c = 0; c < 4; ++c) {
+            const unsigned long long b = __ballot(writer && st == c);
+            if ((threadIdx.x & 63) == 0 && b) atomicAdd(&C.tally[c], (unsigned long long)__popcll(b));
+        }
+    }
+}

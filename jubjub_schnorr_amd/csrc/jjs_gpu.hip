@@ -71,6 +71,7 @@
 #include "msig_sign.h"
 #include "batch_verdict.h"
 #include "keyset_verdict.h"
+#include "points_check.h"
 #include "jjs_sponge_tags_long.inc"
 
 using namespace jjs;
@@ -516,6 +517,7 @@ static int resident_call(const call_shape& S, const void* const* d, size_t n, vo
 
 #include "host_lanes.h"
 #include "keyset_calls.h"
+#include "points_check_calls.h"
 
 // a host-buffer call: blocking
 static int host_call(int scheme, int format, const uint8_t* const* ptrs, size_t n, uint8_t* status, uint64_t tally[4]) {

@@ -390,15 +390,15 @@ static int keyset_check_cols(int scheme, int format, const void* key_idx, const 
 // before it has left, and leaves through blocking_call_leave (engine_state.h) on every way out.
 extern "C++" {
 // The call's columns and outputs in dev's staging area (under dev->host_mu): column i of widths[i] bytes per item (0: not
-// used) copied from src[i] on the key-set stream s, then output areas of out_bytes[j] bytes, each part padded to 256 bytes.
+// used) copied from src[i] on the key-set stream s, then up to five output areas of out_bytes[j] bytes, each part padded to 256 bytes.
 struct keyset_stage {
     const void* d[6];
-    uint8_t* out[3];
+    uint8_t* out[5];
     hipStream_t s;
 };
 static int keyset_stage_in(device_state* dev, const size_t* widths, const void* const* src, size_t cols, size_t n, const size_t* out_bytes,
                            size_t outs, keyset_stage& S) {
-    size_t off[9], total = 0;
+    size_t off[11], total = 0;
     for (size_t i = 0; i < cols; ++i) { off[i] = total; total += pad256(widths[i] * n); }
     for (size_t j = 0; j < outs; ++j) { off[cols + j] = total; total += pad256(out_bytes[j]); }
     if (int rc = dev->ks_stage.ensure(total)) return rc;

@@ -11,8 +11,8 @@ for line in sys.stdin:
     m = re.search(r"remark: Function Name: (\S+)", line)
     if m:
         name = m.group(1)
-        k = re.search(r"\d+([a-z_0-9]+_kernel)", name)
-        cur, vals = (k.group(1) if k else name), {}
+        k = re.search(r"\d+([a-z_0-9]+_kernel)(?:I([A-Za-z0-9]+?)E)?", name)       # a template argument as it is mangled: <Lj2>
+        cur, vals = ((k.group(1) + ("<%s>" % k.group(2) if k.group(2) else "")) if k else name), {}
         continue
     m = re.search(r"remark: +([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
     if m and cur:
