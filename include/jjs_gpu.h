@@ -759,6 +759,63 @@ int jjs_sign_double_dev(const void* sk, const void* rnd, const void* m, size_t n
 int jjs_sign_vargen_dev(const void* sk, const void* gen_scalar, const void* rnd, const void* m, size_t n, void* u_out,
                         void* R_out, void* PK_out, void* Gen_out, void* stream);
 
+/* ---- var-generator signing and key derivation with the generator as a POINT (csrc/sign_vargen.h) ----
+ * The reference's SecretKeyVarGen holds { sk, generator: JubJubExtended } (src/keys/secret/var_gen.rs:98-101); `new` (:147),
+ * SecretKey::with_variable_generator and from_bytes (:109-131, 64 bytes = sk || generator compressed) all take the generator as
+ * a point, which in real use has no known discrete logarithm.  jjs_sign_vargen_dev above takes a SCALAR and serves
+ * SecretKeyVarGen::random alone; these calls take the point.
+ * GENERATORS OF TEST AND BENCHMARK MATERIAL, as jjs_sign_*: NOT constant time -- table look-ups and branches depend on sk and
+ * on the nonce; never use with production keys.
+ * format describes Gen: JJS_FORMAT_AFFINE n_gen x 64, JJS_FORMAT_EXT n_gen x 96 (U || V || Z), JJS_FORMAT_WIRE n_gen x 32
+ * (JubJubAffine::to_bytes).  sk, rnd: n x 32 scalars; m: n x 32.  The n_gen rule: n_gen is n (one generator per item) or 1 (one
+ * generator for the whole call: with_variable_generator over many keys); any other value gives -1; n_gen == 1 with n == 1 is
+ * the per-item call.
+ * Outputs: u_out n x 32; R_out, PK_out n x 64 affine; Gen_out n_gen x 64, the canonical affine generator (what
+ * to_hash_inputs() returns); status n bytes.  status, u_out and R_out are required, PK_out too for the derivation call; PK_out
+ * of the signing call and Gen_out may be NULL.
+ * status[i] is 0 or 3 (the reference's signer has no error; the ABI is total).  3: sk[i] >= r, rnd[i] >= r (the reference draws
+ * a JubJubScalar, src/nonce.rs:92), m[i] >= q, or the item's generator is unusable: a coordinate >= q; extended, Z >= q or
+ * Z = 0; a wire encoding that jjs_decompress_dev refuses; or a point that is not on the curve (the test jjs_multisig_verify
+ * applies to inline keys, for the same reason: off the curve the addition law computes nothing).  Every output row of a
+ * status-3 item is zero bytes; when a shared generator is unusable every item gets 3 and Gen_out is zero.  0: everything else.
+ * The generator is NOT validated, as in the reference: the identity, small-order points, points with a torsion part and sk = 0
+ * (tests/schnorr_var_generator.rs:119) sign and derive.
+ * For status 0 the values are byte for byte the reference's: r = H(rnd, sk, gen_u, gen_v, m) truncated, R = r * Gen,
+ * PK = sk * Gen, c = H(R, PK, Gen, m), u = r - c * sk (oracle/jjs_oracle.py sign_vargen_with_rand, mul).
+ * Extended and wire formats follow the multisignature family's rule: the outputs are those of the affine call on derived
+ * columns in which every usable point is its canonical affine form and every unusable point 64 bytes of 0xFF, which the range
+ * test turns into status 3.
+ * _dev: device pointers, 16-byte aligned (status: any alignment), asynchronous on `stream`, ordered with the other signing
+ * calls as they order themselves (they share a workspace).  The host forms are blocking, ask no alignment, take the route of
+ * jjs_multisig_sign, one at a time per device; the staged bytes of sk and rnd are cleared on the stream behind the last kernel,
+ * before the call returns.  n == 0 returns 0 and writes nothing.  -4 before jjs_init, before any argument is looked at; -1 for
+ * a bad format, a bad n_gen, a NULL required pointer or a misaligned device pointer.  No call allocates once the engine's
+ * buffers have reached its shape; jjs_trim frees what this adds.
+ * Two routes.  Per item (n_gen == n, and n_gen == 1 below 64 items): one lane per item builds the 4-bit table of its generator and
+ * runs two multiplications of 252 doublings; R and PK share ONE inversion; a shared generator is read with stride 0.  Shared
+ * generator (a signing call with n_gen == 1 and n >= 64): the 6-bit window tables of the one generator are built once per call
+ * (204 KB of grow-only scratch), and each lane walks them twice, 43 additions a walk and no doubling.  The two routes give the
+ * same bytes for every point of the curve.  jjs_debug_sign_limits reports the 64; the derivation call always runs per item.
+ * Rates (profiles/r17_sign_vargen_pt.jsonl, the record of tools/sign_vargen_pt_rate.py: one MI355X, resident inputs made on the
+ * device, 7 rounds, medians, the variants alternating; ms per call): against jjs_sign_vargen_dev on gen_scalar with
+ * Gen = gen_scalar * G, the per-item route takes 0.93-0.95x its time from 64 items on (2^20 items: 39.8 ms against 42.3, 26.3 M
+ * against 24.8 M signatures/s; extended 40.0 ms, wire 41.5 ms; one item: 3.0 against 3.3 ms, within the spread of 0.9).  With
+ * one generator for the call the shared route against the per-item route: 2.25 against 2.72 ms at 64 items, 2.32 / 2.76 at 1 024,
+ * 2.30 / 2.82 at 16 384, 5.35 / 10.2 at 2^18 and 17.8 / 39.7 ms at 2^20 (58.9 M signatures/s), each difference beyond the spread
+ * of either side; at one item 2.41 against 2.88 ms with spreads of 0.4 and 0.7: no winner, hence the threshold of 64.
+ */
+int jjs_public_keys_vargen_dev(int format, const void* sk, const void* Gen, size_t n_gen, size_t n,
+                               void* PK_out, void* Gen_out, void* status, void* stream);
+int jjs_sign_vargen_pt_dev(int format, const void* sk, const void* Gen, size_t n_gen, const void* rnd, const void* m, size_t n,
+                           void* u_out, void* R_out, void* PK_out, void* Gen_out, void* status, void* stream);
+int jjs_public_keys_vargen(int format, const uint8_t* sk, const uint8_t* Gen, size_t n_gen, size_t n,
+                           uint8_t* PK_out, uint8_t* Gen_out, uint8_t* status);
+int jjs_sign_vargen_pt(int format, const uint8_t* sk, const uint8_t* Gen, size_t n_gen, const uint8_t* rnd, const uint8_t* m, size_t n,
+                       uint8_t* u_out, uint8_t* R_out, uint8_t* PK_out, uint8_t* Gen_out, uint8_t* status);
+/* [0] lanes of the signing kernels resident at once on the current device, [1] the smallest n the shared-generator route
+ * serves (UINT64_MAX: none).  Negative return: an error code. */
+int jjs_debug_sign_limits(uint64_t out[2]);
+
 /* ---- primitives exposed for parity tests ------------------------------------------------------ */
 /* out[i] = a[i] * b[i] mod q (canonical bytes in and out) */
 int jjs_debug_fq_mul_dev(const void* a, const void* b, size_t n, void* out, void* stream);

@@ -281,6 +281,82 @@ class PublicKeyVarGen {
     AffinePoint pk_, generator_;
 };
 
+// `SecretKeyVarGen { sk, generator }` (reference src/keys/secret/var_gen.rs:98-101) with the generator as a POINT, as `new` (:147),
+// `SecretKey::with_variable_generator` and `from_bytes` (:109-131) take it: affine u || v, or the 32 bytes of JubJubAffine::to_bytes,
+// which go to the device as they are (jjs_sign_vargen_pt, jjs_public_keys_vargen).  A generator of test and benchmark material like
+// every signer of the engine, NOT constant time: never use with production keys.  An empty optional is the engine's status 3, the
+// reference's BytesError: sk or rnd >= r, message >= q, or a generator that is not canonical, does not decode or is off the curve.
+class SecretKeyVarGen {
+  public:
+    SecretKeyVarGen(const JubJubScalar& sk, const AffinePoint& generator) : sk_(sk), gen_(generator), wire_(false) {}     // SecretKeyVarGen::new
+    static SecretKeyVarGen from_bytes(const std::array<uint8_t, 64>& bytes) {      // sk || generator compressed; nothing is decoded here
+        SecretKeyVarGen k(JubJubScalar{}, AffinePoint{});
+        std::memcpy(k.sk_.data(), bytes.data(), 32);
+        std::memcpy(k.gen_.data(), bytes.data() + 32, 32);
+        k.wire_ = true;
+        return k;
+    }
+    std::array<uint8_t, 64> to_bytes() const {
+        std::array<uint8_t, 64> out{};
+        std::memcpy(out.data(), sk_.data(), 32);
+        std::memcpy(out.data() + 32, gen_.data() + (wire_ ? 0 : 32), 32);
+        if (!wire_) out[63] |= (uint8_t)((gen_[0] & 1) << 7);               // v with the parity of u in bit 255
+        return out;
+    }
+    const JubJubScalar& secret() const { return sk_; }
+    // PublicKeyVarGen::from(&SecretKeyVarGen): pk = sk * generator
+    std::optional<PublicKeyVarGen> public_key() const {
+        AffinePoint pk{}, gen{};
+        uint8_t status = 0;
+        int rc = jjs_public_keys_vargen(format(), sk_.data(), gen_.data(), 1, 1, pk.data(), gen.data(), &status);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_public_keys_vargen");
+        if (status != JJS_STATUS_OK) return std::nullopt;
+        return PublicKeyVarGen(pk, gen);
+    }
+    // SecretKeyVarGen::sign (:228-256) given the RNG draw `rnd` that the hedged nonce mixes in
+    std::optional<SignatureVarGen> sign(const JubJubScalar& rnd, const BlsScalar& message) const;
+    struct Item;
+    static std::vector<std::optional<SignatureVarGen>> sign_batch(const std::vector<Item>& items);
+  private:
+    int format() const { return wire_ ? JJS_FORMAT_WIRE : JJS_FORMAT_AFFINE; }
+    JubJubScalar sk_;
+    AffinePoint gen_;                      // a wire generator: its 32 bytes, then zeros
+    bool wire_;
+};
+struct SecretKeyVarGen::Item { SecretKeyVarGen key; JubJubScalar rnd; BlsScalar message; };
+// one call per generator format among the items (the host-buffer call asks no alignment)
+inline std::vector<std::optional<SignatureVarGen>> SecretKeyVarGen::sign_batch(const std::vector<Item>& items) {
+    std::vector<std::optional<SignatureVarGen>> out(items.size());
+    for (int wire = 0; wire < 2; ++wire) {
+        std::vector<size_t> idx;
+        for (size_t i = 0; i < items.size(); ++i)
+            if ((int)items[i].key.wire_ == wire) idx.push_back(i);
+        const size_t n = idx.size(), w = wire ? 32 : 64;
+        if (!n) continue;
+        std::vector<uint8_t> sk(n * 32), gen(n * w), rnd(n * 32), m(n * 32), u(n * 32), R(n * 64), status(n);
+        for (size_t j = 0; j < n; ++j) {
+            const Item& it = items[idx[j]];
+            std::memcpy(&sk[32 * j], it.key.sk_.data(), 32); std::memcpy(&gen[w * j], it.key.gen_.data(), w);
+            std::memcpy(&rnd[32 * j], it.rnd.data(), 32); std::memcpy(&m[32 * j], it.message.data(), 32);
+        }
+        int rc = jjs_sign_vargen_pt(wire ? JJS_FORMAT_WIRE : JJS_FORMAT_AFFINE, sk.data(), gen.data(), n, rnd.data(), m.data(), n, u.data(), R.data(),
+                                    nullptr, nullptr, status.data());
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_sign_vargen_pt");
+        for (size_t j = 0; j < n; ++j) {
+            if (status[j] != JJS_STATUS_OK) continue;
+            SignatureVarGen s;
+            std::memcpy(s.u.data(), &u[32 * j], 32); std::memcpy(s.R.data(), &R[64 * j], 64);
+            out[idx[j]] = s;
+        }
+    }
+    return out;
+}
+inline std::optional<SignatureVarGen> SecretKeyVarGen::sign(const JubJubScalar& rnd, const BlsScalar& message) const {
+    return sign_batch({Item{*this, rnd, message}})[0];
+}
+// `SecretKey::with_variable_generator(generator)` (the header has no SecretKey type: the scalar stands for it)
+inline SecretKeyVarGen with_variable_generator(const JubJubScalar& sk, const AffinePoint& generator) { return SecretKeyVarGen(sk, generator); }
+
 // `is_valid` alone (include/jjs_gpu.h jjs_keys_check / jjs_signatures_check): one bool per key or signature -- every point on
 // the curve, not the identity and torsion-free -- without verifying anything; a malformed encoding (a coordinate >= q, a scalar
 // >= r, bytes `from_bytes` refuses) is not valid.  Blocking host-buffer calls.  The ExtendedPoint and PointBytes forms take

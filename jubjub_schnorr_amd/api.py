@@ -494,6 +494,63 @@ class Engine:
                    "jjs_public_keys_dev")
         return (PK, PKp, bad) if double else (PK, bad)
 
+    _GEN_WIDTHS = {"affine": 64, "ext": 96, "wire": 32}
+
+    def _vargen_pt(self, sign: bool, sk, Gen, rnd, m, fmt: str):
+        w, fmt_id = self._GEN_WIDTHS[fmt], self._FORMAT_IDS[fmt]
+        n, ng = sk.shape[0], Gen.shape[0]
+        if ng != n and ng != 1:
+            raise ValueError(f"Gen has {ng} rows: one per item ({n}) or one for the call")
+        if not _is_torch(sk):
+            hsk, hgen = self._host(sk, 32), self._host(Gen, w)
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+            PK, G_out, status = np.zeros((n, 64), np.uint8), np.zeros((ng, 64), np.uint8), np.zeros(n, np.uint8)
+            if not sign:
+                _ffi.check(self._lib.jjs_public_keys_vargen(fmt_id, p(hsk), p(hgen), ng, n, p(PK), p(G_out), p(status)), "jjs_public_keys_vargen")
+                return PK, G_out, status
+            hrnd, hm = self._host(rnd, 32), self._host(m, 32)
+            if hrnd.shape[0] != n or hm.shape[0] != n:
+                raise ValueError("sk, rnd and m do not have the same rows")
+            u, R = np.zeros((n, 32), np.uint8), np.zeros((n, 64), np.uint8)
+            _ffi.check(self._lib.jjs_sign_vargen_pt(fmt_id, p(hsk), p(hgen), ng, p(hrnd), p(hm), n, p(u), p(R), p(PK), p(G_out), p(status)),
+                       "jjs_sign_vargen_pt")
+            return u, R, PK, G_out, status
+        import torch
+        new = lambda rows, width: torch.empty((max(rows, 1), width), dtype=torch.uint8, device=sk.device)[:rows]  # noqa: E731
+        o = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        PK, G_out, status = new(n, 64), new(ng, 64), torch.empty(max(n, 1), dtype=torch.uint8, device=sk.device)[:n]
+        if not sign:
+            _ffi.check(self._lib.jjs_public_keys_vargen_dev(fmt_id, self._dev_ptr(sk, 32, n), self._dev_ptr(Gen, w, ng), ng, n, o(PK), o(G_out),
+                                                            o(status), self._stream()), "jjs_public_keys_vargen_dev")
+            return PK, G_out, status
+        u, R = new(n, 32), new(n, 64)
+        _ffi.check(self._lib.jjs_sign_vargen_pt_dev(fmt_id, self._dev_ptr(sk, 32, n), self._dev_ptr(Gen, w, ng), ng, self._dev_ptr(rnd, 32, n),
+                                                    self._dev_ptr(m, 32, n), n, o(u), o(R), o(PK), o(G_out), o(status), self._stream()),
+                   "jjs_sign_vargen_pt_dev")
+        return u, R, PK, G_out, status
+
+    def public_keys_vargen(self, sk, Gen, fmt: str = "affine"):
+        """`PublicKeyVarGen::from(&SecretKeyVarGen)` for a batch with the generator as a POINT: PK = sk * Gen.  sk (n, 32); Gen
+        (n, 64) affine, (n, 96) extended or (n, 32) wire by `fmt` -- or ONE row, the generator of the whole call
+        (`with_variable_generator` over many keys).  torch CUDA tensors run asynchronously on the current stream
+        (jjs_public_keys_vargen_dev), numpy arrays block (jjs_public_keys_vargen).  NOT constant time: test and benchmark
+        material.  Returns (PK (n, 64), Gen (rows of Gen, 64) canonical affine, status (n,)): 0, or 3 for sk >= r or an unusable
+        generator (a coordinate >= q, Z = 0, an encoding that does not decode, a point off the curve), with zero rows."""
+        return self._vargen_pt(False, sk, Gen, None, None, fmt)
+
+    def sign_vargen_pt(self, sk, Gen, rnd, m, fmt: str = "affine"):
+        """`SecretKeyVarGen::sign` for a batch given the RNG draws, with the generator as a POINT (any point of the curve: it is
+        not validated, as in the reference).  Arguments and dispatch as `public_keys_vargen`, with rnd and m (n, 32).  NOT
+        constant time: test and benchmark material.  Returns (u, R, PK, Gen, status); status 3 also for rnd >= r and m >= q."""
+        return self._vargen_pt(True, sk, Gen, rnd, m, fmt)
+
+    def sign_limits(self) -> dict:
+        """jjs_debug_sign_limits: the lanes of the signing kernels resident at once, and the smallest n from which a signing call
+        with one generator takes the shared-generator route (None: no call takes it by size)."""
+        out = (ctypes.c_uint64 * 2)()
+        _ffi.check(self._lib.jjs_debug_sign_limits(out), "jjs_debug_sign_limits")
+        return {"resident_lanes": int(out[0]), "shared_generator_from": None if out[1] == 2**64 - 1 else int(out[1])}
+
     def multisig_sign_round1(self, r, s):
         """`sign_round_1` for a batch given the two RNG draws (reference src/multisig.rs:169-184): R = r*G, S = s*G.  torch CUDA
         tensors (n, 32); NOT constant time.  Returns (R, S, bad): bad[i] = 1 where r[i] or s[i] is not a canonical
@@ -820,6 +877,65 @@ class PublicKeyVarGen:
             _rows([k.pk for k, _, _ in items], 64), _rows([k.generator for k, _, _ in items], 64),
             _rows([m for _, _, m in items], 32), statuses_on_failure=False)
         return ok
+
+
+@dataclass(frozen=True)
+class SecretKeyVarGen:
+    """`SecretKeyVarGen { sk, generator }` (reference src/keys/secret/var_gen.rs:98-101) with the generator as a POINT: affine
+    u || v (64 bytes, `new`) or the 32 bytes of `JubJubAffine::to_bytes` (`from_bytes`, which goes to the device as it is).
+    Signing here is a generator of test and benchmark material, NOT constant time: never use with production keys."""
+    sk: bytes
+    generator: bytes
+    fmt: str = "affine"
+
+    @staticmethod
+    def new(sk: bytes, generator: bytes) -> "SecretKeyVarGen":
+        """`SecretKeyVarGen::new(sk, generator)` (:147): sk 32 bytes, generator affine u || v."""
+        return SecretKeyVarGen(_b(sk, 32), _b(generator, 64), "affine")
+
+    @staticmethod
+    def from_bytes(data: bytes) -> "SecretKeyVarGen":
+        """`SecretKeyVarGen::from_bytes` (:109-131): 64 bytes = sk || generator compressed.  Nothing is decoded here: an
+        encoding that does not decode raises `Malformed` when the key is used."""
+        data = _b(data, 64)
+        return SecretKeyVarGen(data[:32], data[32:], "wire")
+
+    def to_bytes(self) -> bytes:
+        """sk || generator compressed (v with the sign of u in the top bit)."""
+        if self.fmt == "wire":
+            return self.sk + self.generator
+        enc = bytearray(self.generator[32:])
+        enc[31] |= (self.generator[0] & 1) << 7
+        return self.sk + bytes(enc)
+
+    def public_key(self) -> "PublicKeyVarGen":
+        """`PublicKeyVarGen::from(&SecretKeyVarGen)`: pk = sk * generator (jjs_public_keys_vargen)."""
+        PK, Gen, st = engine().public_keys_vargen(_rows([self.sk], 32), _rows([self.generator], len(self.generator)), fmt=self.fmt)
+        _raise_first(st)
+        return PublicKeyVarGen(PK[0].tobytes(), Gen[0].tobytes())
+
+    def sign(self, rnd: bytes, message: bytes) -> "SignatureVarGen":
+        """`SecretKeyVarGen::sign` (:228-256) given the RNG draw `rnd` the hedged nonce mixes in (32 bytes, < r)."""
+        return self.sign_batch([(self, rnd, message)])[0]
+
+    @staticmethod
+    def sign_batch(items: Sequence[tuple]) -> list:
+        """items: (SecretKeyVarGen, rnd bytes, message bytes).  One SignatureVarGen per item (jjs_sign_vargen_pt, one call per
+        generator format among the items); raises `Malformed` for the first item the engine refuses."""
+        out = [None] * len(items)
+        for fmt in ("affine", "wire"):
+            idx = [i for i, (k, _, _) in enumerate(items) if k.fmt == fmt]
+            if not idx:
+                continue
+            u, R, _, _, st = engine().sign_vargen_pt(_rows([items[i][0].sk for i in idx], 32),
+                                                     _rows([items[i][0].generator for i in idx], Engine._GEN_WIDTHS[fmt]),
+                                                     _rows([items[i][1] for i in idx], 32), _rows([items[i][2] for i in idx], 32), fmt=fmt)
+            _raise_first(st)
+            for j, i in enumerate(idx):
+                out[i] = SignatureVarGen(u[j].tobytes(), R[j].tobytes())
+        if any(x is None for x in out):
+            raise ValueError("a key's generator format is neither affine nor wire")
+        return out
 
 
 # ------------------------------------------------------------------------------------------------

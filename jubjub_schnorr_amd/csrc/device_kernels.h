@@ -596,6 +596,28 @@ __global__ __launch_bounds__(BLOCK) void sign_kernel(sign_params P) {
     uint32_t* ws = P.workspace + gtid * WS_WORDS_PER_LANE;
     for (uint64_t item = gtid; item < P.n; item += total) sign_item(P, item, ws);
 }
+// The var-generator signer and key derivation with the generator as a point (sign_vargen.h): one lane per item, grid-stride over
+// the resident lanes, the lane's workspace as sign_kernel's.  NOT constant time: generators of test and benchmark material.
+__global__ __launch_bounds__(BLOCK) void sign_vargen_pt_kernel(sign_vargen_params P) {
+    const uint64_t gtid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    uint32_t* ws = P.workspace + gtid * WS_WORDS_PER_LANE;
+    for (uint64_t item = gtid; item < P.n; item += total) sign_vargen_item<true>(P, item, ws);
+}
+// ... the shared-generator route: the lanes walk the window tables of the call's one generator (P.tables), which
+// msig_group_chain_kernel and msig_group_table_kernel built in front of this launch; the workspace holds the transcript area alone
+__global__ __launch_bounds__(BLOCK) void sign_vargen_shared_kernel(sign_vargen_params P) {
+    const uint64_t gtid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    uint32_t* ws = P.workspace + gtid * WS_WORDS_PER_LANE;
+    for (uint64_t item = gtid; item < P.n; item += total) sign_vargen_item<true, true>(P, item, ws);
+}
+__global__ __launch_bounds__(BLOCK) void derive_vargen_pt_kernel(sign_vargen_params P) {
+    const uint64_t gtid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    uint32_t* ws = P.workspace + gtid * WS_WORDS_PER_LANE;
+    for (uint64_t item = gtid; item < P.n; item += total) sign_vargen_item<false>(P, item, ws);
+}
 
 // PublicKey::from(&SecretKey) = sk * G (reference src/keys/public.rs:54-60) and the second half of
 // PublicKeyDouble::from (sk * G', src/keys/public/double.rs:47-57): fixed-base only, NOT constant time.

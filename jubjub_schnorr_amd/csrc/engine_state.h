@@ -279,6 +279,8 @@ struct device_state {
     size_t retired_bytes = 0;
     stream_owner ks_stream;              // host-buffer calls on a registered key set (jjs_keyset_verify): uploads, launch, statuses
     grow_only<uint8_t> ks_stage;         // ... their device copies of the inputs and outputs (bytes; under host_mu)
+    grow_only<uint8_t> sign_tables;      // jjs_sign_vargen_pt*: the chain of bases and the window tables of a call's shared generator (bytes);
+                                         // used in the order of slot 0's event, grows under the engine's mutex; jjs_trim frees it
     grow_only<uint8_t> msig_stage;       // host-buffer multisig calls (jjs_multisig_combine, jjs_msig_group_combine): their columns and
                                          // outputs (bytes), on ks_stream under host_mu; it grows under the engine's mutex as well, which
                                          // jjs_memory_stats reads it under; jjs_trim frees it

@@ -24,6 +24,7 @@
 //   msig_keyset_calls.h  the multisignature call against a registered key set, both forms
 //   msig_verify_calls.h  the verifier's half: aggregate_pk, and aggregate_pk followed by the single-scheme verification
 //   msig_sign_calls.h  the signer's half: sign_round_1, and sign_round_2 over whole ragged batches (a generator of test material)
+//   sign_vargen_calls.h  var-generator signing and key derivation with the generator as a point, both forms (test material)
 //   host_lanes.h       the small ones (included among the entry points, behind the table of call shapes): staging lanes
 //                      outside the engine's mutex, calls of several threads in one launch
 //   (here)             the table of call shapes and the staged_call builder it drives; the extern "C" entry points
@@ -64,6 +65,7 @@
 #include "keyset.h"
 #include "keyset_lookup.h"
 #include "sign_core.h"
+#include "sign_vargen.h"
 #include "multisig_core.h"
 #include "msig_group.h"
 #include "msig_keyset.h"
@@ -722,6 +724,7 @@ int jjs_trim(void) {
         HIP_TRY(hipSetDevice(d->device));
         HIP_TRY(hipDeviceSynchronize());
         free_retired(*d);
+        HIP_TRY(d->sign_tables.free());                        // the tables of a signing call's shared generator
         HIP_TRY(d->msig_stage.free());                         // the staging of the host-buffer multisig calls (host_mu is held)
         for (call_slot& c : d->slots) {
             if (!c.key_pool) continue;
@@ -745,7 +748,7 @@ int jjs_memory_stats(uint64_t out[JJS_MEMORY_STATS]) {
     }
     for (const host_lane& l : g->lanes) lanes += l.dev.reported_bytes() + l.pinned.reported_bytes();
     out[JJS_MEMORY_KEY_POOLS] = pool;
-    out[JJS_MEMORY_SLOT_BUFFERS] = slots;
+    out[JJS_MEMORY_SLOT_BUFFERS] = slots + g->sign_tables.reported_bytes();
     out[JJS_MEMORY_HOST_STAGING] = lanes + g->stage.reported_bytes() + g->pinned.reported_bytes() + g->msig_stage.reported_bytes();
     out[JJS_MEMORY_RETIRED] = g->retired_bytes;
     return JJS_OK;
@@ -1131,6 +1134,8 @@ int jjs_public_keys_dev(const void* sk, size_t n, void* PK_out, void* PKp_out, v
     return JJS_OK;
 }
 
+#include "sign_vargen_calls.h"
+
 // ---- debug primitives ------------------------------------------------------------------------------
 int jjs_debug_fq_mul_dev(const void* a, const void* b, size_t n, void* out, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
@@ -1190,6 +1195,7 @@ int jjs_debug_force_path(int which) {
     g_keep_order = (which & 0x1000) != 0;
     g_force_window = ((which >> 8) & 15) == KT_WINDOW_NARROW ? ((which >> 8) & 15) : 0;   // 0x500: narrow key-table windows whatever the keys
     g_force_verdict = (which & 0x2000) ? 1 : ((which & 0x4000) ? 2 : 0);   // jjs_verify_all_*: 0x2000 the verdict algorithm, 0x4000 the per-item path
+    g_force_sign_shared = (which & 0x8000) ? 1 : ((which & 0x200000) ? 2 : 0);   // jjs_sign_vargen_pt* with one generator: 0x8000 the shared-generator route at any n, 0x200000 the per-item route
     g_force_msm_window = (which >> 16) & 31;                                // ... and bits 16-20 its window width (8-16; 0 by size)
     return JJS_OK;
 }
