@@ -816,6 +816,72 @@ int jjs_sign_vargen_pt(int format, const uint8_t* sk, const uint8_t* Gen, size_t
  * serves (UINT64_MAX: none).  Negative return: an error code. */
 int jjs_debug_sign_limits(uint64_t out[2]);
 
+/* ---- signing and key derivation with a SecretKey, single and double scheme (csrc/sign_fixed.h) ----
+ * What a holder of the reference's SecretKey calls: PublicKey::from(&sk) (src/keys/public.rs:54-60), PublicKeyDouble::from(&sk)
+ * (src/keys/public/double.rs:47-57), SecretKey::sign (src/keys/secret.rs:174-194) and sign_double (src/keys/secret/double.rs:56-85),
+ * with range checks and statuses, host buffers and wire bytes out.  jjs_sign_single_dev, jjs_sign_double_dev and
+ * jjs_public_keys_dev above stay as they are.
+ * GENERATORS OF TEST AND BENCHMARK MATERIAL, as jjs_sign_*: NOT constant time -- table look-ups and branches depend on sk and
+ * on the nonce; never use with production keys.
+ * scheme: JJS_SCHEME_SINGLE or JJS_SCHEME_DOUBLE; JJS_SCHEME_VARGEN and anything else give -1 (that scheme has
+ * jjs_sign_vargen_pt).  The n_sk rule: n_sk is n (a key per item) or 1 (one key for the call: sk is one row, and PK_out, PKp_out
+ * and pk_w_out are one row); any other value gives -1; n_sk == 1 with n == 1 is the per-item call.
+ * Layouts: sk n_sk x 32 and rnd n x 32 scalars; m n x 32; u_out n x 32; R_out, Rp_out n x 64 affine; PK_out, PKp_out n_sk x 64
+ * affine; sig_w_out n x 64 (single) or n x 96 (double), Signature::to_bytes = u || compress(R) [|| compress(R')]; pk_w_out
+ * n_sk x 32 (single) or n_sk x 64 (double), PublicKey::to_bytes = compress(PK) [|| compress(PK')]; status n bytes, any
+ * alignment.  compress is jjs_compress_dev's: little-endian v, the parity of u in bit 255.
+ * Required: the inputs and status.  Every output is nullable on its own; a signing call with u_out, R_out, Rp_out and sig_w_out
+ * all NULL gives -1, and so does a derivation call with all three outputs NULL.  Rp_out and PKp_out must be NULL for the single
+ * scheme (the rule of jjs_keys_check for a column the scheme does not have).
+ * status[i] is 0 or 3 (the reference's signer has no error; the ABI is total).  3: sk >= r, rnd[i] >= r (the reference draws a
+ * JubJubScalar, src/nonce.rs:92) or m[i] >= q; the derivation call tests sk[i] alone.  Every output row a status-3 item owns is
+ * zero bytes.  With n_sk == 1 the key rows belong to the call: they are the key's whatever the items' rnd and m are, and an
+ * unusable key gives every item 3 and zero key rows.  sk is the only validated input: sk = 0 signs, its key is the identity.
+ * For status 0 the values are byte for byte the reference's: r = H(rnd, sk, tag, m) truncated with tag 1 (single) or 2 (double),
+ * R = r * G, R' = r * G', c the 5-input or the tagged 10-input challenge, u = r - c * sk; the affine outputs are byte for byte
+ * what jjs_sign_single_dev / jjs_sign_double_dev write for the same sk, rnd and m, and the wire outputs what jjs_compress_dev
+ * makes of them.
+ * _dev: device pointers, 16-byte aligned (status: any alignment), asynchronous on `stream`, ordered with the other signing
+ * calls as they order themselves (they share a workspace).  The host forms are blocking, ask no alignment, take the route of
+ * jjs_sign_vargen_pt, one at a time per device; the staged bytes of sk and rnd are cleared on the stream behind the last kernel,
+ * before the call returns, on every way out.  n == 0 returns 0 and writes nothing.  -4 before jjs_init, before any argument is
+ * looked at; -1 for the cases above, a NULL required pointer or a misaligned device pointer; -2 when scratch cannot be
+ * allocated.  A refused call writes nothing.  No call allocates once the engine's buffers have reached its shape; jjs_trim frees
+ * what this adds.
+ * One lane per item; all the points of an item share ONE field inversion (jjs_sign_*_dev: one per point).  Two routes for
+ * n_sk == 1.  Per item: every lane reads the one key row and multiplies it out again.  Keyed: a one-lane launch in front derives
+ * PK (and PK') once into 256 bytes of grow-only scratch, and each lane runs r * G (and r * G') alone.  Both give the same bytes.
+ * A call with n_sk == 1 takes the keyed route from 2^20 items on (jjs_debug_sign_fixed_limits reports it); the derivation call
+ * always runs per item.
+ * Rates (profiles/r18_sign_fixed.jsonl, the record of tools/sign_fixed_rate.py: one MI355X, resident inputs made on the device,
+ * 7 rounds, medians, the variants alternating; ms per call, max - min of the rounds in brackets).  Against jjs_sign_single_dev /
+ * jjs_sign_double_dev with n_sk = n: single 0.78x their time at one item (0.83 against 1.07 ms), 0.94-0.95x from 64 to 2^18 and
+ * 0.96x at 2^20 (11.15 (0.19) against 11.60 (0.22) ms, 94.1 M against 90.4 M signatures/s); double level at one item (1.30
+ * against 1.30 ms) and 0.89-0.91x from 64 items on (2^20: 15.93 (0.14) against 17.60 (0.12) ms, 65.8 M against 59.6 M/s); at no
+ * recorded shape slower beyond the spreads.  The wire outputs add at most 1 % from 64 items on (2^20: 11.19 and 16.00 ms); at
+ * one item 0.94 against 0.83 ms (single) and 1.50 against 1.30 ms (double, 1.16x the old signer's time: the one shape at which a
+ * new call is slower than the old one).  One key for the call, keyed against per item: slower by 5-10 % from 64 to 16 384 items
+ * in both schemes (single 0.882 against 0.828 ms at 64) and by 31 % at one double item (1.58 against 1.20 ms); single within the
+ * spread at 2^18 (2.67 against 2.73 ms, spreads to 0.08) and 0.95x at 2^20 (10.41 (0.08) against 10.95 (0.12) ms, 100.7 M/s);
+ * double 0.95x at 2^18 (3.66 against 3.85 ms) and 0.92x at 2^20 (14.40 (0.25) against 15.59 (0.13) ms, 72.8 M/s): hence the
+ * threshold of 2^20, the first shape at which both schemes win.  Derivation against jjs_public_keys_dev: single level
+ * (0.94-1.02x, 1.32 against 1.31 ms at 2^20, with the range test and status it adds), double 0.65-0.83x (2.06 against 2.74 ms at
+ * 2^20: one inversion instead of two).
+ */
+int jjs_sign_fixed_dev(int scheme, const void* sk, size_t n_sk, const void* rnd, const void* m, size_t n,
+                       void* u_out, void* R_out, void* Rp_out, void* PK_out, void* PKp_out,
+                       void* sig_w_out, void* pk_w_out, void* status, void* stream);
+int jjs_sign_fixed(int scheme, const uint8_t* sk, size_t n_sk, const uint8_t* rnd, const uint8_t* m, size_t n,
+                   uint8_t* u_out, uint8_t* R_out, uint8_t* Rp_out, uint8_t* PK_out, uint8_t* PKp_out,
+                   uint8_t* sig_w_out, uint8_t* pk_w_out, uint8_t* status);
+int jjs_public_keys_fixed_dev(int scheme, const void* sk, size_t n, void* PK_out, void* PKp_out, void* pk_w_out,
+                              void* status, void* stream);
+int jjs_public_keys_fixed(int scheme, const uint8_t* sk, size_t n, uint8_t* PK_out, uint8_t* PKp_out,
+                          uint8_t* pk_w_out, uint8_t* status);
+/* [0] lanes of the SecretKey signing kernels resident at once on the current device, [1] the smallest n the keyed route
+ * serves (UINT64_MAX: none).  Negative return: an error code. */
+int jjs_debug_sign_fixed_limits(uint64_t out[2]);
+
 /* ---- primitives exposed for parity tests ------------------------------------------------------ */
 /* out[i] = a[i] * b[i] mod q (canonical bytes in and out) */
 int jjs_debug_fq_mul_dev(const void* a, const void* b, size_t n, void* out, void* stream);

@@ -354,8 +354,108 @@ inline std::vector<std::optional<SignatureVarGen>> SecretKeyVarGen::sign_batch(c
 inline std::optional<SignatureVarGen> SecretKeyVarGen::sign(const JubJubScalar& rnd, const BlsScalar& message) const {
     return sign_batch({Item{*this, rnd, message}})[0];
 }
-// `SecretKey::with_variable_generator(generator)` (the header has no SecretKey type: the scalar stands for it)
+// `SecretKey::with_variable_generator(generator)` from the bare scalar (SecretKey below has it as a member)
 inline SecretKeyVarGen with_variable_generator(const JubJubScalar& sk, const AffinePoint& generator) { return SecretKeyVarGen(sk, generator); }
+
+// `SecretKey(JubJubScalar)` (reference src/keys/secret.rs) in the single and the double scheme: the 32 little-endian bytes of the
+// scalar, through the blocking host-buffer calls jjs_sign_fixed and jjs_public_keys_fixed.  A generator of test and benchmark
+// material like every signer of the engine, NOT constant time: never use with production keys.  An empty optional is the engine's
+// status 3, the reference's BytesError: sk or rnd >= r, or message >= q.
+class SecretKey {
+  public:
+    explicit SecretKey(const JubJubScalar& sk) : sk_(sk) {}
+    // SecretKey::from_bytes (:120-126): empty for a scalar that is not below the group order (a compare on the host)
+    static std::optional<SecretKey> from_bytes(const std::array<uint8_t, 32>& bytes) {
+        static const uint8_t order_be[32] = {0x0E, 0x7D, 0xB4, 0xEA, 0x65, 0x33, 0xAF, 0xA9, 0x06, 0x67, 0x3B, 0x01, 0x01, 0x34, 0x3B, 0x00,
+                                             0xA6, 0x68, 0x20, 0x93, 0xCC, 0xC8, 0x10, 0x82, 0xD0, 0x97, 0x0E, 0x5E, 0xD6, 0xF7, 0x2C, 0xB7};
+        for (int i = 0; i < 32; ++i) {
+            if (bytes[31 - i] < order_be[i]) return SecretKey(bytes);
+            if (bytes[31 - i] > order_be[i]) return std::nullopt;
+        }
+        return std::nullopt;
+    }
+    std::array<uint8_t, 32> to_bytes() const { return sk_; }
+    const JubJubScalar& secret() const { return sk_; }
+    // PublicKey::from(&SecretKey): sk * G
+    std::optional<PublicKey> public_key() const {
+        AffinePoint pk{};
+        uint8_t status = 0;
+        int rc = jjs_public_keys_fixed(JJS_SCHEME_SINGLE, sk_.data(), 1, pk.data(), nullptr, nullptr, &status);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_public_keys_fixed");
+        if (status != JJS_STATUS_OK) return std::nullopt;
+        return PublicKey(pk);
+    }
+    // PublicKeyDouble::from(&SecretKey): (sk * G, sk * G')
+    std::optional<PublicKeyDouble> public_key_double() const {
+        AffinePoint pk{}, pkp{};
+        uint8_t status = 0;
+        int rc = jjs_public_keys_fixed(JJS_SCHEME_DOUBLE, sk_.data(), 1, pk.data(), pkp.data(), nullptr, &status);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_public_keys_fixed");
+        if (status != JJS_STATUS_OK) return std::nullopt;
+        return PublicKeyDouble(pk, pkp);
+    }
+    struct Item;
+    // SecretKey::sign (:174-194) and sign_double (src/keys/secret/double.rs:56-85) given the RNG draw `rnd` that the hedged nonce mixes in
+    std::optional<Signature> sign(const JubJubScalar& rnd, const BlsScalar& message) const;
+    std::optional<SignatureDouble> sign_double(const JubJubScalar& rnd, const BlsScalar& message) const;
+    // one call per batch; with one key for the call (n_sk = 1) when every item holds the same key
+    static std::vector<std::optional<Signature>> sign_batch(const std::vector<Item>& items);
+    static std::vector<std::optional<SignatureDouble>> sign_double_batch(const std::vector<Item>& items);
+    // SecretKey::with_variable_generator (src/keys/secret/var_gen.rs:34-41)
+    SecretKeyVarGen with_variable_generator(const AffinePoint& generator) const { return SecretKeyVarGen(sk_, generator); }
+  private:
+    struct Columns { std::vector<uint8_t> u, R, Rp, status; };
+    static Columns sign_columns(int scheme, const std::vector<Item>& items);
+    JubJubScalar sk_;
+};
+struct SecretKey::Item { SecretKey key; JubJubScalar rnd; BlsScalar message; };
+inline SecretKey::Columns SecretKey::sign_columns(int scheme, const std::vector<Item>& items) {
+    const size_t n = items.size();
+    bool one = n > 1;
+    for (size_t i = 1; i < n && one; ++i) one = items[i].key.sk_ == items[0].key.sk_;
+    const size_t n_sk = one ? 1 : n;
+    const bool dbl = scheme == JJS_SCHEME_DOUBLE;
+    std::vector<uint8_t> sk(n_sk * 32), rnd(n * 32), m(n * 32);
+    Columns c{std::vector<uint8_t>(n * 32), std::vector<uint8_t>(n * 64), std::vector<uint8_t>(dbl ? n * 64 : 0), std::vector<uint8_t>(n)};
+    for (size_t i = 0; i < n; ++i) {
+        if (i < n_sk) std::memcpy(&sk[32 * i], items[i].key.sk_.data(), 32);
+        std::memcpy(&rnd[32 * i], items[i].rnd.data(), 32); std::memcpy(&m[32 * i], items[i].message.data(), 32);
+    }
+    int rc = jjs_sign_fixed(scheme, sk.data(), n_sk, rnd.data(), m.data(), n, c.u.data(), c.R.data(), dbl ? c.Rp.data() : nullptr, nullptr, nullptr,
+                            nullptr, nullptr, c.status.data());
+    if (rc != JJS_OK) throw EngineError(rc, "jjs_sign_fixed");
+    return c;
+}
+inline std::vector<std::optional<Signature>> SecretKey::sign_batch(const std::vector<Item>& items) {
+    std::vector<std::optional<Signature>> out(items.size());
+    if (items.empty()) return out;
+    const Columns c = sign_columns(JJS_SCHEME_SINGLE, items);
+    for (size_t i = 0; i < items.size(); ++i) {
+        if (c.status[i] != JJS_STATUS_OK) continue;
+        Signature s;
+        std::memcpy(s.u.data(), &c.u[32 * i], 32); std::memcpy(s.R.data(), &c.R[64 * i], 64);
+        out[i] = s;
+    }
+    return out;
+}
+inline std::vector<std::optional<SignatureDouble>> SecretKey::sign_double_batch(const std::vector<Item>& items) {
+    std::vector<std::optional<SignatureDouble>> out(items.size());
+    if (items.empty()) return out;
+    const Columns c = sign_columns(JJS_SCHEME_DOUBLE, items);
+    for (size_t i = 0; i < items.size(); ++i) {
+        if (c.status[i] != JJS_STATUS_OK) continue;
+        SignatureDouble s;
+        std::memcpy(s.u.data(), &c.u[32 * i], 32); std::memcpy(s.R.data(), &c.R[64 * i], 64); std::memcpy(s.R_prime.data(), &c.Rp[64 * i], 64);
+        out[i] = s;
+    }
+    return out;
+}
+inline std::optional<Signature> SecretKey::sign(const JubJubScalar& rnd, const BlsScalar& message) const {
+    return sign_batch({Item{*this, rnd, message}})[0];
+}
+inline std::optional<SignatureDouble> SecretKey::sign_double(const JubJubScalar& rnd, const BlsScalar& message) const {
+    return sign_double_batch({Item{*this, rnd, message}})[0];
+}
 
 // `is_valid` alone (include/jjs_gpu.h jjs_keys_check / jjs_signatures_check): one bool per key or signature -- every point on
 // the curve, not the identity and torsion-free -- without verifying anything; a malformed encoding (a coordinate >= q, a scalar

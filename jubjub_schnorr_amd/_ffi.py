@@ -123,6 +123,11 @@ SIGNATURES = {
     "jjs_public_keys_vargen": [_I, _P, _P, _Z, _Z, _P, _P, _P],
     "jjs_sign_vargen_pt": [_I, _P, _P, _Z, _P, _P, _Z, _P, _P, _P, _P, _P],
     "jjs_debug_sign_limits": [_P],
+    "jjs_sign_fixed_dev": [_I, _P, _Z, _P, _P, _Z, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "jjs_sign_fixed": [_I, _P, _Z, _P, _P, _Z, _P, _P, _P, _P, _P, _P, _P, _P],
+    "jjs_public_keys_fixed_dev": [_I, _P, _Z, _P, _P, _P, _P, _P],
+    "jjs_public_keys_fixed": [_I, _P, _Z, _P, _P, _P, _P],
+    "jjs_debug_sign_fixed_limits": [_P],
     "jjs_verify_all_single": [_P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_double": [_P, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_vargen": [_P, _P, _P, _P, _P, _Z, _P, _P],

@@ -551,6 +551,67 @@ class Engine:
         _ffi.check(self._lib.jjs_debug_sign_limits(out), "jjs_debug_sign_limits")
         return {"resident_lanes": int(out[0]), "shared_generator_from": None if out[1] == 2**64 - 1 else int(out[1])}
 
+    def _fixed(self, sign: bool, scheme: str, sk, rnd, m, wire: bool):
+        if scheme not in ("single", "double"):
+            raise ValueError(f"scheme {scheme!r}: single or double (the var-generator scheme signs with sign_vargen_pt)")
+        dbl, sid = scheme == "double", self._SCHEME_IDS[scheme]
+        nk = sk.shape[0]
+        n = rnd.shape[0] if sign else nk
+        if nk != n and nk != 1:
+            raise ValueError(f"sk has {nk} rows: one per item ({n}) or one for the call")
+        # the outputs in the ABI's order: (rows, width), None for what the call does not ask for
+        sig = [(n, 32), (n, 64), (n, 64) if dbl else None, (nk, 64), (nk, 64) if dbl else None,
+               (n, 96 if dbl else 64) if wire else None, (nk, 64 if dbl else 32) if wire else None]
+        shapes = sig if sign else [sig[3], sig[4], sig[6]]
+        if not _is_torch(sk):
+            hsk = self._host(sk, 32)
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+            outs = [np.zeros(s, np.uint8) if s else None for s in shapes]
+            status = np.zeros(n, np.uint8)
+            if not sign:
+                _ffi.check(self._lib.jjs_public_keys_fixed(sid, p(hsk), n, *[p(a) for a in outs], p(status)), "jjs_public_keys_fixed")
+            else:
+                hrnd, hm = self._host(rnd, 32), self._host(m, 32)
+                if hm.shape[0] != n:
+                    raise ValueError("rnd and m do not have the same rows")
+                _ffi.check(self._lib.jjs_sign_fixed(sid, p(hsk), nk, p(hrnd), p(hm), n, *[p(a) for a in outs], p(status)), "jjs_sign_fixed")
+            return tuple(a for a in outs if a is not None) + (status,)
+        import torch
+        new = lambda s: torch.empty((max(s[0], 1), s[1]), dtype=torch.uint8, device=sk.device)[:s[0]]  # noqa: E731
+        o = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and n else None  # noqa: E731
+        outs = [new(s) if s else None for s in shapes]
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=sk.device)[:n]
+        if not sign:
+            _ffi.check(self._lib.jjs_public_keys_fixed_dev(sid, self._dev_ptr(sk, 32, n), n, *[o(t) for t in outs], o(status), self._stream()),
+                       "jjs_public_keys_fixed_dev")
+        else:
+            _ffi.check(self._lib.jjs_sign_fixed_dev(sid, self._dev_ptr(sk, 32, nk), nk, self._dev_ptr(rnd, 32, n), self._dev_ptr(m, 32, n), n,
+                                                    *[o(t) for t in outs], o(status), self._stream()), "jjs_sign_fixed_dev")
+        return tuple(t for t in outs if t is not None) + (status,)
+
+    def public_keys_fixed(self, scheme: str, sk, wire: bool = False):
+        """`PublicKey::from(&SecretKey)` (scheme "single") or `PublicKeyDouble::from(&SecretKey)` ("double") for a batch, with
+        range checks and statuses.  sk (n, 32).  torch CUDA tensors run asynchronously on the current stream
+        (jjs_public_keys_fixed_dev), numpy arrays block (jjs_public_keys_fixed).  NOT constant time: test and benchmark material.
+        Returns (PK[, PK'][, pk_w], status): the affine keys (n, 64), with `wire` also `to_bytes` of them, (n, 32) or (n, 64);
+        status (n,) 0, or 3 for sk >= r, with zero rows."""
+        return self._fixed(False, scheme, sk, None, None, wire)
+
+    def sign_fixed(self, scheme: str, sk, rnd, m, wire: bool = False):
+        """`SecretKey::sign` (scheme "single") or `SecretKey::sign_double` ("double") for a batch given the RNG draws.  rnd and m
+        (n, 32); sk (n, 32), or ONE row: the key of the whole call, and then the key outputs have one row.  Dispatch as
+        `public_keys_fixed`.  NOT constant time: test and benchmark material.  Returns (u, R[, R'], PK[, PK'][, sig_w, pk_w],
+        status): with `wire` also `Signature::to_bytes`, (n, 64) or (n, 96), and the keys' `to_bytes`; status 3 for sk >= r,
+        rnd >= r or m >= q, with zero rows."""
+        return self._fixed(True, scheme, sk, rnd, m, wire)
+
+    def sign_fixed_limits(self) -> dict:
+        """jjs_debug_sign_fixed_limits: the lanes of the SecretKey signing kernels resident at once, and the smallest n from which
+        a signing call with one key takes the keyed route (None: no call takes it by size)."""
+        out = (ctypes.c_uint64 * 2)()
+        _ffi.check(self._lib.jjs_debug_sign_fixed_limits(out), "jjs_debug_sign_fixed_limits")
+        return {"resident_lanes": int(out[0]), "keyed_from": None if out[1] == 2**64 - 1 else int(out[1])}
+
     def multisig_sign_round1(self, r, s):
         """`sign_round_1` for a batch given the two RNG draws (reference src/multisig.rs:169-184): R = r*G, S = s*G.  torch CUDA
         tensors (n, 32); NOT constant time.  Returns (R, S, bad): bad[i] = 1 where r[i] or s[i] is not a canonical
@@ -936,6 +997,79 @@ class SecretKeyVarGen:
         if any(x is None for x in out):
             raise ValueError("a key's generator format is neither affine nor wire")
         return out
+
+
+_R_ORDER = 0x0E7DB4EA6533AFA906673B0101343B00A6682093CCC81082D0970E5ED6F72CB7    # the JubJubScalar modulus
+
+
+@dataclass(frozen=True)
+class SecretKey:
+    """`SecretKey(JubJubScalar)` (reference src/keys/secret.rs): the 32 little-endian bytes of the scalar.  Signing and key
+    derivation run on the device (jjs_sign_fixed, jjs_public_keys_fixed) and are a generator of test and benchmark material,
+    NOT constant time: never use with production keys."""
+    sk: bytes
+
+    @staticmethod
+    def from_bytes(data: bytes) -> "SecretKey":
+        """`SecretKey::from_bytes` (:120-126): refuses a scalar that is not below the group order with `Malformed` (the
+        reference's Error::InvalidData), by an integer compare on the host."""
+        data = _b(data, 32)
+        if int.from_bytes(data, "little") >= _R_ORDER:
+            raise Malformed()
+        return SecretKey(data)
+
+    def to_bytes(self) -> bytes:
+        return self.sk
+
+    def public_key(self) -> "PublicKey":
+        """`PublicKey::from(&SecretKey)`: sk * G."""
+        PK, st = engine().public_keys_fixed("single", _rows([self.sk], 32))
+        _raise_first(st)
+        return PublicKey(PK[0].tobytes())
+
+    def public_key_double(self) -> "PublicKeyDouble":
+        """`PublicKeyDouble::from(&SecretKey)`: (sk * G, sk * G')."""
+        PK, PKp, st = engine().public_keys_fixed("double", _rows([self.sk], 32))
+        _raise_first(st)
+        return PublicKeyDouble(PK[0].tobytes(), PKp[0].tobytes())
+
+    def sign(self, rnd: bytes, message: bytes) -> "Signature":
+        """`SecretKey::sign` (:174-194) given the RNG draw `rnd` the hedged nonce mixes in (32 bytes, < r)."""
+        return self.sign_batch([(self, rnd, message)])[0]
+
+    def sign_double(self, rnd: bytes, message: bytes) -> "SignatureDouble":
+        """`SecretKey::sign_double` (src/keys/secret/double.rs:56-85) given the RNG draw."""
+        return self.sign_double_batch([(self, rnd, message)])[0]
+
+    @staticmethod
+    def _sign_cols(scheme: str, items: Sequence[tuple]):
+        keys = [k.sk for k, _, _ in items]
+        one = len(items) > 1 and all(k == keys[0] for k in keys)          # every item under the same key: one key for the call
+        out = engine().sign_fixed(scheme, _rows(keys[:1] if one else keys, 32), _rows([r for _, r, _ in items], 32),
+                                  _rows([m for _, _, m in items], 32))
+        _raise_first(out[-1])
+        return out
+
+    @staticmethod
+    def sign_batch(items: Sequence[tuple]) -> list:
+        """items: (SecretKey, rnd bytes, message bytes).  One Signature per item from ONE call (jjs_sign_fixed; with one key for
+        the call when every item holds the same key); raises `Malformed` for the first item the engine refuses."""
+        if not items:
+            return []
+        u, R = SecretKey._sign_cols("single", items)[:2]
+        return [Signature(u[i].tobytes(), R[i].tobytes()) for i in range(len(items))]
+
+    @staticmethod
+    def sign_double_batch(items: Sequence[tuple]) -> list:
+        """The same for `sign_double`: one SignatureDouble per item."""
+        if not items:
+            return []
+        u, R, Rp = SecretKey._sign_cols("double", items)[:3]
+        return [SignatureDouble(u[i].tobytes(), R[i].tobytes(), Rp[i].tobytes()) for i in range(len(items))]
+
+    def with_variable_generator(self, generator: bytes) -> "SecretKeyVarGen":
+        """`SecretKey::with_variable_generator` (src/keys/secret/var_gen.rs:34-41): this scalar under `generator`, affine u || v."""
+        return SecretKeyVarGen.new(self.sk, generator)
 
 
 # ------------------------------------------------------------------------------------------------

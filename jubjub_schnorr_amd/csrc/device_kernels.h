@@ -618,6 +618,32 @@ __global__ __launch_bounds__(BLOCK) void derive_vargen_pt_kernel(sign_vargen_par
     uint32_t* ws = P.workspace + gtid * WS_WORDS_PER_LANE;
     for (uint64_t item = gtid; item < P.n; item += total) sign_vargen_item<false>(P, item, ws);
 }
+// The single and double signers with a SecretKey (sign_fixed.h): one lane per item, grid-stride over the resident lanes, the lane's
+// workspace as sign_kernel's.  A kernel per scheme and route: each keeps its own registers (the per-item double body holds four
+// points across its inversion).  NOT constant time: generators of test and benchmark material.
+template <bool DOUBLE, bool KEYED>
+__device__ __forceinline__ void sign_fixed_lanes(const sign_fixed_params& P) {
+    const uint64_t gtid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    uint32_t* ws = P.workspace + gtid * WS_WORDS_PER_LANE;
+    for (uint64_t item = gtid; item < P.n; item += total) sign_fixed_item<DOUBLE, KEYED>(P, item, ws);
+}
+__global__ __launch_bounds__(BLOCK) void sign_fixed_single_kernel(sign_fixed_params P) { sign_fixed_lanes<false, false>(P); }
+__global__ __launch_bounds__(BLOCK) void sign_fixed_double_kernel(sign_fixed_params P) { sign_fixed_lanes<true, false>(P); }
+// ... the keyed route: the lanes read the call's one key from the record (P.key) that sign_fixed_key_kernel, one block with one
+// working lane, left in front of this launch
+__global__ __launch_bounds__(BLOCK) void sign_fixed_keyed_single_kernel(sign_fixed_params P) { sign_fixed_lanes<false, true>(P); }
+__global__ __launch_bounds__(BLOCK) void sign_fixed_keyed_double_kernel(sign_fixed_params P) { sign_fixed_lanes<true, true>(P); }
+__global__ __launch_bounds__(BLOCK) void sign_fixed_key_kernel(sign_fixed_params P, int dbl) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    if (dbl) sign_fixed_key<true>(P); else sign_fixed_key<false>(P);
+}
+__global__ __launch_bounds__(BLOCK) void derive_fixed_kernel(sign_fixed_params P, int dbl) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t item = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; item < P.n; item += total) {
+        if (dbl) derive_fixed_item<true>(P, item); else derive_fixed_item<false>(P, item);
+    }
+}
 
 // PublicKey::from(&SecretKey) = sk * G (reference src/keys/public.rs:54-60) and the second half of
 // PublicKeyDouble::from (sk * G', src/keys/public/double.rs:47-57): fixed-base only, NOT constant time.

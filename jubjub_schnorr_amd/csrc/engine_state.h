@@ -246,7 +246,7 @@ struct device_state {
     device_mem<uint32_t> comb_gn;
     device_mem<uint8_t> tag;
     device_mem<unsigned long long> tally;
-    int grid_sign = 0, grid_resolve = 0, grid_prepare = 0, grid_key_verify = 0;
+    int grid_sign = 0, grid_sign_fixed = 0, grid_resolve = 0, grid_prepare = 0, grid_key_verify = 0;
     event_owner last_use;          // host-buffer calls: end of the last use of the staging arena and the counters
     device_mem<uint32_t> dlog_pow; // square-root tables (decode.h)
     device_mem<uint8_t> dlog_hash;
@@ -281,6 +281,8 @@ struct device_state {
     grow_only<uint8_t> ks_stage;         // ... their device copies of the inputs and outputs (bytes; under host_mu)
     grow_only<uint8_t> sign_tables;      // jjs_sign_vargen_pt*: the chain of bases and the window tables of a call's shared generator (bytes);
                                          // used in the order of slot 0's event, grows under the engine's mutex; jjs_trim frees it
+    grow_only<uint8_t> sign_key;         // jjs_sign_fixed* with one key for the call: the record of the keyed route's pre-pass (sign_fixed.h,
+                                         // bytes); used and grown as sign_tables; jjs_trim frees it
     grow_only<uint8_t> msig_stage;       // host-buffer multisig calls (jjs_multisig_combine, jjs_msig_group_combine): their columns and
                                          // outputs (bytes), on ks_stream under host_mu; it grows under the engine's mutex as well, which
                                          // jjs_memory_stats reads it under; jjs_trim frees it

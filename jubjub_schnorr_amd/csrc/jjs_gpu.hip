@@ -25,6 +25,7 @@
 //   msig_verify_calls.h  the verifier's half: aggregate_pk, and aggregate_pk followed by the single-scheme verification
 //   msig_sign_calls.h  the signer's half: sign_round_1, and sign_round_2 over whole ragged batches (a generator of test material)
 //   sign_vargen_calls.h  var-generator signing and key derivation with the generator as a point, both forms (test material)
+//   sign_fixed_calls.h  signing and key derivation with a SecretKey in the single and double schemes, both forms (test material)
 //   host_lanes.h       the small ones (included among the entry points, behind the table of call shapes): staging lanes
 //                      outside the engine's mutex, calls of several threads in one launch
 //   (here)             the table of call shapes and the staged_call builder it drives; the extern "C" entry points
@@ -66,6 +67,7 @@
 #include "keyset_lookup.h"
 #include "sign_core.h"
 #include "sign_vargen.h"
+#include "sign_fixed.h"
 #include "multisig_core.h"
 #include "msig_group.h"
 #include "msig_keyset.h"
@@ -149,6 +151,18 @@ int init_device(device_state& d, int ordinal) {
     d.slots[0].grid_verify = prop.multiProcessorCount * per_cu_v;
     int lanes_blocks = d.slots[0].grid_verify > d.grid_sign ? d.slots[0].grid_verify : d.grid_sign;
     if (d.grid_msig > lanes_blocks) lanes_blocks = d.grid_msig;
+    {   // the SecretKey signers (sign_fixed.h): one grid for their four kernels, within the lanes the workspace is sized for
+        int per_cu_f = 0, least = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&least, sign_fixed_single_kernel, BLOCK, 0));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, sign_fixed_double_kernel, BLOCK, 0));
+        if (per_cu_f < least) least = per_cu_f;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, sign_fixed_keyed_single_kernel, BLOCK, 0));
+        if (per_cu_f < least) least = per_cu_f;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, sign_fixed_keyed_double_kernel, BLOCK, 0));
+        if (per_cu_f < least) least = per_cu_f;
+        d.grid_sign_fixed = prop.multiProcessorCount * (least < 1 ? 1 : least);
+        if (d.grid_sign_fixed > lanes_blocks) d.grid_sign_fixed = lanes_blocks;
+    }
     for (int i = 0; i < N_SLOTS; ++i) {
         call_slot& c = d.slots[i];
         const bool big = i == 0 || i == SECOND_BIG_SLOT;
@@ -725,6 +739,7 @@ int jjs_trim(void) {
         HIP_TRY(hipDeviceSynchronize());
         free_retired(*d);
         HIP_TRY(d->sign_tables.free());                        // the tables of a signing call's shared generator
+        HIP_TRY(d->sign_key.free());                           // the key record of a signing call with one key
         HIP_TRY(d->msig_stage.free());                         // the staging of the host-buffer multisig calls (host_mu is held)
         for (call_slot& c : d->slots) {
             if (!c.key_pool) continue;
@@ -748,7 +763,7 @@ int jjs_memory_stats(uint64_t out[JJS_MEMORY_STATS]) {
     }
     for (const host_lane& l : g->lanes) lanes += l.dev.reported_bytes() + l.pinned.reported_bytes();
     out[JJS_MEMORY_KEY_POOLS] = pool;
-    out[JJS_MEMORY_SLOT_BUFFERS] = slots + g->sign_tables.reported_bytes();
+    out[JJS_MEMORY_SLOT_BUFFERS] = slots + g->sign_tables.reported_bytes() + g->sign_key.reported_bytes();
     out[JJS_MEMORY_HOST_STAGING] = lanes + g->stage.reported_bytes() + g->pinned.reported_bytes() + g->msig_stage.reported_bytes();
     out[JJS_MEMORY_RETIRED] = g->retired_bytes;
     return JJS_OK;
@@ -1135,6 +1150,7 @@ int jjs_public_keys_dev(const void* sk, size_t n, void* PK_out, void* PKp_out, v
 }
 
 #include "sign_vargen_calls.h"
+#include "sign_fixed_calls.h"
 
 // ---- debug primitives ------------------------------------------------------------------------------
 int jjs_debug_fq_mul_dev(const void* a, const void* b, size_t n, void* out, void* stream) {
@@ -1196,6 +1212,7 @@ int jjs_debug_force_path(int which) {
     g_force_window = ((which >> 8) & 15) == KT_WINDOW_NARROW ? ((which >> 8) & 15) : 0;   // 0x500: narrow key-table windows whatever the keys
     g_force_verdict = (which & 0x2000) ? 1 : ((which & 0x4000) ? 2 : 0);   // jjs_verify_all_*: 0x2000 the verdict algorithm, 0x4000 the per-item path
     g_force_sign_shared = (which & 0x8000) ? 1 : ((which & 0x200000) ? 2 : 0);   // jjs_sign_vargen_pt* with one generator: 0x8000 the shared-generator route at any n, 0x200000 the per-item route
+    g_force_sign_keyed = (which & 0x400000) ? 1 : ((which & 0x800000) ? 2 : 0);   // jjs_sign_fixed* with one key: 0x400000 the keyed route at any n, 0x800000 the per-item route
     g_force_msm_window = (which >> 16) & 31;                                // ... and bits 16-20 its window width (8-16; 0 by size)
     return JJS_OK;
 }
