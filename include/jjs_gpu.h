@@ -269,6 +269,57 @@ int jjs_keyset_verify_keys_dev(jjs_keyset ks, int format, const void* K0, const 
 int jjs_keyset_verify_keys(jjs_keyset ks, int format, const uint8_t* K0, const uint8_t* K1, const uint8_t* s0, const uint8_t* s1,
                            const uint8_t* s2, const uint8_t* m, size_t n, uint8_t* status, uint64_t tally[4], uint32_t* idx_out);
 
+/* ---- adding keys to a live key set ------------------------------------------------------------------
+ * A validator set, a wallet's accounts and the signers of a contract gain keys over time.  jjs_keyset_add extends a set where
+ * it stands: old indices never change, the old keys are neither decoded nor tabled again, and calls against the set go on
+ * meanwhile -- they see the old set or the new one, never a mixture.
+ *   jjs_keyset_add(ks, format, keys, keys2, n, mode, key_status, idx_out, n_added): keys, keys2 and format as
+ *     jjs_keyset_create takes them for the set's scheme; host buffers; blocking.  key_status (n bytes), idx_out (n x uint32)
+ *     and n_added are nullable.
+ *     JJS_KEYSET_ADD_APPEND  candidate i is registered at index n_old + i whatever it is -- malformed keys, keys that are not
+ *       `is_valid` and duplicates included, as jjs_keyset_create registers them.  idx_out[i] = n_old + i, *n_added = n,
+ *       key_status as jjs_keyset_create writes it.  Afterwards the set is indistinguishable from jjs_keyset_create of the old
+ *       keys followed by the new ones: every jjs_keyset_* and jjs_multisig_*_keyset* call gives the same bytes.
+ *     JJS_KEYSET_ADD_UNIQUE  for sets populated from traffic: the caller need not know what the set holds.  A candidate with
+ *       key_status 3 is not registered and gets idx_out[i] = 0xFFFFFFFF.  Any other candidate is compared by the canonical
+ *       affine row(s) jjs_keyset_create would store for it: if jjs_keyset_find would find that row, idx_out[i] is that (lowest)
+ *       index and nothing is registered (counted under JJS_KEYSET_ADD_KNOWN); otherwise the first occurrence in input order is
+ *       registered at n_old + (the number of earlier first occurrences) and every later equal candidate gets the same index.
+ *       Keys that are not `is_valid` are registered.  *n_added = the number of first occurrences; key_status[i] is the status
+ *       of the key at idx_out[i] (3 for a candidate that was not registered).  The indices are a function of the input alone.
+ *       Afterwards the set equals jjs_keyset_create of the old keys followed by the first occurrences in order.
+ *   Capacity.  jjs_keyset_create allocates exactly its keys.  An add that fits the capacity writes the new rows, flags, tables
+ *     and lookup entries in place behind the old ones and moves nothing.  One that does not fit allocates room for
+ *     max(needed, capacity + capacity / 2) keys (at most 2^24), copies device to device, builds the new keys and retires the old
+ *     allocation, which launches already queued still read and jjs_trim frees.
+ *     JJS_KEYSET_DEVICE_BYTES counts the set's one allocation; every add in place also takes a 256-byte block for the new
+ *     size (4 KB per 16 adds, kept until the set moves or is destroyed), which that word leaves out.
+ *   jjs_keyset_reserve(ks, n_keys_total): grows the capacity to exactly n_keys_total keys; nothing when the set has that much.
+ *   jjs_keyset_growth(ks, out): JJS_KEYSET_CAPACITY .. JJS_KEYSET_ADD_KNOWN below.
+ * One add or reserve runs at a time per set; another waits for it.  jjs_shutdown waits for an add in progress, and so does
+ * jjs_trim.  A jjs_keyset_destroy that overtakes an add makes the add return -1; nothing leaks.  A failed add leaves the set
+ * as it was.
+ * Return codes: those of jjs_keyset_create; n == 0 returns 0 and changes nothing; -1 when n_old + n or n_keys_total exceeds
+ * 2^24 or the mode is unknown.
+ * Measured (profiles/r19_keyset_add.jsonl, tools/keyset_add_rate.py), an add against jjs_keyset_create of all the
+ * keys: 64 keys added to 32 768 in place 1.00 ms against 11.5 ms (0.09x), moving the set 4.0 ms (0.35x); 4 096 added to 32 768
+ * 2.2 / 5.3 against 12.7 ms; to 4 096 keys 0.47-0.64x in place, 0.65-0.74x moving; to a set of 64 keys an add costs what the
+ * create costs (0.99-1.05x: about 1 ms either way, the floor of a blocking call that allocates).  jjs_keyset_verify_dev against a
+ * grown set and a created one: equal within the spread (1.000-1.005x).  The existing routes against the parent commit, processes
+ * alternating in swapped order (scripts/keyset_add_ab.sh): level at 1, 64 and 131 072 items and in bench.py (median +0.06 %). */
+#define JJS_KEYSET_ADD_APPEND 0
+#define JJS_KEYSET_ADD_UNIQUE 1
+int jjs_keyset_add(jjs_keyset ks, int format, const uint8_t* keys, const uint8_t* keys2, size_t n, int mode, uint8_t* key_status,
+                   uint32_t* idx_out, size_t* n_added);
+int jjs_keyset_reserve(jjs_keyset ks, size_t n_keys_total);
+#define JJS_KEYSET_CAPACITY 0                     /* keys the copies hold room for */
+#define JJS_KEYSET_ADD_CALLS 1
+#define JJS_KEYSET_RELOCATIONS 2                  /* adds / reserves that moved the copies to a larger allocation */
+#define JJS_KEYSET_LOOKUP_REBUILDS 3              /* adds after which the lookup table has more slots */
+#define JJS_KEYSET_ADD_KNOWN 4                    /* UNIQUE candidates answered with an index that already existed */
+#define JJS_KEYSET_GROWTH 5
+int jjs_keyset_growth(jjs_keyset ks, uint64_t out[JJS_KEYSET_GROWTH]);
+
 /* ---- `is_valid` alone: keys and signatures checked without verifying anything --------------------
  * The reference's six validity predicates -- PublicKey / PublicKeyDouble / PublicKeyVarGen::is_valid, Signature /
  * SignatureDouble / SignatureVarGen::is_valid -- and the `from_bytes` of those types, in bulk: what a caller runs when a key or

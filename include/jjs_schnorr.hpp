@@ -670,6 +670,44 @@ class KeySet {
         find(JJS_FORMAT_AFFINE, c.data(), nullptr, keys.size(), idx.data());
         return idx;
     }
+    // ADDING KEYS to the live set (jjs_keyset_add): keys, keys2 and format as the raw constructor takes them.  Appended, candidate
+    // i is registered at index n_old + i whatever it is; with `unique` a candidate the set (or an earlier candidate) already holds
+    // gets that index and a malformed one 0xFFFFFFFF.  Old indices never change; calls from other threads go on meanwhile.
+    // key_status() follows the set.  Host buffers, blocking.
+    struct Added {
+        std::vector<uint32_t> idx;            // per candidate: the index its key is registered at
+        std::vector<uint8_t> key_status;      // per candidate: 0 valid, 1 not `is_valid`, 3 malformed
+        size_t n_added = 0;                   // keys the set gained
+    };
+    Added add(int format, const uint8_t* keys, const uint8_t* keys2, size_t n, bool unique = false) {
+        Added a;
+        a.idx.resize(n); a.key_status.resize(n);
+        int rc = jjs_keyset_add(handle_, format, keys, keys2, n, unique ? JJS_KEYSET_ADD_UNIQUE : JJS_KEYSET_ADD_APPEND, a.key_status.data(),
+                                a.idx.data(), &a.n_added);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_add");
+        for (size_t i = 0; i < n; ++i) {
+            if (a.idx[i] == 0xFFFFFFFFu || a.idx[i] < status_.size()) continue;
+            status_.resize((size_t)a.idx[i] + 1);
+            status_[a.idx[i]] = a.key_status[i];
+        }
+        return a;
+    }
+    Added add(const std::vector<PublicKey>& keys, bool unique = false) {
+        if (scheme_ != JJS_SCHEME_SINGLE) throw std::invalid_argument("PublicKey candidates need a key set of PublicKey");
+        const detail::Soa c = column(keys, [](const PublicKey& k) { return k.as_ref(); });
+        return add(JJS_FORMAT_AFFINE, c.data(), nullptr, keys.size(), unique);
+    }
+    // room for n_keys_total keys in all (jjs_keyset_reserve): the adds up to there move nothing
+    void reserve(size_t n_keys_total) {
+        int rc = jjs_keyset_reserve(handle_, n_keys_total);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_reserve");
+    }
+    std::array<uint64_t, JJS_KEYSET_GROWTH> growth() const {
+        std::array<uint64_t, JJS_KEYSET_GROWTH> out{};
+        int rc = jjs_keyset_growth(handle_, out.data());
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_growth");
+        return out;
+    }
     // one verdict for the batch (jjs_keyset_verify_all): true when every item verifies; `status` (nullable, n bytes) holds
     // the statuses of verify() when the verdict is false and is all zero otherwise
     bool verify_all(int format, const uint32_t* key_idx, const uint8_t* s0, const uint8_t* s1, const uint8_t* s2, const uint8_t* m, size_t n,

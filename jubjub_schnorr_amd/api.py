@@ -1391,6 +1391,48 @@ class KeySet:
         _ffi.check(self._lib.jjs_keyset_info(self.handle, out), "jjs_keyset_info")
         return dict(zip(self.INFO_NAMES, (int(v) for v in out)))
 
+    # ---- adding keys to the live set (include/jjs_gpu.h "adding keys to a live key set") -----------------------
+    GROWTH_NAMES = ("capacity", "add_calls", "relocations", "lookup_rebuilds", "add_known")
+
+    def add(self, keys, keys2=None, fmt: str = "affine", unique: bool = False):
+        """Register more keys (`keys`, `keys2`, `fmt` as `Engine.keyset` takes them; numpy, blocking).  Appended, candidate i
+        goes to index n_keys + i whatever it is; with `unique` a candidate the set or an earlier candidate already holds gets
+        that index, and a malformed one `KeySet.MISS`.  Old indices never change.  Returns (idx, key_status), one entry per
+        candidate; `n_keys` and `key_status` follow the set."""
+        if self.handle == 0:
+            raise _ffi.JjsError("the key set is closed")
+        two = self.scheme != "single"
+        if fmt == "wire":
+            if keys2 is not None:
+                raise ValueError("wire keys come in one column (pk || pk' or pk || generator): keys2 must be None")
+            k1, k2 = self._eng._host(keys, 64 if two else 32), None
+        else:
+            w = 96 if fmt == "ext" else 64
+            k1 = self._eng._host(keys, w)
+            k2 = self._eng._host(keys2, w) if two else None
+            if two and k2.shape[0] != k1.shape[0]:
+                raise ValueError("both key columns must have the same number of keys")
+        n = k1.shape[0]
+        idx, status, added = np.empty(n, np.uint32), np.empty(n, np.uint8), ctypes.c_size_t(0)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+        _ffi.check(self._lib.jjs_keyset_add(self.handle, Engine._FORMAT_IDS[fmt], p(k1), p(k2), n, 1 if unique else 0, p(status), p(idx),
+                                             ctypes.byref(added)), "jjs_keyset_add")
+        grown = np.zeros(self.n_keys + added.value, np.uint8)
+        grown[:self.n_keys] = self.key_status
+        fresh = (idx != self.MISS) & (idx >= self.n_keys)
+        grown[idx[fresh]] = status[fresh]
+        self.key_status, self.n_keys = grown, self.n_keys + added.value
+        return idx, status
+
+    def reserve(self, n: int) -> None:
+        """Room for `n` keys in all: the adds up to there write in place and move nothing."""
+        _ffi.check(self._lib.jjs_keyset_reserve(self.handle, n), "jjs_keyset_reserve")
+
+    def growth(self) -> dict:
+        out = (ctypes.c_uint64 * len(self.GROWTH_NAMES))()
+        _ffi.check(self._lib.jjs_keyset_growth(self.handle, out), "jjs_keyset_growth")
+        return dict(zip(self.GROWTH_NAMES, (int(v) for v in out)))
+
     def close(self) -> None:
         if self.handle:
             h, self.handle = self.handle, 0

@@ -424,7 +424,8 @@ void free_retired(device_state& d) {      // the caller has made sure that the d
     d.retired_bytes = 0;
 }
 // Registered objects: key sets (keyset.h; jjs_keyset_*) and multisig signer groups (msig_group.h; jjs_msig_group_*).  An object
-// is immutable once built and has one copy per driven device.  Handles are (generation << 32) | (registry index + 1): a
+// has one copy per driven device and is immutable once built -- but for a key set that grows (keyset_add_calls.h), which changes
+// nothing a queued launch reads and publishes its new size and pointers under the engine's mutex.  Handles are (generation << 32) | (registry index + 1): a
 // destroyed object's index may be reused, its generation never is, so a stale handle finds nothing (JJS_ERR_ARG) and never
 // reaches freed memory -- and the generation counter is ONE for every kind, so a handle of one kind is no handle of another.
 // A registry is only read or changed under the engine's mutex; a destroyed object's device memory is retired (retire()), so
@@ -432,6 +433,7 @@ void free_retired(device_state& d) {      // the caller has made sure that the d
 struct device_copy {
     device_state* dev = nullptr;
     device_mem<uint8_t> mem;               // one allocation: the regions its owner carves from it
+    std::vector<device_mem<uint8_t>> side; // small allocations beside it that live and retire with it (a grown key set's size words)
 };
 template <class Copy>
 struct registered {
@@ -459,7 +461,12 @@ struct registry {                          // every member: under L.mu
     }
     static void retire_copies(Entry& e) {             // the devices of its copies are alive
         device_state* const keep = g;
-        for (auto& c : e.copies) { g = c.dev; c.mem.release(); }
+        for (auto& c : e.copies) {
+            g = c.dev;
+            c.mem.release();
+            for (auto& m : c.side) m.release();
+            c.side.clear();
+        }
         g = keep;
     }
     bool destroy(uint64_t h) {             // launches already queued still read it: freed by jjs_trim / jjs_shutdown
@@ -484,7 +491,7 @@ auto copy_for(const Entry& e, const device_state* d) -> decltype(&e.copies[0]) {
 // A set's copy: its affine keys (64 B per point, the challenge hash reads them), the flags of its points, their window tables
 // (KEYSET_WINDOW bits), the lookup table of the by-key calls and three device words (n_keys, n_keys, the window width: the counters the grouping kernels read, and
 // the key-table flag of verify_params).
-struct keyset_copy : device_copy {
+struct keyset_regions {
     uint8_t* keys[2] = {};                 // n_keys x 64 affine, per point column
     uint8_t* flags[2] = {};                // n_keys KT_KEY_* flags, per point column
     uint32_t* tables[2] = {};              // n_keys x kt_positions(w) x kt_table_words(w), per point column
@@ -492,12 +499,23 @@ struct keyset_copy : device_copy {
     uint32_t* lookup = nullptr;            // the lookup table (keyset_lookup.h): lookup_mask + 1 slots ...
     uint32_t lookup_mask = 0;
     uint8_t* on_curve = nullptr;           // ... and n_keys bytes: every point of the key is on the curve (what a wire query may hit)
+    // A set that has grown (keyset_add_calls.h): its allocation holds room for the entry's `capacity` keys in every region and
+    // for `lookup_room` slots of lookup tables (0: the one table create built).
+    uint32_t lookup_room = 0;
+};
+struct keyset_copy : device_copy, keyset_regions {
+    // every published size of a grown set has a words block of its own: the first in the allocation, the later ones in `side`,
+    // KEYSET_WORD_BLOCKS to an allocation
+    uint32_t word_blocks = 0;              // blocks of side.back() that are taken
 };
 struct keyset_entry : registered<keyset_copy> {
     int scheme = 0;
     uint32_t n_keys = 0, n_cols = 0, valid = 0;
     uint64_t small_calls = 0, large_calls = 0;
     uint64_t lookup_seed = 0;              // of the lookup table's hash: one per set, the same on every device
+    uint32_t capacity = 0;                 // keys every copy holds room for (n_keys until the set grows)
+    bool growing = false;                  // a jjs_keyset_add / jjs_keyset_reserve is extending the copies outside the mutex: the next one waits
+    uint64_t growth[JJS_KEYSET_GROWTH] = {};   // jjs_keyset_growth ([JJS_KEYSET_CAPACITY] is `capacity`)
 };
 struct msig_group_copy : device_copy {
     uint8_t* agg_pk = nullptr;             // 64 B affine
@@ -518,6 +536,9 @@ registry<msig_group_entry>& g_msig_groups = *new registry<msig_group_entry>;
 // host-buffer calls against a key set, the verdict algorithm's host route): jjs_shutdown waits for them before it frees a
 // device.  Counted in under L.mu ...
 uint32_t g_blocking_calls = 0;
+// ... and those among them that write into a registered set's copies (jjs_keyset_add, jjs_keyset_reserve): jjs_trim waits for
+// them, because a set destroyed under such a call is retired memory the call may still be writing.
+uint32_t g_keyset_grows = 0;
 struct blocking_call_leave {               // ... and out here, on every path
     ~blocking_call_leave() {
         std::lock_guard<std::mutex> lock(L.mu);

@@ -65,6 +65,7 @@
 #include "key_tables.h"
 #include "keyset.h"
 #include "keyset_lookup.h"
+#include "keyset_add.h"
 #include "sign_core.h"
 #include "sign_vargen.h"
 #include "sign_fixed.h"
@@ -85,6 +86,7 @@ namespace {
 #include "device_kernels.h"
 #include "verdict_kernels.h"
 #include "keyset_verdict_kernels.h"
+#include "keyset_add_kernels.h"
 #include "device_owners.h"
 #include "engine_state.h"
 #include "verify_job.h"
@@ -533,6 +535,7 @@ static int resident_call(const call_shape& S, const void* const* d, size_t n, vo
 
 #include "host_lanes.h"
 #include "keyset_calls.h"
+#include "keyset_add_calls.h"
 #include "points_check_calls.h"
 
 // a host-buffer call: blocking
@@ -731,6 +734,8 @@ int jjs_trim(void) {
     std::vector<std::unique_lock<std::mutex>> big;            // no large host-buffer call in progress on any device
     for (device_state* d : devs) big.emplace_back(d->host_mu);
     std::unique_lock<std::mutex> lock(L.mu);
+    // a key set that grows in place may have been destroyed meanwhile: what it still writes is not freed under it (keyset_add_calls.h)
+    L.lane_cv.wait(lock, [] { return g_keyset_grows == 0; });
     if (int rc = check_ready()) return rc;
     if (devs != L.devs) return fail(JJS_ERR_NOT_INIT, "the engine was re-initialised during the call");
     device_restore restore;

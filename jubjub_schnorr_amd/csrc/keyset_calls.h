@@ -444,7 +444,7 @@ int jjs_keyset_create(int scheme, int format, const uint8_t* keys, const uint8_t
         return rc;
     keyset_entry& k = *call.e;
     const uint32_t cols = keyset_cols(scheme);
-    k.scheme = scheme; k.n_keys = (uint32_t)n_keys; k.n_cols = cols;
+    k.scheme = scheme; k.n_keys = (uint32_t)n_keys; k.n_cols = cols; k.capacity = (uint32_t)n_keys;
     k.lookup_seed = next_seed();
 #if defined(JJS_PROFILING)
     if (g_pin_hash_seed) k.lookup_seed = 0;
