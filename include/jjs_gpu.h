@@ -320,6 +320,69 @@ int jjs_keyset_reserve(jjs_keyset ks, size_t n_keys_total);
 #define JJS_KEYSET_GROWTH 5
 int jjs_keyset_growth(jjs_keyset ks, uint64_t out[JJS_KEYSET_GROWTH]);
 
+/* ---- removing keys from a live key set, and compacting it -------------------------------------------
+ * A validator that is slashed or rotates out, a contract signer that is revoked, must stop verifying -- at once, without the
+ * set being built again and without any other index changing.
+ *   jjs_keyset_remove(ks, idx, n, result, n_removed): idx is a host buffer of n key indices; blocking; in place.  Afterwards the
+ *     set is indistinguishable from jjs_keyset_create of the same keys in the same order with every removed key replaced by a
+ *     malformed one (64 bytes of 0xFF per point column): every jjs_keyset_* and jjs_multisig_*_keyset* call and a later
+ *     jjs_keyset_add in either mode give the same bytes -- statuses, tallies, found indices, outputs.
+ *       Indices   no index moves and a removed index is never used again; JJS_KEYSET_KEYS does not change, JJS_KEYSET_VALID_KEYS
+ *                 drops by the number of removed keys that had status 0.
+ *       By index  an item that names a removed key gets status 3, as an index beyond the set does; a multisig transcript that
+ *                 names one gets status 3 and no outputs.
+ *       By key    a removed key is found nowhere (0xFFFFFFFF, JJS_STATUS_KEY_NOT_IN_SET): a key registered at several indices
+ *                 is found at the lowest surviving one, and the host form of jjs_keyset_verify_keys verifies a miss inline.
+ *       A later JJS_KEYSET_ADD_UNIQUE registers a key equal to a removed one anew, at a new index.
+ *     result (nullable, n bytes): the key's status before this call -- 0, 1 or 3; JJS_KEY_WAS_REMOVED for a key that had been
+ *     removed already; JJS_KEY_NOT_IN_RANGE for idx[i] >= the set's keys, which addresses nothing.  An index named twice in one
+ *     call gets the same answer both times.  *n_removed (nullable): the distinct indices this call removed.  Both are a function
+ *     of the input and the set alone.
+ *     A remove frees nothing: JJS_KEYSET_DEVICE_BYTES is unchanged.  jjs_keyset_compact gives the memory back.
+ *     Return codes: n == 0 returns 0 and changes nothing; -4 before jjs_init; -1 for a stale handle or a null idx; -2 for a
+ *     device failure -- a remove that failed may be repeated (removing is idempotent); the set's counts change only on success.
+ *   Calls that overlap a remove.  A remove writes flag bytes and lookup slots that launches already queued read.  A call that
+ *     names no key being removed is unaffected.  Each item of jjs_keyset_verify* / jjs_keyset_verify_keys* that names a key being
+ *     removed gets its status from before the remove or from after it (by index: the before status or 3; by key: the before
+ *     status or JJS_STATUS_KEY_NOT_IN_SET, which it may also get while a higher duplicate of the key survives; with a status
+ *     column a by-key item never reports 3 for a key removed under it, unless the call was queued before the set's first
+ *     jjs_keyset_remove ever came in).  The jjs_multisig_*_keyset* calls read a row's flags once, in the pass that gathers the
+ *     keys: a transcript that names keys being removed gets the answer from before the remove (every such row read before) or
+ *     status 3 and no outputs (any row read after), never outputs of neither state.  jjs_keyset_verify_all* reads the flags in
+ *     two passes: a batch that names a key being removed gets the verdict from before the remove or the verdict 0 with the
+ *     per-item statuses described above, never a verdict 1 that neither state gives.  Calls issued after
+ *     jjs_keyset_remove has returned see it complete.
+ *   jjs_keyset_compact(ks, map_out, map_len, n_keys_out): afterwards the handle names a set that is jjs_keyset_create of the
+ *     surviving keys in their order, byte for byte through every call; keys that were registered malformed or not `is_valid`
+ *     and never removed survive.  map_out (nullable; map_len must equal the old JJS_KEYSET_KEYS, else -1): map_out[i] is the
+ *     new index of old index i, 0xFFFFFFFF for a removed one.  *n_keys_out (nullable): the new count.  No survivors: -1, nothing
+ *     changes (destroy the set instead).  Nothing removed: 0, the identity map, nothing changes.  The set moves to a new
+ *     allocation that holds exactly the survivors (a later add is in place or moving by the usual capacity rule); the old one
+ *     is retired as jjs_keyset_destroy retires it: launches already queued still read it, WITH THE OLD INDICES, and jjs_trim
+ *     frees it.  The move counts under JJS_KEYSET_RELOCATIONS.  EVERY INDEX CHANGES: quiescing the callers that still hold old
+ *     indices (key_idx columns, multisig committees, indices JJS_KEYSET_ADD_UNIQUE handed out) is the caller's business.
+ *   jjs_keyset_removal(ks, out): JJS_KEYSET_REMOVED_KEYS .. JJS_KEYSET_COMPACT_CALLS below.
+ * One add, reserve, remove or compact runs at a time per set; another waits.  jjs_shutdown and jjs_trim wait for one in progress.
+ * Measured (profiles/r20_keyset_remove.jsonl, tools/keyset_remove_rate.py), against jjs_keyset_destroy plus
+ * jjs_keyset_create of the survivors: a remove of 1, 64 or 4 096 keys from 32 768 takes 0.45-0.49 ms against 9.6-11.2 ms
+ * (0.04-0.05x), from 4 096 keys 0.42-0.44 against 2.1-2.2 ms (0.19-0.20x): what the call costs does not grow with k.  A compact
+ * of 32 768 keys with a quarter / a half removed 2.71 / 2.68 ms against 8.7 / 6.5 ms (0.31 / 0.41x), of 4 096 keys 0.69 / 0.60
+ * against 1.90 / 1.61 ms; the survivors' tables move at 2.5-3.7 TB/s read plus written, counted over the whole call.
+ * jjs_keyset_verify_dev against a set with half its keys removed, its compacted form and a created set of the survivors: equal
+ * within the spreads at 1, 64 and 131 072 items (1.000-1.003x).  The existing routes against the parent commit, processes
+ * alternating in swapped order (scripts/keyset_remove_ab.sh): level at 1, 64 and 131 072 items and in bench.py (eight pairs,
+ * medians 8.465 against 8.446 ms per step, either tree 8.41-8.50). */
+#define JJS_KEY_WAS_REMOVED 8                     /* result[] only */
+#define JJS_KEY_NOT_IN_RANGE 0xFF                 /* result[] only */
+int jjs_keyset_remove(jjs_keyset ks, const uint32_t* idx, size_t n, uint8_t* result, size_t* n_removed);
+int jjs_keyset_compact(jjs_keyset ks, uint32_t* map_out, size_t map_len, size_t* n_keys_out);
+#define JJS_KEYSET_REMOVED_KEYS 0                 /* indices currently removed */
+#define JJS_KEYSET_LIVE_KEYS 1                    /* JJS_KEYSET_KEYS minus the above */
+#define JJS_KEYSET_REMOVE_CALLS 2
+#define JJS_KEYSET_COMPACT_CALLS 3
+#define JJS_KEYSET_REMOVAL 4
+int jjs_keyset_removal(jjs_keyset ks, uint64_t out[JJS_KEYSET_REMOVAL]);
+
 /* ---- `is_valid` alone: keys and signatures checked without verifying anything --------------------
  * The reference's six validity predicates -- PublicKey / PublicKeyDouble / PublicKeyVarGen::is_valid, Signature /
  * SignatureDouble / SignatureVarGen::is_valid -- and the `from_bytes` of those types, in bulk: what a caller runs when a key or

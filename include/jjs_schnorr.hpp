@@ -708,6 +708,41 @@ class KeySet {
         if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_growth");
         return out;
     }
+    // REMOVING KEYS from the live set (jjs_keyset_remove), in place: no index moves, a removed index verifies nothing (status 3)
+    // and its key is found nowhere.  key_status() becomes 3 at removed indices.  Host buffers, blocking.
+    struct Removed {
+        std::vector<uint8_t> result;          // per index: the key's status before the call, JJS_KEY_WAS_REMOVED or JJS_KEY_NOT_IN_RANGE
+        size_t n_removed = 0;                 // distinct indices this call removed
+    };
+    Removed remove(const std::vector<uint32_t>& idx) {
+        Removed r;
+        r.result.resize(idx.size());
+        int rc = jjs_keyset_remove(handle_, idx.data(), idx.size(), r.result.data(), &r.n_removed);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_remove");
+        for (uint32_t i : idx)
+            if (i < status_.size()) status_[i] = 3;
+        return r;
+    }
+    // Drops the removed keys (jjs_keyset_compact): the set becomes the set of the survivors in their order, in a new allocation.
+    // EVERY INDEX CHANGES: returns the map, map[i] the new index of old index i, 0xFFFFFFFF for a removed one; quiescing the
+    // callers that still hold old indices is the caller's business.  key_status() follows.
+    std::vector<uint32_t> compact() {
+        std::vector<uint32_t> map(status_.size());
+        size_t n_new = 0;
+        int rc = jjs_keyset_compact(handle_, map.data(), map.size(), &n_new);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_compact");
+        std::vector<uint8_t> kept(n_new);
+        for (size_t i = 0; i < map.size(); ++i)
+            if (map[i] != 0xFFFFFFFFu) kept[map[i]] = status_[i];
+        status_.swap(kept);
+        return map;
+    }
+    std::array<uint64_t, JJS_KEYSET_REMOVAL> removal() const {
+        std::array<uint64_t, JJS_KEYSET_REMOVAL> out{};
+        int rc = jjs_keyset_removal(handle_, out.data());
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_keyset_removal");
+        return out;
+    }
     // one verdict for the batch (jjs_keyset_verify_all): true when every item verifies; `status` (nullable, n bytes) holds
     // the statuses of verify() when the verdict is false and is all zero otherwise
     bool verify_all(int format, const uint32_t* key_idx, const uint8_t* s0, const uint8_t* s1, const uint8_t* s2, const uint8_t* m, size_t n,

@@ -78,6 +78,9 @@ SIGNATURES = {
     "jjs_keyset_add": [ctypes.c_uint64, _I, _P, _P, _Z, _I, _P, _P, _P],
     "jjs_keyset_reserve": [ctypes.c_uint64, _Z],
     "jjs_keyset_growth": [ctypes.c_uint64, _P],
+    "jjs_keyset_remove": [ctypes.c_uint64, _P, _Z, _P, _P],
+    "jjs_keyset_compact": [ctypes.c_uint64, _P, _Z, _P],
+    "jjs_keyset_removal": [ctypes.c_uint64, _P],
     "jjs_keys_check_dev": [_I, _I, _P, _P, _Z, _P, _P, _P, _P, _P],
     "jjs_keys_check": [_I, _I, _P, _P, _Z, _P, _P, _P, _P],
     "jjs_signatures_check_dev": [_I, _I, _P, _P, _P, _Z, _P, _P, _P, _P, _P, _P],

@@ -1433,6 +1433,56 @@ class KeySet:
         _ffi.check(self._lib.jjs_keyset_growth(self.handle, out), "jjs_keyset_growth")
         return dict(zip(self.GROWTH_NAMES, (int(v) for v in out)))
 
+    # ---- removing keys, and compacting the set (include/jjs_gpu.h "removing keys from a live key set") ---------
+    REMOVAL_NAMES = ("removed_keys", "live_keys", "remove_calls", "compact_calls")
+    WAS_REMOVED, NOT_IN_RANGE = 8, 0xFF
+
+    @property
+    def removed(self) -> np.ndarray:
+        """Boolean mask over the indices: removed, and not yet dropped by `compact`."""
+        mask = getattr(self, "_removed", None)
+        if mask is None or len(mask) != self.n_keys:
+            grown = np.zeros(self.n_keys, bool)
+            if mask is not None:
+                grown[:min(len(mask), self.n_keys)] = mask[:self.n_keys]
+            self._removed = mask = grown
+        return mask
+
+    def remove(self, idx):
+        """Remove the keys at `idx` (uint32 indices; numpy, blocking), in place: no index moves, a removed index verifies
+        nothing (status 3) and its key is found nowhere.  Returns (result, n_removed): per index the key's status before the
+        call (0, 1, 3), `KeySet.WAS_REMOVED` or `KeySet.NOT_IN_RANGE`; and the distinct indices this call removed.
+        `key_status` becomes 3 at removed indices."""
+        if self.handle == 0:
+            raise _ffi.JjsError("the key set is closed")
+        idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), np.uint32)
+        result, n_removed = np.empty(len(idx), np.uint8), ctypes.c_size_t(0)
+        _ffi.check(self._lib.jjs_keyset_remove(self.handle, idx.ctypes.data_as(ctypes.c_void_p), len(idx),
+                                                result.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_removed)), "jjs_keyset_remove")
+        gone = idx[idx < self.n_keys]
+        mask = self.removed
+        mask[gone] = True
+        self.key_status[gone] = 3
+        return result, n_removed.value
+
+    def compact(self) -> np.ndarray:
+        """Drop the removed keys: the set becomes `Engine.keyset` of the survivors in their order, in a new allocation (`Engine.trim`
+        frees the old one).  EVERY INDEX CHANGES: returns the map, `map[i]` the new index of old index i, `KeySet.MISS` for a
+        removed one.  `n_keys`, `key_status` and `removed` follow."""
+        if self.handle == 0:
+            raise _ffi.JjsError("the key set is closed")
+        m, n_new = np.empty(self.n_keys, np.uint32), ctypes.c_size_t(0)
+        _ffi.check(self._lib.jjs_keyset_compact(self.handle, m.ctypes.data_as(ctypes.c_void_p), len(m), ctypes.byref(n_new)), "jjs_keyset_compact")
+        keep = m != self.MISS
+        self.key_status, self.n_keys = np.ascontiguousarray(self.key_status[keep]), n_new.value
+        self._removed = np.zeros(self.n_keys, bool)
+        return m
+
+    def removal(self) -> dict:
+        out = (ctypes.c_uint64 * len(self.REMOVAL_NAMES))()
+        _ffi.check(self._lib.jjs_keyset_removal(self.handle, out), "jjs_keyset_removal")
+        return dict(zip(self.REMOVAL_NAMES, (int(v) for v in out)))
+
     def close(self) -> None:
         if self.handle:
             h, self.handle = self.handle, 0

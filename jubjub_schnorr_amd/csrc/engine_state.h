@@ -425,7 +425,8 @@ void free_retired(device_state& d) {      // the caller has made sure that the d
 }
 // Registered objects: key sets (keyset.h; jjs_keyset_*) and multisig signer groups (msig_group.h; jjs_msig_group_*).  An object
 // has one copy per driven device and is immutable once built -- but for a key set that grows (keyset_add_calls.h), which changes
-// nothing a queued launch reads and publishes its new size and pointers under the engine's mutex.  Handles are (generation << 32) | (registry index + 1): a
+// nothing a queued launch reads and publishes its new size and pointers under the engine's mutex, and one that keys are removed
+// from (keyset_remove_calls.h: what a queued launch may then read, and why each outcome is one the contract allows).  Handles are (generation << 32) | (registry index + 1): a
 // destroyed object's index may be reused, its generation never is, so a stale handle finds nothing (JJS_ERR_ARG) and never
 // reaches freed memory -- and the generation counter is ONE for every kind, so a handle of one kind is no handle of another.
 // A registry is only read or changed under the engine's mutex; a destroyed object's device memory is retired (retire()), so
@@ -514,8 +515,11 @@ struct keyset_entry : registered<keyset_copy> {
     uint64_t small_calls = 0, large_calls = 0;
     uint64_t lookup_seed = 0;              // of the lookup table's hash: one per set, the same on every device
     uint32_t capacity = 0;                 // keys every copy holds room for (n_keys until the set grows)
-    bool growing = false;                  // a jjs_keyset_add / jjs_keyset_reserve is extending the copies outside the mutex: the next one waits
+    bool growing = false;                  // a jjs_keyset_add / _reserve / _remove / _compact is changing the copies outside the mutex: the next one waits
     uint64_t growth[JJS_KEYSET_GROWTH] = {};   // jjs_keyset_growth ([JJS_KEYSET_CAPACITY] is `capacity`)
+    uint32_t removed = 0;                  // indices that jjs_keyset_remove has removed and no compact has dropped (keyset_remove_calls.h)
+    uint64_t remove_calls = 0, compact_calls = 0;
+    bool removed_from = false;             // a jjs_keyset_remove has been let in: by-key calls take keyset_miss_removed_kernel from here on
 };
 struct msig_group_copy : device_copy {
     uint8_t* agg_pk = nullptr;             // 64 B affine
@@ -536,8 +540,9 @@ registry<msig_group_entry>& g_msig_groups = *new registry<msig_group_entry>;
 // host-buffer calls against a key set, the verdict algorithm's host route): jjs_shutdown waits for them before it frees a
 // device.  Counted in under L.mu ...
 uint32_t g_blocking_calls = 0;
-// ... and those among them that write into a registered set's copies (jjs_keyset_add, jjs_keyset_reserve): jjs_trim waits for
-// them, because a set destroyed under such a call is retired memory the call may still be writing.
+// ... and those among them that write into a registered set's copies (jjs_keyset_add, jjs_keyset_reserve, jjs_keyset_remove; a
+// jjs_keyset_compact reads them): jjs_trim waits for them, because a set destroyed under such a call is retired memory the call
+// may still be writing or reading.
 uint32_t g_keyset_grows = 0;
 struct blocking_call_leave {               // ... and out here, on every path
     ~blocking_call_leave() {

@@ -66,6 +66,7 @@
 #include "keyset.h"
 #include "keyset_lookup.h"
 #include "keyset_add.h"
+#include "keyset_remove.h"
 #include "sign_core.h"
 #include "sign_vargen.h"
 #include "sign_fixed.h"
@@ -87,6 +88,7 @@ namespace {
 #include "verdict_kernels.h"
 #include "keyset_verdict_kernels.h"
 #include "keyset_add_kernels.h"
+#include "keyset_remove_kernels.h"
 #include "device_owners.h"
 #include "engine_state.h"
 #include "verify_job.h"
@@ -536,6 +538,7 @@ static int resident_call(const call_shape& S, const void* const* d, size_t n, vo
 #include "host_lanes.h"
 #include "keyset_calls.h"
 #include "keyset_add_calls.h"
+#include "keyset_remove_calls.h"
 #include "points_check_calls.h"
 
 // a host-buffer call: blocking

@@ -293,8 +293,13 @@ static int keyset_launch(keyset_entry& k, const keyset_copy& c, int format, cons
         F.X.key_idx = sl->found;
     }
     const auto finish = [&]() -> int {
-        if (B) hipLaunchKernelGGL(keyset_miss_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const uint32_t*)sl->found.get(),
-                                  (uint64_t)n, (uint8_t*)status, (unsigned long long*)tally);
+        if (B && !k.removed_from)
+            hipLaunchKernelGGL(keyset_miss_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const uint32_t*)sl->found.get(),
+                               (uint64_t)n, (uint8_t*)status, (unsigned long long*)tally);
+        else if (B)         // a set that has been removed from (keyset_remove.h): a key removed under the call is a miss, never status 3
+            hipLaunchKernelGGL(keyset_miss_removed_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s,
+                               (const uint32_t*)sl->found.get(), (uint64_t)n, (uint8_t*)status, (unsigned long long*)tally, k.n_keys,
+                               (const uint8_t*)c.flags[0]);
         HIP_TRY(hipGetLastError());
         return end_shared(s);
     };
