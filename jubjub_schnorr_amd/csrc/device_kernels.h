@@ -342,14 +342,18 @@ __global__ __launch_bounds__(BLOCK) void key_scatter_kernel(key_params K) {
         if (active) K.order[K.keep_order ? (uint32_t)item : slot] = (uint32_t)item;
     }
 }
-__global__ __launch_bounds__(BLOCK, 2) void key_verify_kernel(verify_params P, key_params K) {
+// Three waves per SIMD (168 registers): the recoded challenge and u of the lane's item lie in LDS, [word][lane], while the
+// additions run (kt_finish_item_lanes).  No barrier: a lane reads only its own column, and the lanes of a block do not leave
+// the loop together.
+__global__ __launch_bounds__(BLOCK, 3) void key_verify_kernel(verify_params P, key_params K) {
     if (!keyed_mode(P)) return;
+    __shared__ uint32_t scalars[16][BLOCK];
     const uint64_t total = (uint64_t)gridDim.x * BLOCK;
     for (uint64_t base = 0; base < P.n; base += total) {
         const uint64_t idx = base + (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
         const bool active = idx < P.n;
         const uint64_t item = K.order[active ? idx : P.n - 1];
-        publish_status(P, item, active, kt_finish_item(P, K, item, load_prep(P.prep, P.n, item)));
+        publish_status(P, item, active, kt_finish_item_lanes<BLOCK>(P, K, item, load_prep(P.prep, P.n, item), active, &scalars[0][threadIdx.x]));
     }
 }
 

@@ -442,20 +442,54 @@ JJS_HD void kt_load_affine(const uint32_t* src, fe_t& ypx, fe_t& ymx, fe_t& t2d)
 #pragma unroll
     for (int i = 0; i < 9; ++i) { ypx.l[i] = w[i]; ymx.l[i] = w[9 + i]; t2d.l[i] = w[27 + i]; }
 }
-// acc + (digit `pos` of the recoded scalar) * base_pos; pos and w are wave-uniform, the digit is per lane
-JJS_HD ext_pt kt_add_digit(const ext_pt& acc, const uint32_t* tab, const words8& sc, int pos, int w) {
+// Signed digit `pos` of the recoded scalar sc (words_in_regs, words_in_lanes: verify_core.h), |digit| <= 2^(w-1) = the last
+// entry of a table: the top position is unsigned, and what an out-of-range (malformed) scalar leaves there is clamped to
+// the last entry.  pos and w are wave-uniform.
+struct kt_signed_digit {       // neg ? -idx : idx
+    uint32_t idx;
+    bool neg;
+};
+template <class WORDS>
+JJS_HD kt_signed_digit kt_digit(const WORDS& sc, int pos, int w) {
     const int bit = w * pos, wi = bit >> 5, sh = bit & 31;
-    uint32_t v = word_at(sc, wi) >> sh;
-    if (sh + w > 32) v |= word_at(sc, wi + 1 > 7 ? 7 : wi + 1) << (32 - sh);
+    const uint32_t lo = sc.word(wi);
+    uint32_t v = lo >> sh;
+    if (sh + w > 32) v |= sc.word(wi + 1 > 7 ? 7 : wi + 1) << (32 - sh);
     const uint32_t raw = v & ((1u << w) - 1u);
     const bool top = pos == kt_positions(w) - 1;
-    const int d = top ? (int)(word_at(sc, wi) >> sh) : (int)raw - (1 << (w - 1));
+    const int d = top ? (int)(lo >> sh) : (int)raw - (1 << (w - 1));
     const bool neg = d < 0;
     uint32_t idx = (uint32_t)(neg ? -d : d);
     idx = idx >= (uint32_t)kt_entries(w) ? (uint32_t)kt_entries(w) - 1u : idx;     // out-of-range (malformed) scalars only
+    return kt_signed_digit{idx, neg};
+}
+// acc + d * base for a digit d and the table of the base
+JJS_HD ext_pt kt_add_entry(const ext_pt& acc, const uint32_t* tab, const kt_signed_digit& d) {
     fe_t ypx, ymx, t2d;
-    kt_load_affine(tab + idx * ENTRY_WORDS, ypx, ymx, t2d);
-    return ext_add_affine_niels_signed(acc, ypx, ymx, t2d, neg, true);
+    kt_load_affine(tab + d.idx * ENTRY_WORDS, ypx, ymx, t2d);
+    return ext_add_affine_niels_signed(acc, ypx, ymx, t2d, d.neg, true);
+}
+// d * base as a point, T valid: what kt_add_entry(ext_identity(), tab, d) is, in three products instead of seven.  An entry
+// holds (v+u, v-u) of the affine point: (X : Y : Z : T) = (4u : 4v : 4 : 4uv), the product being (2u)(2v); the opposite point
+// swaps the two sums as it does in the addition; entry 0 is (1, 1), which gives (0 : 4 : 4 : 0).  The products by one only
+// bring the two values below 2q.
+JJS_HD ext_pt kt_first_entry(const uint32_t* tab, const kt_signed_digit& d) {
+    fe_t ypx, ymx, t2d;
+    kt_load_affine(tab + d.idx * ENTRY_WORDS, ypx, ymx, t2d);
+    const fe_t s_ypx = fq_select(d.neg, ymx, ypx), s_ymx = fq_select(d.neg, ypx, ymx);
+    const fe_n u2 = fq_mul_hot(fq_norm(fq_sub(s_ypx, s_ymx)), fq_one());
+    const fe_n v2 = fq_mul_hot(fq_norm(fq_add(s_ypx, s_ymx)), fq_one());
+    const fe_n two = fq_reduce(fq_norm(fq_dbl(fe_n_one())));
+    ext_pt p;
+    p.x = fq_reduce(fq_norm(fq_dbl(u2)));
+    p.y = fq_reduce(fq_norm(fq_dbl(v2)));
+    p.z = fq_reduce(fq_norm(fq_dbl(two)));
+    p.t = fq_mul_hot(u2, v2);
+    return p;
+}
+// acc + (digit `pos` of the recoded scalar) * base_pos; pos and w are wave-uniform, the digit is per lane
+JJS_HD ext_pt kt_add_digit(const ext_pt& acc, const uint32_t* tab, const words8& sc, int pos, int w) {
+    return kt_add_entry(acc, tab, kt_digit(words_in_regs{sc}, pos, w));
 }
 // acc + s * P for the key `id` of column C, s < 2^252: one addition per position, no doubling.  T of the result is valid.
 JJS_HD ext_pt kt_add_scalar(ext_pt acc, const key_column& C, uint32_t id, const words8& s, int w) {
@@ -519,5 +553,75 @@ JJS_HD uint32_t kt_finish_item(const verify_params& P, const key_params& K, uint
     // the equations hold: every R is a sum of torsion-free points; they fail: R's own subgroup test decides
     return eq_ok ? ST_OK : ST_PENDING_EQ_FAILED;
 }
+
+#if defined(__HIPCC__)
+// kt_finish_item for key_verify_kernel: the same verdicts, with the registers of three waves per SIMD.
+//   digits    the recoded challenge goes once per item, and u once per equation -- as it is for the comb, recoded for a
+//             per-item generator --, into the lane's column of a [word][lane] array in LDS (`lane`: 16 words, STRIDE apart),
+//             and every position reads its digit from there (kt_digit / comb_digit over words_in_lanes): neither scalar holds
+//             registers while the additions run, and no select chain picks a word.  A lane reads only what it wrote, so there
+//             is no barrier.  u is loaded for u < r at the top and again behind the c * PK loop: it is not live across it.
+//             The per-item generator reads its digits from LDS too: with the register form (kt_add_scalar) beside the two
+//             other loops the kernel needs 169 registers and spills at three waves.
+//   no sums   an equation none of whose active lanes has valid keys in every column is skipped by the whole wave: the
+//             verdict of such an item never reads the sum.  In a mixed wave the lanes of an invalid key -- its tables were
+//             never built -- read the tables of a valid key of their wave instead.
+//   first     the sum starts as the top position's entry (kt_first_entry), not as the identity plus that entry.
+__device__ __forceinline__ uint32_t kt_wave_pool(const key_column& C, uint32_t id, bool ok) {
+    const unsigned long long have = __ballot(ok);
+    const uint32_t pi = kt_pool(C, id);
+    const uint32_t lent = (uint32_t)__shfl((int)pi, have ? __ffsll((long long)have) - 1 : 0);
+    return ok ? pi : lent;
+}
+template <int STRIDE>
+__device__ __forceinline__ uint32_t kt_finish_item_lanes(const verify_params& P, const key_params& K, uint64_t item, const prep_record& r,
+                                                         bool active, uint32_t* lane) {
+    const int w = (int)*P.key_flag;                  // the window width this batch's tables were built with
+    const words_in_lanes<STRIDE> sc{lane}, su{lane + 8 * STRIDE};
+    // u < r is checked here: the head launch of prepare_kernel, which made r, does not read u (verify_core.h prep_phase)
+    const bool u_ok = words_lt(load_words(P.u, item), JJS_FR_WORDS);
+    sc.put(kt_recode(r.c, w));
+    bool keys_valid = true, keys_malformed = false, eq_ok = true;
+    for (uint32_t e = 0; e < P.n_eq; ++e) {
+        const eq_desc& E = P.eq[e];
+        const key_column C = kt_col(K, E.pk_col), G = kt_col(K, E.comb ? E.pk_col : E.gen_col);
+        const uint32_t id = C.keyid[item], f = C.key_flags[id];
+        const bool pk_ok = (f & KT_KEY_VALID) != 0;
+        keys_malformed = keys_malformed || (f & KT_KEY_MALFORMED) != 0;
+        uint32_t gid = 0;
+        bool gen_ok = true;
+        if (!E.comb) {
+            gid = G.keyid[item];
+            const uint32_t gf = G.key_flags[gid];
+            gen_ok = (gf & KT_KEY_VALID) != 0;
+            keys_malformed = keys_malformed || (gf & KT_KEY_MALFORMED) != 0;
+        }
+        keys_valid = keys_valid && pk_ok && gen_ok;
+        if (!__ballot(active && pk_ok && gen_ok)) continue;                   // wave-uniform
+        const uint32_t pi = kt_wave_pool(C, id, pk_ok);
+        int pos = kt_challenge_positions(w) - 1;
+        ext_pt acc = kt_first_entry(kt_table(C, pi, (uint32_t)pos, w), kt_digit(sc, pos, w));
+        while (--pos >= 0) acc = kt_add_entry(acc, kt_table(C, pi, (uint32_t)pos, w), kt_digit(sc, pos, w));     // c * PK
+        const words8 u = load_words(P.u, item);
+        su.put(E.comb ? u : kt_recode(u, w));
+        __asm__ volatile("" ::: "memory");           // the digits are READ from LDS: nothing is forwarded from the registers of u
+        if (E.comb) {
+            // T of the last addition too, which nothing reads: a loop whose last round differs is peeled, and the registers
+            // of the peeled round beside the comparison with R are what the third wave does not have
+            acc = add_comb_range_from(acc, E.comb, su, 0, COMB_WINDOWS, true, JJS_SKIP(P, 16u));                // + u * G (G')
+        } else {
+            const uint32_t gi = kt_wave_pool(G, gid, gen_ok);
+            for (pos = kt_positions(w) - 1; pos >= 0; --pos)
+                acc = kt_add_entry(acc, kt_table(G, gi, (uint32_t)pos, w), kt_digit(su, pos, w));               // + u * Gen
+        }
+        const fe_n ru = load_fq(E.r, item), rv = load_fq(E.r, item, 32);
+        eq_ok = ext_eq_affine(acc, ru, rv) && eq_ok;
+    }
+    if (r.malformed || keys_malformed || !u_ok) return ST_MALFORMED;
+    if (!r.valid || !keys_valid) return ST_INVALID_POINT;
+    if (JJS_SKIP(P, 1u)) return eq_ok ? ST_OK : ST_INVALID_SIGNATURE;        // profiling only: no resolve pass
+    return eq_ok ? ST_OK : ST_PENDING_EQ_FAILED;
+}
+#endif
 
 }  // namespace jjs

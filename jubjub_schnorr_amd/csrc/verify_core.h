@@ -176,6 +176,22 @@ JJS_HD uint32_t word_at(const words8& s, int j) {
     for (int k = 1; k < 8; ++k) r = (j == k) ? s.w[k] : r;
     return r;
 }
+// Where a digit extraction takes the words of a scalar from: the registers of the lane (word_at), or memory the lane wrote
+// them to, word j at p[j * STRIDE] (key_verify_kernel: the lane's column of a [word][lane] array in LDS, so that the scalar
+// holds no registers while the additions run).  The extraction itself is one function of the source (comb_digit, kt_digit).
+struct words_in_regs {
+    const words8& s;
+    JJS_HD uint32_t word(int j) const { return word_at(s, j); }
+};
+template <int STRIDE>
+struct words_in_lanes {
+    uint32_t* p;
+    JJS_HD uint32_t word(int j) const { return p[j * STRIDE]; }
+    JJS_HD void put(const words8& s) const {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) p[j * STRIDE] = s.w[j];
+    }
+};
 JJS_HD uint32_t nibble(const words8& s, int i) { return (word_at(s, i >> 3) >> ((i & 7) * 4)) & 15u; }
 // acc + (digit `w` of the recoded scalar) * P; `top` is the index of the unsigned top digit; `flip` adds
 // the opposite point (used for -b*R)
@@ -615,12 +631,18 @@ JJS_HD bool point_on_curve_not_identity(const fe_n& u, const fe_n& v) {
     return affine_on_curve(u, v) && !affine_is_identity(u, v);
 }
 
+// digit i of the comb: COMB_BITS bits of the scalar, unsigned
+template <class WORDS>
+JJS_HD uint32_t comb_digit(const WORDS& k, int i) {
+    constexpr int per_word = 32 / COMB_BITS;
+    return (k.word(i / per_word) >> ((i % per_word) * COMB_BITS)) & (uint32_t)(COMB_ENTRIES - 1);
+}
 // digit positions [lo, hi) of the comb; T of the result is valid only when t_last is set
-JJS_HD ext_pt add_comb_range(ext_pt acc, const uint32_t* comb, const words8& k, int lo, int hi, bool t_last,
-                             bool one_entry = false) {
+template <class WORDS>
+JJS_HD ext_pt add_comb_range_from(ext_pt acc, const uint32_t* comb, const WORDS& k, int lo, int hi, bool t_last,
+                                  bool one_entry = false) {
     for (int i = lo; i < hi; ++i) {
-        constexpr int per_word = 32 / COMB_BITS;
-        uint32_t digit = (word_at(k, i / per_word) >> ((i % per_word) * COMB_BITS)) & (uint32_t)(COMB_ENTRIES - 1);
+        uint32_t digit = comb_digit(k, i);
         digit = one_entry ? (digit & 255u) : digit;  // profiling ablation only: 256 entries per row, cache-resident
         const u32x4* p = reinterpret_cast<const u32x4*>(comb + ((size_t)i * COMB_ENTRIES + digit) * COMB_ENTRY_WORDS);
         uint32_t w[COMB_ENTRY_WORDS];
@@ -632,6 +654,10 @@ JJS_HD ext_pt add_comb_range(ext_pt acc, const uint32_t* comb, const words8& k, 
         acc = ext_add_affine_niels(acc, ypx, ymx, t2d, t_last || i != hi - 1);
     }
     return acc;
+}
+JJS_HD ext_pt add_comb_range(ext_pt acc, const uint32_t* comb, const words8& k, int lo, int hi, bool t_last,
+                             bool one_entry = false) {
+    return add_comb_range_from(acc, comb, words_in_regs{k}, lo, hi, t_last, one_entry);
 }
 JJS_HD ext_pt add_comb(ext_pt acc, const uint32_t* comb, const words8& k, bool one_entry = false) {
     return add_comb_range(acc, comb, k, 0, COMB_WINDOWS, false, one_entry);
