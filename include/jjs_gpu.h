@@ -849,6 +849,82 @@ int jjs_multisig_sign(int format, const uint8_t* PK, const uint8_t* R, const uin
                       const uint32_t* signer_row, const uint8_t* sk, const uint8_t* r, const uint8_t* s, size_t n_signing,
                       uint8_t* z_out, uint8_t* sign_status);
 
+/* ---- multisignature: verify_share on its own (csrc/msig_share.h; reference src/multisig.rs verify_share :284-309,
+ * verify_share_with_coefficients :366-387) ----
+ * verify_share(share, participant_index, pk_vec, R_vec, S_vec, msg) for single shares: the check a coordinator makes as shares
+ * arrive, before anyone may combine.  A call takes B transcripts exactly as the combine call of the same route takes them
+ * (jjs_multisig_combine_dev: PK, R, S, m, offsets_host; jjs_msig_group_combine_dev: R, S, m for B transcripts of the group's n
+ * participants; jjs_multisig_combine_keyset_dev: key_idx, R, S, m, offsets_host), with that call's offsets rules and limits,
+ * and Q = n_shares queries: share_transcript[q] (uint32) the transcript t the share belongs to, share_slot[q] (uint32) the
+ * reference's participant_index inside that transcript, z[q] (32 bytes) the share.  Several queries on one transcript or on
+ * one slot (with equal or different z), queries in any order and transcripts without a query are all legal; Q may exceed the
+ * number of rows.  `format` describes the point columns and is JJS_FORMAT_AFFINE, _EXT or _WIRE; extended and wire points go
+ * through the combine calls' ingest in poison mode (an unusable point becomes 64 bytes of 0xFF).
+ * share_status[q] (required, Q bytes) -- the first rule that matches:
+ *   3  share_transcript[q] >= B
+ *   3  z[q] >= the group order
+ *   3  an encoding of transcript t is unusable: a coordinate of any PK, R or S >= q, or m[t] >= q (affine); what poison mode
+ *      turns into 0xFF rows (extended, wire); an index outside the set, or a key the set refused or has removed (key set).
+ *      Every query of that transcript gets 3: jjs_multisig_sign's rule
+ *   5  (JJS_STATUS_INVALID_TRANSCRIPT) transcript t has no participants, or share_slot[q] >= its number of participants
+ *      (src/multisig.rs:292-298)
+ *   4  z * G + (c * d_j mod r) * PK_j != R_j + a * S_j, with c * d_j reduced before the point is multiplied (csrc/msig_group.h)
+ *   0  otherwise
+ * A query whose status is 3 or 5 addresses nothing through its indices.
+ * sig_R (nullable, B x 64) receives the aggregate commitment RSa of EVERY transcript, named by a query or not: byte for byte
+ * what the combine call returns as R for that transcript with valid shares, and 64 zero bytes for a transcript to which the
+ * third rule or the rule of status 5 applies.  A coordinate set < q that names no point of the curve has no defined outputs.
+ * n_transcripts == 0 returns 0 and writes nothing; so does n_shares == 0 with sig_R == NULL; with sig_R given a call without
+ * queries still fills it.  -4 before jjs_init; -1 for a bad format, a NULL or misaligned pointer, an unknown handle or
+ * unacceptable offsets.  The _dev forms take device pointers, the columns 16-byte aligned, the two query index columns (and
+ * key_idx) 4-byte aligned, share_status unaligned, and are asynchronous on `stream` on the calling thread's device.  The
+ * forms without _dev are the same from host buffers, blocking, on the route of jjs_multisig_combine: no alignment is asked,
+ * one such call runs at a time per device.  Group calls count in JJS_MSIG_GROUP_CALLS.
+ * Scratch is the grow-only multisignature scratch, enlarged by one extended point per query (144 bytes), one flag word per
+ * transcript and the two columns a call may have no output for (132 bytes per transcript); no call allocates per call.
+ * What a call runs.  Per transcript of n participants: the front of the route's combine call (inline: the map, n hashes and
+ * n products d_i * PK_i, pk_agg and a; group: the hash of a alone; key set: the gather, n hashes and n table walks, pk_agg and
+ * a), n range tests, then 2 n point additions, ONE variable-base product (RSa = sum R_i + a * sum S_i -- the same group element
+ * as the combine call's sum of n products, on the whole curve: DESIGN.md 6.6) and the hash of c.  Per query: one product
+ * a * S_j, and the equation -- a comb and one product by PK_j (inline) or one walk over the stored tables (group, key set).  The
+ * combine route to the same answer runs n products a * S_i, n products by PK_i and n combs per transcript, and clears sig_R
+ * when the filler shares fail.
+ * Rates (profiles/r21_msig_share.jsonl, the record of tools/msig_share_rate.py: one MI355X, resident inputs made on the device, one
+ * query per transcript against the route's combine call with the query's z at its row and zero filler, alternating, 7 rounds,
+ * medians), time of the new call / time of the combine route.  Where the device is full the saved work shows:
+ * B = 4 096 transcripts of 64 and 256 participants 0.86 and 0.94 inline, 0.78 and 0.70 by group (10.9 against 14.0 ms, 37.9
+ * against 54.2 ms), 0.90 and 0.96 by key set.  At B = 64 (8, 64, 256 participants) and at B = 4 096 of 8 it is 1.01-1.06 on
+ * every route: no faster, inside the 10 % spread between boxes and runs.  At B = 1 it is SLOWER than that margin on seven of
+ * twelve shapes: 8 participants 1.08 / 1.15 / 1.23 (inline / group / key set: 5.9 against 5.5 ms, 3.4 against 3.0, 4.7 against
+ * 3.8), 64 participants 0.96 / 1.13 / 1.12, 256 participants 1.15 / 1.01 / 1.11, one transcript of 1 000 participants 1.08 /
+ * 0.99 / 1.16 (223 against 206 ms inline).  A call with one transcript is as long as its longest lane: the products and combs the
+ * new call leaves out ran in lanes that were idle anyway, while its sums lane does 2 n additions, two inversions and a product
+ * one after the other where the combine call spreads the products over n lanes. */
+int jjs_multisig_verify_share_dev(int format, const void* PK, const void* R, const void* S, const void* m,
+                                  const uint32_t* offsets_host, size_t n_transcripts,
+                                  const void* share_transcript, const void* share_slot, const void* z, size_t n_shares,
+                                  void* share_status, void* sig_R, void* stream);
+int jjs_multisig_verify_share(int format, const uint8_t* PK, const uint8_t* R, const uint8_t* S, const uint8_t* m,
+                              const uint32_t* offsets, size_t n_transcripts,
+                              const uint32_t* share_transcript, const uint32_t* share_slot, const uint8_t* z, size_t n_shares,
+                              uint8_t* share_status, uint8_t* sig_R);
+int jjs_msig_group_verify_share_dev(jjs_msig_group g, int format, const void* R, const void* S, const void* m,
+                                    size_t n_transcripts,
+                                    const void* share_transcript, const void* share_slot, const void* z, size_t n_shares,
+                                    void* share_status, void* sig_R, void* stream);
+int jjs_msig_group_verify_share(jjs_msig_group g, int format, const uint8_t* R, const uint8_t* S, const uint8_t* m,
+                                size_t n_transcripts,
+                                const uint32_t* share_transcript, const uint32_t* share_slot, const uint8_t* z, size_t n_shares,
+                                uint8_t* share_status, uint8_t* sig_R);
+int jjs_multisig_verify_share_keyset_dev(jjs_keyset ks, int format, const void* key_idx, const void* R, const void* S,
+                                         const void* m, const uint32_t* offsets_host, size_t n_transcripts,
+                                         const void* share_transcript, const void* share_slot, const void* z, size_t n_shares,
+                                         void* share_status, void* sig_R, void* stream);
+int jjs_multisig_verify_share_keyset(jjs_keyset ks, int format, const uint32_t* key_idx, const uint8_t* R, const uint8_t* S,
+                                     const uint8_t* m, const uint32_t* offsets, size_t n_transcripts,
+                                     const uint32_t* share_transcript, const uint32_t* share_slot, const uint8_t* z,
+                                     size_t n_shares, uint8_t* share_status, uint8_t* sig_R);
+
 /* ---- transcript parity (debug export): c_out = n x 32 bytes, the 250-bit challenge per item ---- */
 int jjs_challenge_single_dev(const void* R, const void* PK, const void* m, size_t n, void* c_out, void* stream);
 int jjs_challenge_double_dev(const void* R, const void* R_prime, const void* PK, const void* PK_prime, const void* m,

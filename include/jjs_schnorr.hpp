@@ -596,7 +596,7 @@ inline bool verify_all_vargen(const std::vector<PublicKeyVarGen::Item>& items, s
 
 // Registered key sets (include/jjs_gpu.h jjs_keyset_*): keys validated and tabled once on the device, then verified against by
 // index.  Move-only; the destructor destroys the set (calls already queued on a stream still complete).
-namespace multisig { struct CombineResult; }
+namespace multisig { struct CombineResult; struct CombineError; }
 class KeySet {
   public:
     // raw form: scheme JJS_SCHEME_*, key format JJS_FORMAT_* and the key columns of jjs_keyset_create
@@ -761,6 +761,22 @@ class KeySet {
                                              sig_u, sig_R);
         if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_combine_keyset");
     }
+    // raw form of verify_share against the set (jjs_multisig_verify_share_keyset): host buffers, blocking; the transcripts of
+    // multisig_combine, n_shares queries (share_transcript, share_slot: uint32; z: 32 bytes each), share_status n_shares bytes,
+    // sig_R nullable (n_transcripts x 64); format JJS_FORMAT_AFFINE, _EXT or _WIRE (R, S)
+    void multisig_verify_share(int format, const uint32_t* key_idx, const uint8_t* R, const uint8_t* S, const uint8_t* m, const uint32_t* offsets,
+                               size_t n_transcripts, const uint32_t* share_transcript, const uint32_t* share_slot, const uint8_t* z,
+                               size_t n_shares, uint8_t* share_status, uint8_t* sig_R = nullptr) const {
+        int rc = jjs_multisig_verify_share_keyset(handle_, format, key_idx, R, S, m, offsets, n_transcripts, share_transcript, share_slot, z, n_shares,
+                                                  share_status, sig_R);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_verify_share_keyset");
+    }
+    // verify_share(share, participant_index, ., R_vec, S_vec, msg) of ONE transcript whose signers are keys of this set, named by
+    // index in the committee's order: as multisig::verify_share (defined behind it); a transcript the engine refuses is BytesError
+    inline std::optional<multisig::CombineError> multisig_verify_share(const JubJubScalar& share, size_t participant_index,
+                                                                       const std::vector<uint32_t>& key_idx, const std::vector<ExtendedPoint>& R_vec,
+                                                                       const std::vector<ExtendedPoint>& S_vec, const BlsScalar& msg,
+                                                                       AffinePoint* sig_R = nullptr) const;
     // `combine` of ONE transcript whose signers are keys of this set (scheme single), named by index in the committee's order;
     // R and S as the Rust side holds them.  A transcript that names an index outside the set or a key whose key_status is not 0
     // is refused by the engine: BytesError with the index of its first such row (defined behind multisig::CombineResult).
@@ -1024,6 +1040,102 @@ inline VerifyResult verify(const std::vector<P>& pk_vec, const SignatureBytes& s
     return r;
 }
 
+// ---- verify_share on its own (reference src/multisig.rs:284-309; include/jjs_gpu.h jjs_multisig_verify_share) ----
+// verify_share(share, participant_index, pk_vec, R_vec, S_vec, msg): what a coordinator checks as shares arrive.  Nothing: the
+// share verifies.  InvalidMultisigTranscript (decided here, without a call, as the reference decides it before any arithmetic): an
+// empty transcript, vectors of unequal length, or participant_index beyond them.  InvalidMultisigShare CARRYING participant_index:
+// status 4.  BytesError with the same index: status 3, an encoding the Rust types cannot hold (share >= r, a coordinate >= q,
+// Z = 0, m >= q, bytes that do not decode).  sig_R (nullable) receives the transcript's aggregate commitment, what `combine` returns as R.
+// One transcript per call is no faster than `combine` with filler shares (profiles/r21_msig_share.jsonl; include/jjs_gpu.h): batch
+// the queries (verify_share_batch) where shares of many transcripts are at hand.
+using ShareResult = std::optional<CombineError>;
+namespace share_detail {
+inline ShareResult share_result(uint8_t status, size_t participant_index) {
+    if (status == JJS_STATUS_OK) return std::nullopt;
+    if (status == JJS_STATUS_INVALID_TRANSCRIPT) return CombineError{CombineError::InvalidMultisigTranscript, 0};
+    return CombineError{status == JJS_STATUS_INVALID_SHARE ? CombineError::InvalidMultisigShare : CombineError::BytesError, participant_index};
+}
+template <class P>
+inline ShareResult verify_share(int format, const JubJubScalar& share, size_t participant_index, const std::vector<P>& pk_vec,
+                                const std::vector<P>& R_vec, const std::vector<P>& S_vec, const BlsScalar& msg, AffinePoint* sig_R) {
+    const size_t n = pk_vec.size();
+    if (n == 0 || R_vec.size() != n || S_vec.size() != n || participant_index >= n || n > 0xFFFFFFFFull)
+        return CombineError{CombineError::InvalidMultisigTranscript, 0};
+    const uint32_t offsets[2] = {0, (uint32_t)n}, transcript = 0, slot = (uint32_t)participant_index;
+    uint8_t status = 0;
+    const int rc = jjs_multisig_verify_share(format, pk_vec[0].data(), R_vec[0].data(), S_vec[0].data(), msg.data(), offsets, 1, &transcript, &slot,
+                                             share.data(), 1, &status, sig_R ? sig_R->data() : nullptr);
+    if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_verify_share");
+    return share_result(status, participant_index);
+}
+}  // namespace share_detail
+inline ShareResult verify_share(const JubJubScalar& share, size_t participant_index, const std::vector<ExtendedPoint>& pk_vec,
+                                const std::vector<ExtendedPoint>& R_vec, const std::vector<ExtendedPoint>& S_vec, const BlsScalar& msg,
+                                AffinePoint* sig_R = nullptr) {
+    return share_detail::verify_share(JJS_FORMAT_EXT, share, participant_index, pk_vec, R_vec, S_vec, msg, sig_R);
+}
+// ... from PublicKey::to_bytes keys and JubJubAffine::to_bytes nonce commitments
+template <class P, class = if_point_bytes<P>>
+inline ShareResult verify_share(const JubJubScalar& share, size_t participant_index, const std::vector<P>& pk_vec, const std::vector<P>& R_vec,
+                                const std::vector<P>& S_vec, const BlsScalar& msg, AffinePoint* sig_R = nullptr) {
+    return share_detail::verify_share(JJS_FORMAT_WIRE, share, participant_index, pk_vec, R_vec, S_vec, msg, sig_R);
+}
+// The batch form: many transcripts, many queries in any order, one call (several queries may name one transcript or one slot).
+struct ShareTranscript {
+    std::vector<ExtendedPoint> pk_vec, R_vec, S_vec;
+    BlsScalar message;
+};
+struct ShareQuery {
+    size_t transcript, participant_index;
+    JubJubScalar share;
+};
+// One result per query, as verify_share gives it; a query that names no transcript is InvalidMultisigTranscript as well.  sig_R
+// (nullable) receives one aggregate commitment per transcript, zero for a transcript that is empty, malformed or of unequal vectors.
+inline std::vector<ShareResult> verify_share_batch(const std::vector<ShareTranscript>& transcripts, const std::vector<ShareQuery>& queries,
+                                                   std::vector<AffinePoint>* sig_R = nullptr) {
+    const size_t B = transcripts.size(), Q = queries.size();
+    std::vector<uint32_t> offsets(B + 1, 0);
+    std::vector<bool> usable(B);
+    size_t n = 0;
+    for (size_t t = 0; t < B; ++t) {
+        const ShareTranscript& T = transcripts[t];
+        usable[t] = !T.pk_vec.empty() && T.R_vec.size() == T.pk_vec.size() && T.S_vec.size() == T.pk_vec.size();
+        n += usable[t] ? T.pk_vec.size() : 0;                   // an unusable transcript travels as an empty one
+        if (n > 0xFFFFFFFFull) throw std::invalid_argument("the participant rows of a call are indexed with 32 bits");
+        offsets[t + 1] = (uint32_t)n;
+    }
+    std::vector<ExtendedPoint> pk(n), R(n), S(n);
+    std::vector<Scalar> m(B), z(Q);
+    std::vector<uint32_t> qt(Q), qs(Q);
+    std::vector<uint8_t> status(Q);
+    std::vector<AffinePoint> rsa(B);
+    for (size_t t = 0, at = 0; t < B; ++t) {
+        m[t] = transcripts[t].message;
+        if (!usable[t]) continue;
+        for (size_t i = 0; i < transcripts[t].pk_vec.size(); ++i, ++at) { pk[at] = transcripts[t].pk_vec[i]; R[at] = transcripts[t].R_vec[i]; S[at] = transcripts[t].S_vec[i]; }
+    }
+    std::vector<ShareResult> out(Q);
+    for (size_t q = 0; q < Q; ++q) {
+        const bool named = queries[q].transcript < B && usable[queries[q].transcript] &&
+                           queries[q].participant_index < transcripts[queries[q].transcript].pk_vec.size();
+        qt[q] = named ? (uint32_t)queries[q].transcript : 0u;
+        qs[q] = named ? (uint32_t)queries[q].participant_index : 0xFFFFFFFFu;     // beyond every transcript: status 5 at most
+        z[q] = queries[q].share;
+    }
+    if (B && (Q || sig_R)) {
+        const int rc = jjs_multisig_verify_share(JJS_FORMAT_EXT, n ? pk[0].data() : nullptr, n ? R[0].data() : nullptr, n ? S[0].data() : nullptr,
+                                                 m[0].data(), offsets.data(), B, Q ? qt.data() : nullptr, Q ? qs.data() : nullptr,
+                                                 Q ? z[0].data() : nullptr, Q, Q ? status.data() : nullptr, sig_R ? rsa[0].data() : nullptr);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_multisig_verify_share");
+    }
+    for (size_t q = 0; q < Q; ++q) {
+        const bool named = qs[q] != 0xFFFFFFFFu && B != 0;
+        out[q] = named ? share_detail::share_result(status[q], queries[q].participant_index) : ShareResult(CombineError{CombineError::InvalidMultisigTranscript, 0});
+    }
+    if (sig_R) *sig_R = rsa;
+    return out;
+}
+
 // ---- the signer's half (reference src/multisig.rs sign_round_1 :169-184, sign_round_2 :213-257) ----
 // TEST AND BENCHMARK MATERIAL, as the engine's calls behind it (include/jjs_gpu.h jjs_multisig_sign): NOT constant time, here or
 // on the device -- never with production keys.  Nothing enforces the one-shot MultisigNonce of the reference (:131-141): using
@@ -1179,6 +1291,22 @@ inline multisig::CombineResult KeySet::multisig_combine(const std::vector<uint32
     return CombineResult{Signature{u, R}, std::nullopt};
 }
 
+inline std::optional<multisig::CombineError> KeySet::multisig_verify_share(const JubJubScalar& share, size_t participant_index,
+                                                                           const std::vector<uint32_t>& key_idx,
+                                                                           const std::vector<ExtendedPoint>& R_vec,
+                                                                           const std::vector<ExtendedPoint>& S_vec, const BlsScalar& msg,
+                                                                           AffinePoint* sig_R) const {
+    using namespace multisig;
+    const size_t n = key_idx.size();
+    if (n == 0 || R_vec.size() != n || S_vec.size() != n || participant_index >= n || n > 0xFFFFFFFFull)
+        return CombineError{CombineError::InvalidMultisigTranscript, 0};
+    const uint32_t offsets[2] = {0, (uint32_t)n}, transcript = 0, slot = (uint32_t)participant_index;
+    uint8_t status = 0;
+    multisig_verify_share(JJS_FORMAT_EXT, key_idx.data(), R_vec[0].data(), S_vec[0].data(), msg.data(), offsets, 1, &transcript, &slot, share.data(), 1,
+                          &status, sig_R ? sig_R->data() : nullptr);
+    return share_detail::share_result(status, participant_index);
+}
+
 namespace multisig {
 class SignerGroup {
   public:
@@ -1252,6 +1380,32 @@ class SignerGroup {
                  uint8_t* transcript_status, uint8_t* sig_u, uint8_t* sig_R) const {
         int rc = jjs_msig_group_combine(handle_, format, z, R, S, m, n_transcripts, share_status, transcript_status, sig_u, sig_R);
         if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_combine");
+    }
+    // verify_share against the group, raw forms (jjs_msig_group_verify_share[_dev]): the transcripts of `combine`, n_shares queries
+    // (share_transcript, share_slot: uint32; z: 32 bytes each), share_status n_shares bytes, sig_R nullable (n_transcripts x 64);
+    // format JJS_FORMAT_AFFINE, _EXT or _WIRE (R, S)
+    void verify_share(int format, const uint8_t* R, const uint8_t* S, const uint8_t* m, size_t n_transcripts, const uint32_t* share_transcript,
+                      const uint32_t* share_slot, const uint8_t* z, size_t n_shares, uint8_t* share_status, uint8_t* sig_R = nullptr) const {
+        int rc = jjs_msig_group_verify_share(handle_, format, R, S, m, n_transcripts, share_transcript, share_slot, z, n_shares, share_status, sig_R);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_verify_share");
+    }
+    void verify_share_dev(int format, const void* R, const void* S, const void* m, size_t n_transcripts, const void* share_transcript,
+                          const void* share_slot, const void* z, size_t n_shares, void* share_status, void* sig_R = nullptr,
+                          void* stream = nullptr) const {
+        int rc = jjs_msig_group_verify_share_dev(handle_, format, R, S, m, n_transcripts, share_transcript, share_slot, z, n_shares, share_status,
+                                                 sig_R, stream);
+        if (rc != JJS_OK) throw EngineError(rc, "jjs_msig_group_verify_share_dev");
+    }
+    // verify_share(share, participant_index, ., R_vec, S_vec, msg) of ONE transcript of the group's signers, as multisig::verify_share
+    ShareResult verify_share(const JubJubScalar& share, size_t participant_index, const std::vector<ExtendedPoint>& R_vec,
+                             const std::vector<ExtendedPoint>& S_vec, const BlsScalar& msg, AffinePoint* sig_R = nullptr) const {
+        if (R_vec.size() != participants_ || S_vec.size() != participants_ || participant_index >= participants_)
+            return CombineError{CombineError::InvalidMultisigTranscript, 0};
+        const uint32_t transcript = 0, slot = (uint32_t)participant_index;
+        uint8_t status = 0;
+        verify_share(JJS_FORMAT_EXT, R_vec[0].data(), S_vec[0].data(), msg.data(), 1, &transcript, &slot, share.data(), 1, &status,
+                     sig_R ? sig_R->data() : nullptr);
+        return share_detail::share_result(status, participant_index);
     }
 
   private:

@@ -124,6 +124,13 @@ SIGNATURES = {
     "jjs_multisig_round1_dev": [_P, _P, _Z, _P, _P, _P, _P],
     "jjs_multisig_sign_dev": [_I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _Z, _P, _P, _P],
     "jjs_multisig_sign": [_I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _Z, _P, _P],
+    # verify_share on its own: the transcripts of the route's combine call, then share_transcript, share_slot, z, n_shares, the outputs
+    "jjs_multisig_verify_share_dev": [_I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _Z, _P, _P, _P],
+    "jjs_multisig_verify_share": [_I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _Z, _P, _P],
+    "jjs_msig_group_verify_share_dev": [ctypes.c_uint64, _I, _P, _P, _P, _Z, _P, _P, _P, _Z, _P, _P, _P],
+    "jjs_msig_group_verify_share": [ctypes.c_uint64, _I, _P, _P, _P, _Z, _P, _P, _P, _Z, _P, _P],
+    "jjs_multisig_verify_share_keyset_dev": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _Z, _P, _P, _P],
+    "jjs_multisig_verify_share_keyset": [ctypes.c_uint64, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _Z, _P, _P],
     "jjs_public_keys_vargen_dev": [_I, _P, _P, _Z, _Z, _P, _P, _P, _P],
     "jjs_sign_vargen_pt_dev": [_I, _P, _P, _Z, _P, _P, _Z, _P, _P, _P, _P, _P, _P],
     "jjs_public_keys_vargen": [_I, _P, _P, _Z, _Z, _P, _P, _P],

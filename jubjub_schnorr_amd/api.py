@@ -666,6 +666,65 @@ class Engine:
                                                    self._dev_ptr(s, 32, k), k, o(z), o(status), self._stream()), "jjs_multisig_sign_dev")
         return z, status
 
+    _MSIG_SHARE_WIDTH = {"affine": 64, "ext": 96, "wire": 32}
+
+    def multisig_verify_share(self, PK, R, S, m, offsets, share_transcript, share_slot, z, fmt: str = "affine", want_R: bool = False):
+        """`verify_share` for single shares (reference src/multisig.rs:284-309): the transcripts as `multisig_combine` takes
+        them -- PK / R / S (N, 64), (N, 96) with fmt="ext" or (N, 32) with fmt="wire", m (B, 32), offsets B + 1 ints (host) -- and
+        Q queries: share_transcript (Q,) and share_slot (Q,) uint32 name the transcript and the participant_index inside it, z
+        (Q, 32) is the share.  torch CUDA tensors run asynchronously on the current stream (jjs_multisig_verify_share_dev; the
+        two index columns int32 / uint32 tensors), numpy arrays block (jjs_multisig_verify_share).  Returns share_status (Q,):
+        0 ok, 3 malformed (the transcript index, z, or an encoding of the transcript), 5 no such participant, 4 the share does
+        not verify; with want_R, (share_status, sig_R (B, 64)): the aggregate commitment of every transcript, zero where the
+        transcript is malformed or empty."""
+        offs = np.ascontiguousarray(offsets, dtype=np.uint32)
+        return self._msig_verify_share("jjs_multisig_verify_share", [], PK, None, R, S, m, offs, len(offs) - 1, PK.shape[0],
+                                       share_transcript, share_slot, z, fmt, want_R)
+
+    def _msig_verify_share(self, name, head, keys, idx_keys, R, S, m, offs, B, N, qt, qs, z, fmt, want_R):
+        """The three verify_share calls: `keys` is the PK column (idx_keys None), a key-set's indices (idx_keys True) or None
+        (a signer group, offs None)."""
+        if fmt not in self._MSIG_SHARE_WIDTH:
+            raise ValueError(f"verify_share takes fmt 'affine', 'ext' or 'wire', not {fmt!r}")
+        w, fmt_id = self._MSIG_SHARE_WIDTH[fmt], self._FORMAT_IDS[fmt]
+        Q = z.shape[0]
+        if offs is not None and B and int(offs[-1]) != N:
+            raise ValueError("the columns do not have the rows the offsets ask for")
+        po = [offs.ctypes.data_as(ctypes.c_void_p)] if offs is not None else []
+        if not _is_torch(z):
+            hr, hs, hm, hz = self._host(R, w), self._host(S, w), self._host(m, 32), self._host(z, 32)
+            hk = []
+            if keys is not None:
+                hk = [np.ascontiguousarray(keys, dtype=np.uint32) if idx_keys else self._host(keys, w)]
+            hq = [np.ascontiguousarray(q, dtype=np.uint32) for q in (qt, qs)]
+            if any(x.shape[0] != N for x in (hr, hs, *hk)) or hm.shape[0] != B or any(q.shape != (Q,) for q in hq):
+                raise ValueError("the columns do not have the rows the transcripts and the queries ask for")
+            status = np.zeros(Q, np.uint8)
+            sr = np.zeros((B, 64), np.uint8) if want_R else None
+            p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None  # noqa: E731
+            _ffi.check(getattr(self._lib, name)(*head, fmt_id, *(p(k) for k in hk), p(hr), p(hs), p(hm), *po, B, p(hq[0]), p(hq[1]), p(hz), Q,
+                                                p(status), p(sr)), name)
+            return (status, sr) if want_R else status
+        import torch
+        for q in (qt, qs):
+            if not (_is_torch(q) and q.is_cuda and q.is_contiguous() and q.shape == (Q,)
+                    and q.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+                raise ValueError("expected contiguous 1-d CUDA tensors of int32 / uint32, one entry per query")
+        dev_ = z.device
+        status = torch.empty(max(Q, 1), dtype=torch.uint8, device=dev_)[:Q]
+        sr = torch.empty((max(B, 1), 64), dtype=torch.uint8, device=dev_)[:B] if want_R else None
+        o = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        d = self._dev_ptr
+        dk = []
+        if keys is not None:
+            if idx_keys and not (_is_torch(keys) and keys.is_cuda and keys.is_contiguous() and keys.shape == (N,)
+                                 and keys.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+                raise ValueError("expected a contiguous 1-d CUDA tensor of int32 / uint32 indices, one per participant row")
+            dk = [o(keys) if idx_keys else d(keys, w, N)]
+        _ffi.check(getattr(self._lib, name + "_dev")(*head, fmt_id, *dk, d(R, w, N), d(S, w, N), d(m, 32, B), *po, B, o(qt), o(qs),
+                                                     d(z, 32, Q), Q, o(status), o(sr), self._stream()), name + "_dev")
+        return (status, sr) if want_R else status
+
     # ---- primitives for parity tests ------------------------------------------------------------
     def debug_fq_mul(self, a, b):
         import torch
@@ -1366,6 +1425,18 @@ class KeySet:
         (jjs_multisig_combine_keyset_wire[_dev]); a share with an undecodable point gets status 3."""
         return self._msig_combine(key_idx, z, R_w, S_w, m, offsets, "affine", True)
 
+    def multisig_verify_share(self, key_idx, R, S, m, offsets, share_transcript, share_slot, z, fmt: str = "affine", want_R: bool = False):
+        """`Engine.multisig_verify_share` for committees drawn from this set (scheme "single"): key_idx (N,) uint32 names the
+        key of every participant row instead of a PK column (jjs_multisig_verify_share_keyset[_dev]).  Every query of a
+        transcript naming an index outside the set, or a key the set refused or has removed, gets status 3."""
+        if self.handle == 0:
+            raise _ffi.JjsError("the key set is closed")
+        if not _is_torch(key_idx) and np.asarray(key_idx).dtype.kind not in "iu":
+            raise ValueError("key indices must be integers")
+        offs = np.ascontiguousarray(offsets, dtype=np.uint32)
+        return self._eng._msig_verify_share("jjs_multisig_verify_share_keyset", [self.handle], key_idx, True, R, S, m, offs, len(offs) - 1,
+                                            R.shape[0], share_transcript, share_slot, z, fmt, want_R)
+
     def multisig_verify_wire(self, key_idx, offsets, sig_w, m, want_status: bool = True):
         """`multisig_verify` with the aggregate signature as sig_w (B, 64) = u || R (jjs_multisig_verify_keyset_wire[_dev]).
         Returns (status, tally, agg_pk)."""
@@ -1557,6 +1628,14 @@ class SignerGroup:
         _ffi.check(getattr(self._lib, name)(self.handle, d(z, 32, N), d(R, w, N), d(S, w, N), d(m, 32, B), B, o(status),
                                             o(tstatus), o(su), o(sr), Engine._stream()), name)
         return status, su, sr, tstatus
+
+    def verify_share(self, R, S, m, share_transcript, share_slot, z, fmt: str = "affine", want_R: bool = False):
+        """`Engine.multisig_verify_share` over B transcripts of the group's n participants (R / S (B n, ...), m (B, 32), share
+        (t, i) at row t n + i): the group's d_i, aggregate key and tables are on the device already
+        (jjs_msig_group_verify_share[_dev])."""
+        B = m.shape[0]
+        return self._eng._msig_verify_share("jjs_msig_group_verify_share", [self.handle], None, None, R, S, m, None, B, B * self.participants,
+                                            share_transcript, share_slot, z, fmt, want_R)
 
     def info(self) -> dict:
         out = (ctypes.c_uint64 * len(self.INFO_NAMES))()

@@ -941,6 +941,40 @@ __global__ __launch_bounds__(BLOCK) void msig_round1_kernel(const uint8_t* r, co
     for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += total) ms_round1_item(r, s, comb_g, i, R_out, S_out, bad);
 }
 
+// ---- verify_share on its own (msig_share.h) -----------------------------------------------------------------
+// The check pass behind the map (a lane per participant row); the sums pass (msig_kernel's lane rules: eight lanes per transcript
+// when the call has few; a table in the lane) and, in the lanes behind it, the first step of the query pass (a lane per query, a
+// table in the lane): one launch, the two read a_words alone and share no output; the queries' lanes begin at a multiple of the
+// wave (MSH_QUERY_ALIGN), so that no wave runs both bodies one after the other; the second step of the query pass (a lane per
+// query).  Grid-stride.
+__global__ __launch_bounds__(BLOCK) void msig_share_check_kernel(msig_share_params X) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < X.M.n_total; i += total) msh_check_item(X, i);
+}
+__global__ __launch_bounds__(BLOCK, 2) void msig_share_sums_kernel(msig_share_params X) {
+    const uint64_t gtid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    uint32_t* ws = X.M.lane_ws + gtid * WS_WORDS_PER_LANE;
+    const uint32_t hl = X.M.hash_lanes;
+    const int coop = hl > 1 ? (int)(gtid % hl) : -1;
+    const uint64_t sums_lanes = (uint64_t)X.M.n_transcripts * hl, first_query = msh_first_query_lane(sums_lanes);
+    for (uint64_t k = gtid; k < first_query + X.n_queries; k += total) {
+        if (k < sums_lanes) msh_sums_item(X, (uint32_t)(k / hl), ws, coop);
+        else if (k >= first_query) msh_commit_item(X, k - first_query, ws);
+    }
+}
+__global__ __launch_bounds__(BLOCK, 2) void msig_share_inline_kernel(msig_share_params X) {
+    const uint64_t gtid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    uint32_t* ws = X.M.lane_ws + gtid * WS_WORDS_PER_LANE;
+    for (uint64_t q = gtid; q < X.n_queries; q += total) msh_inline_item(X, q, ws);
+}
+// a comb and a walk over the group's or the set's tables per query; no workspace
+__global__ __launch_bounds__(BLOCK, 2) void msig_share_tables_kernel(msig_share_params X) {
+    const uint64_t total = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t q = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; q < X.n_queries; q += total) msh_tables_item(X, q);
+}
+
 // ---- `is_valid` alone (points_check.h) ---------------------------------------------------------------------
 // One lane per point; the two lanes of a two-point item are the lanes 2j and 2j + 1 of one wave (the grid's lane count is a
 // multiple of the block), so one exchange with lane ^ 1 gives both the item's status; each then writes its own output row and

@@ -256,6 +256,7 @@ struct device_state {
     size_t msig_ext_rows = 0;      // ... and a third: rows whose extended points an *_ext call normalises into it (0 until one asks)
     size_t msig_ks_rows = 0, msig_ks_transcripts = 0;   // ... and the gathered keys of a key-set call (msig_keyset.h; 0 until one asks)
     size_t msig_sign_rows = 0, msig_sign_transcripts = 0;   // ... and the flags and columns of a signing call (msig_sign.h; 0 until one asks)
+    size_t msig_share_queries = 0, msig_share_transcripts = 0;   // ... and the points, flags and columns of a verify_share call (msig_share.h; 0 until one asks)
     int grid_msig = 0;
     int key_priority = 0;                // stream priority of the slots' key streams
     int table_priority = 0;              // ... and of their table streams (the lowest)

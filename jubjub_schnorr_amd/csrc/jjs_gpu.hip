@@ -24,6 +24,7 @@
 //   msig_keyset_calls.h  the multisignature call against a registered key set, both forms
 //   msig_verify_calls.h  the verifier's half: aggregate_pk, and aggregate_pk followed by the single-scheme verification
 //   msig_sign_calls.h  the signer's half: sign_round_1, and sign_round_2 over whole ragged batches (a generator of test material)
+//   msig_share_calls.h  verify_share on its own: single shares by transcript and slot, inline, by signer group and by key set
 //   sign_vargen_calls.h  var-generator signing and key derivation with the generator as a point, both forms (test material)
 //   sign_fixed_calls.h  signing and key derivation with a SecretKey in the single and double schemes, both forms (test material)
 //   host_lanes.h       the small ones (included among the entry points, behind the table of call shapes): staging lanes
@@ -75,6 +76,7 @@
 #include "msig_keyset.h"
 #include "msig_verify.h"
 #include "msig_sign.h"
+#include "msig_share.h"
 #include "batch_verdict.h"
 #include "keyset_verdict.h"
 #include "points_check.h"
@@ -837,7 +839,10 @@ int jjs_compress_dev(const void* affine, size_t n, void* out, void* stream) {
 // table index of every row (4) and the refused word of every transcript (4).  Behind those, once a signing call (msig_sign.h) has
 // asked for it (g->msig_sign_rows rows in g->msig_sign_transcripts transcripts; no other caller pays for it): the flag words of the
 // check pass -- pk_repeats (4) per row, bad_enc and dup_nonce (4 each) per transcript, one run of words that the call clears with
-// one memset -- and the two columns a signing call has no output for, pk_agg and RSa (64 bytes per transcript each).
+// one memset -- and the two columns a signing call has no output for, pk_agg and RSa (64 bytes per transcript each).  Behind those,
+// once a verify_share call (msig_share.h) has asked for it (g->msig_share_queries queries in g->msig_share_transcripts transcripts;
+// no other caller pays for it): one extended point per query (EXT_WORDS words), the flag word of every transcript (4 bytes), and
+// the two columns such a call may have no output for, pk_agg and RSa (64 bytes per transcript each).
 struct msig_scratch {
     uint32_t *tr_of, *d_words, *dpk, *e_pt, *a_words, *c_words, *offsets, *long_tags;
     uint8_t* norm[3];
@@ -846,11 +851,13 @@ struct msig_scratch {
     uint32_t *ks_row_key, *ks_refused;
     uint32_t* sign_flags;                 // pk_repeats [rows], bad_enc [transcripts], dup_nonce [transcripts]
     uint8_t *sign_agg, *sign_rsa;
+    uint32_t *share_pt, *share_bad;       // [queries][EXT_WORDS], [transcripts]
+    uint8_t *share_agg, *share_rsa;
 };
 constexpr size_t MSIG_EXT_ROW_BYTES = 3 * 64 + 9 * 4;
 static size_t msig_scratch_bytes(size_t items, size_t transcripts, size_t ext_rows, size_t ks_rows = 0, size_t ks_transcripts = 0,
-                                 size_t sign_rows = 0, size_t sign_transcripts = 0) {
-    return items * 4 * (1 + 8 + 2 * EXT_WORDS) + transcripts * 4 * (16 + 1 + 18) + 64 + (ext_rows ? ext_rows * MSIG_EXT_ROW_BYTES + 64 : 0) +
+                                 size_t sign_rows = 0, size_t sign_transcripts = 0, size_t share_queries = 0, size_t share_transcripts = 0) {
+    return (share_queries ? share_queries * 4 * EXT_WORDS + share_transcripts * (4 + 128) + 128 : 0) + items * 4 * (1 + 8 + 2 * EXT_WORDS) + transcripts * 4 * (16 + 1 + 18) + 64 + (ext_rows ? ext_rows * MSIG_EXT_ROW_BYTES + 64 : 0) +
            (ks_rows ? ks_rows * (64 + 4) + ks_transcripts * 4 + 128 : 0) + (sign_rows ? sign_rows * 4 + sign_transcripts * (8 + 128) + 128 : 0);
 }
 static msig_scratch msig_scratch_carve() {
@@ -881,12 +888,19 @@ static msig_scratch msig_scratch_carve() {
         W.sign_flags = w; w += g->msig_sign_rows + 2 * g->msig_sign_transcripts;
         W.sign_agg = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(w) + 63) & ~uintptr_t(63));
         W.sign_rsa = W.sign_agg + 64 * g->msig_sign_transcripts;
+        w = reinterpret_cast<uint32_t*>(W.sign_rsa + 64 * g->msig_sign_transcripts);
+    }
+    if (g->msig_share_queries) {
+        W.share_pt = w; w += EXT_WORDS * g->msig_share_queries;
+        W.share_bad = w; w += g->msig_share_transcripts;
+        W.share_agg = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(w) + 63) & ~uintptr_t(63));
+        W.share_rsa = W.share_agg + 64 * g->msig_share_transcripts;
     }
     return W;
 }
 static int ensure_msig_scratch(size_t n, size_t n_transcripts, size_t ext_rows = 0, size_t ks_rows = 0, size_t ks_transcripts = 0,
-                               size_t sign_rows = 0, size_t sign_transcripts = 0) {
-    if (n <= g->msig_items && n_transcripts <= g->msig_transcripts && ext_rows <= g->msig_ext_rows && ks_rows <= g->msig_ks_rows &&
+                               size_t sign_rows = 0, size_t sign_transcripts = 0, size_t share_queries = 0, size_t share_transcripts = 0) {
+    if (share_queries <= g->msig_share_queries && share_transcripts <= g->msig_share_transcripts && n <= g->msig_items && n_transcripts <= g->msig_transcripts && ext_rows <= g->msig_ext_rows && ks_rows <= g->msig_ks_rows &&
         ks_transcripts <= g->msig_ks_transcripts && sign_rows <= g->msig_sign_rows && sign_transcripts <= g->msig_sign_transcripts)
         return JJS_OK;
     size_t ci = grown(n < 4096 ? 4096 : n), ct = grown(n_transcripts < 1024 ? 1024 : n_transcripts);
@@ -900,12 +914,17 @@ static int ensure_msig_scratch(size_t n, size_t n_transcripts, size_t ext_rows =
     size_t cs = sign_rows ? grown(sign_rows < 4096 ? 4096 : sign_rows) : 0, cst = sign_rows ? grown(sign_transcripts < 1024 ? 1024 : sign_transcripts) : 0;
     if (cs < g->msig_sign_rows) cs = g->msig_sign_rows;
     if (cst < g->msig_sign_transcripts) cst = g->msig_sign_transcripts;
+    size_t cq = share_queries ? grown(share_queries < 4096 ? 4096 : share_queries) : 0;
+    size_t cqt = share_queries ? grown(share_transcripts < 1024 ? 1024 : share_transcripts) : 0;
+    if (cq < g->msig_share_queries) cq = g->msig_share_queries;
+    if (cqt < g->msig_share_transcripts) cqt = g->msig_share_transcripts;
     device_mem<uint8_t> fresh;
-    HIP_TRY(fresh.alloc(msig_scratch_bytes(ci, ct, ce, ck, ckt, cs, cst)));
+    HIP_TRY(fresh.alloc(msig_scratch_bytes(ci, ct, ce, ck, ckt, cs, cst, cq, cqt)));
     g->msig.replace(std::move(fresh));
     g->msig_items = ci; g->msig_transcripts = ct; g->msig_ext_rows = ce;
     g->msig_ks_rows = ck; g->msig_ks_transcripts = ckt;
     g->msig_sign_rows = cs; g->msig_sign_transcripts = cst;
+    g->msig_share_queries = cq; g->msig_share_transcripts = cqt;
     return JJS_OK;
 }
 // The normalisation in front of the passes of an extended call: `cols` columns of n rows (96 bytes a point) into the scratch's
@@ -1053,6 +1072,7 @@ static const dlog_tables& host_dlog_tables() {
 #include "msig_keyset_calls.h"
 #include "msig_verify_calls.h"
 #include "msig_sign_calls.h"
+#include "msig_share_calls.h"
 
 // ---- challenge export ---------------------------------------------------------------------------
 static int launch_challenge(challenge_params P, void* stream) {

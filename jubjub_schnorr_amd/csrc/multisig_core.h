@@ -113,12 +113,16 @@ JJS_HD void msig_agg_item(const msig_params& P, uint32_t t, int coop = -1) {
     msig_binding_hash(P, t, lo, hi, msig_tag(P, t, hi - lo, 1, 3 + 4 * (int)(hi - lo)), P.agg_pk, t, coop);
 }
 // pass 3 (lane per participant): E_i = R_i + a * S_i
-JJS_HD void msig_commit_share(const msig_params& P, uint64_t i, uint32_t t, uint32_t* ws) {
+// (row i of transcript t, into dst: the row's own slot of e_pt here, a query's point in msig_share.h)
+JJS_HD void msig_commit_share_to(const msig_params& P, uint64_t i, uint32_t t, uint32_t* ws, uint32_t* dst) {
     const fe_src rs{P.R, 64, 0}, ss{P.S, 64, 0};
     build_point_table(ws, load_fq(ss, i), load_fq(ss, i, 32));
     ext_pt as = table_mul(ws, load_w8(P.a_words + 8 * t), true);
     ext_pt r = ext_from_affine(load_fq(rs, i), load_fq(rs, i, 32));
-    store_ext(P.e_pt + EXT_WORDS * i, ext_add_niels(as, to_niels(r), false, true));
+    store_ext(dst, ext_add_niels(as, to_niels(r), false, true));
+}
+JJS_HD void msig_commit_share(const msig_params& P, uint64_t i, uint32_t t, uint32_t* ws) {
+    msig_commit_share_to(P, i, t, ws, P.e_pt + EXT_WORDS * i);
 }
 JJS_HD void msig_commit_item(const msig_params& P, uint64_t i, uint32_t* ws) { msig_commit_share(P, i, P.tr_of[i], ws); }
 // pass 4 (lane per transcript): RSa = sum E_i, c = H(RSa, pk_agg, m), u = sum z_i
