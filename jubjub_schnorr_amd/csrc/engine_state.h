@@ -284,7 +284,7 @@ struct device_state {
                                          // used in the order of slot 0's event, grows under the engine's mutex; jjs_trim frees it
     grow_only<uint8_t> sign_key;         // jjs_sign_fixed* with one key for the call: the record of the keyed route's pre-pass (sign_fixed.h,
                                          // bytes); used and grown as sign_tables; jjs_trim frees it
-    grow_only<uint8_t> msig_stage;       // host-buffer multisig calls (jjs_multisig_combine, jjs_msig_group_combine): their columns and
+    grow_only<uint8_t> msig_stage;       // the blocking host-buffer multisig and signing calls (staged_host_call.h): their columns and
                                          // outputs (bytes), on ks_stream under host_mu; it grows under the engine's mutex as well, which
                                          // jjs_memory_stats reads it under; jjs_trim frees it
 };

@@ -898,6 +898,16 @@ static msig_scratch msig_scratch_carve() {
     }
     return W;
 }
+// What the calls over the scratch set alike in their msig_params.  a_c false: a verifier's call, which computes neither a nor c and
+// leaves their words unset -- as every field a call does not set stays: the kernels read those as flags.
+static void msig_params_common(msig_params& P, const msig_scratch& W, size_t n_transcripts, size_t n, bool a_c = true) {
+    P.n_transcripts = (uint32_t)n_transcripts; P.n_total = n;
+    P.tr_of = W.tr_of; P.d_words = W.d_words; P.dpk = W.dpk; P.offsets = W.offsets;
+    if (a_c) { P.a_words = W.a_words; P.c_words = W.c_words; }
+    P.tags = g->tags_long; P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
+    P.max_table_participants = JJS_MSIG_MAX_PARTICIPANTS;
+    P.long_tags = W.long_tags;
+}
 static int ensure_msig_scratch(size_t n, size_t n_transcripts, size_t ext_rows = 0, size_t ks_rows = 0, size_t ks_transcripts = 0,
                                size_t sign_rows = 0, size_t sign_transcripts = 0, size_t share_queries = 0, size_t share_transcripts = 0) {
     if (share_queries <= g->msig_share_queries && share_transcripts <= g->msig_share_transcripts && n <= g->msig_items && n_transcripts <= g->msig_transcripts && ext_rows <= g->msig_ext_rows && ks_rows <= g->msig_ks_rows &&
@@ -994,15 +1004,11 @@ static int msig_combine_locked(int fmt, const void* z, const void* PK, const voi
     const msig_scratch W = msig_scratch_carve();
     const uint8_t* pts[3] = {(const uint8_t*)PK, (const uint8_t*)R, (const uint8_t*)S};
     msig_params P{};
+    msig_params_common(P, W, n_transcripts, n);
     P.z = (const uint8_t*)z; P.m = (const uint8_t*)m;
-    P.n_transcripts = (uint32_t)n_transcripts; P.n_total = n;
     P.share_status = (uint8_t*)share_status; P.agg_pk = (uint8_t*)agg_pk; P.sig_u = (uint8_t*)sig_u; P.sig_R = (uint8_t*)sig_R;
     P.transcript_status = (uint8_t*)transcript_status;
-    P.tr_of = W.tr_of; P.d_words = W.d_words; P.dpk = W.dpk; P.e_pt = W.e_pt;
-    P.a_words = W.a_words; P.c_words = W.c_words; P.offsets = W.offsets;
-    P.tags = g->tags_long; P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
-    P.max_table_participants = JJS_MSIG_MAX_PARTICIPANTS;
-    P.long_tags = W.long_tags;
+    P.e_pt = W.e_pt;
     big_slot();
     if (int rc = begin_shared(s)) return rc;
     auto queue = [&]() -> int {
@@ -1068,6 +1074,7 @@ static const dlog_tables& host_dlog_tables() {
 }
 
 #include "msig_group_calls.h"
+#include "staged_host_call.h"
 #include "msig_host_calls.h"
 #include "msig_keyset_calls.h"
 #include "msig_verify_calls.h"

@@ -141,6 +141,15 @@ int jjs_msig_group_aggregate_pk(jjs_msig_group h, uint8_t out[64]) {
     return JJS_OK;
 }
 
+// n = the shares of n_transcripts transcripts of group k: fewer than 2^32, they are indexed with 32 bits
+static int msig_group_rows(const msig_group_entry& k, size_t n_transcripts, size_t& n) {
+    const uint64_t per = k.participants;
+    if (n_transcripts >= (1ull << 32) / per + ((1ull << 32) % per ? 1u : 0u))
+        return fail(JJS_ERR_ARG, "%zu transcripts of %llu participants: the shares are indexed with 32 bits", n_transcripts, (unsigned long long)per);
+    n = n_transcripts * per;
+    return JJS_OK;
+}
+
 // The call against group h on device columns, queued on s (under the engine's mutex, g the device).  fmt (JJS_FORMAT_*): R, S are
 // B n x 64, B n x 96 or B n x 32.
 static int msig_group_combine_locked(jjs_msig_group h, int fmt, const void* z, const void* R, const void* S, const void* m, size_t n_transcripts,
@@ -148,10 +157,8 @@ static int msig_group_combine_locked(jjs_msig_group h, int fmt, const void* z, c
     msig_group_entry* k = g_msig_groups.find(h);
     if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed signer group");
     if (n_transcripts == 0) return JJS_OK;
-    const uint64_t per = k->participants;
-    if (n_transcripts >= (1ull << 32) / per + ((1ull << 32) % per ? 1u : 0u))
-        return fail(JJS_ERR_ARG, "%zu transcripts of %llu participants: the shares are indexed with 32 bits", n_transcripts, (unsigned long long)per);
-    const size_t n = n_transcripts * per;
+    size_t n = 0;
+    if (int rc = msig_group_rows(*k, n_transcripts, n)) return rc;
     if (!all_ok(z, R, S, m, sig_u, sig_R) || !share_status) return fail(JJS_ERR_ARG, "null or misaligned pointer");
     const msig_group_copy* c = copy_for(*k, g);
     if (!c) return fail(JJS_ERR_ARG, "the signer group has no copy on this device");
@@ -167,7 +174,7 @@ static int msig_group_combine_locked(jjs_msig_group h, int fmt, const void* z, c
     const msig_scratch W = msig_scratch_carve();
     P.e_pt = W.e_pt; P.a_words = W.a_words; P.c_words = W.c_words;
     P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
-    G.participants = (uint32_t)per;
+    G.participants = k->participants;
     G.d_words = c->d_words; G.tables = c->tables; G.tag_a = c->tag_a + 9;
     G.by_participant = n_transcripts >= MSIG_GROUP_BY_PARTICIPANT_FROM ? 1u : 0u;
 #if defined(JJS_PROFILING)

@@ -26,15 +26,11 @@ static int msig_keyset_combine_locked(const keyset_entry& k, const keyset_copy& 
     const uint8_t* pts[2] = {(const uint8_t*)R, (const uint8_t*)S};
     msig_keyset_params K{};
     msig_params& P = K.M;
+    msig_params_common(P, W, n_transcripts, n);
     P.z = (const uint8_t*)z; P.m = (const uint8_t*)m;
-    P.n_transcripts = (uint32_t)n_transcripts; P.n_total = n;
     P.share_status = (uint8_t*)share_status; P.agg_pk = (uint8_t*)agg_pk; P.sig_u = (uint8_t*)sig_u; P.sig_R = (uint8_t*)sig_R;
     P.transcript_status = (uint8_t*)transcript_status;
-    P.tr_of = W.tr_of; P.d_words = W.d_words; P.dpk = W.dpk; P.e_pt = W.e_pt;
-    P.a_words = W.a_words; P.c_words = W.c_words; P.offsets = W.offsets;
-    P.tags = g->tags_long; P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
-    P.max_table_participants = JJS_MSIG_MAX_PARTICIPANTS;
-    P.long_tags = W.long_tags;
+    P.e_pt = W.e_pt;
     P.PK = W.ks_pk;
     K.key_idx = (const uint32_t*)key_idx; K.n_keys = k.n_keys;
     K.keys = c.keys[0]; K.flags = c.flags[0]; K.tables = c.tables[0];
@@ -69,7 +65,7 @@ static int msig_keyset_combine_locked(const keyset_entry& k, const keyset_copy& 
     return rc ? rc : rc2;
 }
 
-static int msig_keyset_combine_dev(jjs_keyset ks, int format, bool wire, const void* key_idx, const void* z, const void* R, const void* S, const void* m,
+static int msig_keyset_combine_dev(jjs_keyset ks, int format, unsigned formats, const void* key_idx, const void* z, const void* R, const void* S, const void* m,
                                     const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
                                     void* agg_pk, void* sig_u, void* sig_R, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
@@ -78,7 +74,7 @@ static int msig_keyset_combine_dev(jjs_keyset ks, int format, bool wire, const v
     const keyset_copy* c = nullptr;
     int fmt = JJS_FORMAT_AFFINE;
     if (int rc = msig_keyset_find(ks, g, k, c)) return rc;
-    if (int rc = msig_call_format(format, wire, fmt)) return rc;
+    if (int rc = msig_format(format, formats, fmt)) return rc;
     if (n_transcripts == 0) return JJS_OK;
     return no_throw([&] {
         return msig_keyset_combine_locked(*k, *c, fmt, key_idx, z, R, S, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk,
@@ -86,48 +82,39 @@ static int msig_keyset_combine_dev(jjs_keyset ks, int format, bool wire, const v
     });
 }
 
-static int msig_keyset_combine_host(jjs_keyset ks, int format, bool wire, const uint32_t* key_idx, const uint8_t* z, const uint8_t* R, const uint8_t* S,
+// parts: as the inline call's (msig_host_calls.h); the indices travel in its PK column, 4 bytes a share
+static int msig_keyset_combine_host(jjs_keyset ks, int format, unsigned formats, const uint32_t* key_idx, const uint8_t* z, const uint8_t* R, const uint8_t* S,
                                 const uint8_t* m, const uint32_t* offsets, size_t n_transcripts, uint8_t* share_status,
                                 uint8_t* transcript_status, uint8_t* agg_pk, uint8_t* sig_u, uint8_t* sig_R) {
-    device_state* dev = nullptr;
+    const size_t B = n_transcripts;
     int fmt = JJS_FORMAT_AFFINE;
     size_t n = 0;
-    {
-        std::lock_guard<std::mutex> lock(L.mu);
-        if (int rc = check_ready()) return rc;
-        keyset_entry* k = nullptr;
-        const keyset_copy* c = nullptr;
-        if (int rc = msig_keyset_find(ks, g, k, c)) return rc;
-        if (int rc = msig_call_format(format, wire, fmt)) return rc;
-        if (n_transcripts == 0) return JJS_OK;
-        if (int rc = msig_check_offsets(offsets, n_transcripts, n)) return rc;
-        if ((n && (!key_idx || !z || !R || !S || !share_status)) || !m || !agg_pk || !sig_u || !sig_R) return fail(JJS_ERR_ARG, "null pointer");
-        dev = g;
-        ++g_blocking_calls;              // jjs_shutdown does not free `dev` before this call has left
-    }
-    blocking_call_leave leave_on_every_way_out;
-    std::lock_guard<std::mutex> big(dev->host_mu);
-    g = dev;
-    return no_throw([&]() -> int {
-        const size_t B = n_transcripts, w = msig_point_bytes(fmt);
-        const void* src[5] = {z, key_idx, R, S, m};            // the indices travel in the inline call's PK column: 4 bytes a share
-        const size_t in_bytes[5] = {n * 32, n * 4, n * w, n * w, B * 32}, out_bytes[5] = {n, B, B * 64, B * 32, B * 64};
-        msig_stage St{};
-        if (int rc = msig_stage_in(dev, src, in_bytes, out_bytes, St)) return rc;
-        {
-            std::lock_guard<std::mutex> lock(L.mu);
-            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
+    return staged_host_call(
+        [&](bool& go) -> int {
+            keyset_entry* k = nullptr;
+            const keyset_copy* c = nullptr;
+            if (int rc = msig_keyset_find(ks, g, k, c)) return rc;
+            if (int rc = msig_format(format, formats, fmt)) return rc;
+            if (B == 0) return JJS_OK;
+            if (int rc = msig_check_offsets(offsets, B, n)) return rc;
+            if ((n && (!key_idx || !z || !R || !S || !share_status)) || !m || !agg_pk || !sig_u || !sig_R) return fail(JJS_ERR_ARG, "null pointer");
+            go = true;
+            return JJS_OK;
+        },
+        [&] {
+            const size_t w = msig_point_bytes(fmt);
+            return std::vector<stage_part>{{n * 32, z, nullptr}, {n * 4, key_idx, nullptr}, {n * w, R, nullptr}, {n * w, S, nullptr}, {B * 32, m, nullptr},
+                                           {n, nullptr, share_status}, {B, nullptr, transcript_status}, {B * 64, nullptr, agg_pk},
+                                           {B * 32, nullptr, sig_u}, {B * 64, nullptr, sig_R}};
+        },
+        [&](uint8_t* const* p, hipStream_t s) -> int {
             // (the set is looked up again: it may have been destroyed meanwhile)
             keyset_entry* k = nullptr;
             const keyset_copy* c = nullptr;
-            if (int rc = msig_keyset_find(ks, dev, k, c)) return rc;
-            if (int rc = msig_keyset_combine_locked(*k, *c, fmt, St.in[1], St.in[0], St.in[2], St.in[3], St.in[4], offsets, B, St.out[0],
-                                                    transcript_status ? St.out[1] : nullptr, St.out[2], St.out[3], St.out[4], St.s))
-                return rc;
-        }
-        uint8_t* const dst[5] = {share_status, transcript_status, agg_pk, sig_u, sig_R};
-        return msig_stage_out(St, dst, out_bytes);
-    });
+            if (int rc = msig_keyset_find(ks, g, k, c)) return rc;
+            return msig_keyset_combine_locked(*k, *c, fmt, p[1], p[0], p[2], p[3], p[4], offsets, B, p[5], transcript_status ? p[6] : nullptr, p[7],
+                                              p[8], p[9], s);
+        });
 }
 }  // extern "C++"
 
@@ -136,25 +123,25 @@ extern "C" {
 int jjs_multisig_combine_keyset_dev(jjs_keyset ks, int format, const void* key_idx, const void* z, const void* R, const void* S, const void* m,
                                     const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
                                     void* agg_pk, void* sig_u, void* sig_R, void* stream) {
-    return msig_keyset_combine_dev(ks, format, false, key_idx, z, R, S, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk,
+    return msig_keyset_combine_dev(ks, format, MSIG_FORMATS_POINTS, key_idx, z, R, S, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk,
                                    sig_u, sig_R, stream);
 }
 int jjs_multisig_combine_keyset_wire_dev(jjs_keyset ks, const void* key_idx, const void* z, const void* R_w, const void* S_w, const void* m,
                                          const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
                                          void* agg_pk, void* sig_u, void* sig_R, void* stream) {
-    return msig_keyset_combine_dev(ks, JJS_FORMAT_WIRE, true, key_idx, z, R_w, S_w, m, offsets_host, n_transcripts, share_status,
+    return msig_keyset_combine_dev(ks, JJS_FORMAT_WIRE, MSIG_FORMATS_WIRE, key_idx, z, R_w, S_w, m, offsets_host, n_transcripts, share_status,
                                    transcript_status, agg_pk, sig_u, sig_R, stream);
 }
 int jjs_multisig_combine_keyset(jjs_keyset ks, int format, const uint32_t* key_idx, const uint8_t* z, const uint8_t* R, const uint8_t* S,
                                 const uint8_t* m, const uint32_t* offsets, size_t n_transcripts, uint8_t* share_status,
                                 uint8_t* transcript_status, uint8_t* agg_pk, uint8_t* sig_u, uint8_t* sig_R) {
-    return msig_keyset_combine_host(ks, format, false, key_idx, z, R, S, m, offsets, n_transcripts, share_status, transcript_status, agg_pk,
+    return msig_keyset_combine_host(ks, format, MSIG_FORMATS_POINTS, key_idx, z, R, S, m, offsets, n_transcripts, share_status, transcript_status, agg_pk,
                                     sig_u, sig_R);
 }
 int jjs_multisig_combine_keyset_wire(jjs_keyset ks, const uint32_t* key_idx, const uint8_t* z, const uint8_t* R_w, const uint8_t* S_w,
                                      const uint8_t* m, const uint32_t* offsets, size_t n_transcripts, uint8_t* share_status,
                                      uint8_t* transcript_status, uint8_t* agg_pk, uint8_t* sig_u, uint8_t* sig_R) {
-    return msig_keyset_combine_host(ks, JJS_FORMAT_WIRE, true, key_idx, z, R_w, S_w, m, offsets, n_transcripts, share_status,
+    return msig_keyset_combine_host(ks, JJS_FORMAT_WIRE, MSIG_FORMATS_WIRE, key_idx, z, R_w, S_w, m, offsets, n_transcripts, share_status,
                                     transcript_status, agg_pk, sig_u, sig_R);
 }
 

@@ -16,22 +16,12 @@ struct msh_call {
     size_t Q;
     void *status, *sig_R;
 };
-static int msh_format(int format, int& fmt) {
-    if (format != JJS_FORMAT_AFFINE && format != JJS_FORMAT_EXT && format != JJS_FORMAT_WIRE)
-        return fail(JJS_ERR_ARG, "verify_share takes affine, extended or wire points (format %d)", format);
-    fmt = format;
-    return JJS_OK;
-}
 // the rows of a call whose transcripts are acceptable: the combine call's own rules (under the engine's mutex)
 static int msh_rows(const msh_call& A, size_t& n) {
     if (A.route != MSH_GROUP) return msig_check_offsets(A.offsets_host, A.B, n);
     msig_group_entry* k = g_msig_groups.find(A.handle);
     if (!k) return fail(JJS_ERR_ARG, "unknown or destroyed signer group");
-    const uint64_t per = k->participants;
-    if (A.B >= (1ull << 32) / per + ((1ull << 32) % per ? 1u : 0u))
-        return fail(JJS_ERR_ARG, "%zu transcripts of %llu participants: the shares are indexed with 32 bits", A.B, (unsigned long long)per);
-    n = A.B * per;
-    return JJS_OK;
+    return msig_group_rows(*k, A.B, n);
 }
 // The call on device columns, queued on st (under the engine's mutex, g the device; B > 0, and Q > 0 or sig_R given).
 static int msig_share_locked(const msh_call& A, hipStream_t st) {
@@ -63,15 +53,11 @@ static int msig_share_locked(const msh_call& A, hipStream_t st) {
     const uint8_t** cols = A.route == MSH_INLINE ? pts : pts + 1;
     msig_share_params X{};
     msig_params& P = X.M;
+    msig_params_common(P, W, B, n);
     P.m = (const uint8_t*)A.m;
-    P.n_transcripts = (uint32_t)B; P.n_total = n;
     P.sig_R = A.sig_R ? (uint8_t*)A.sig_R : W.share_rsa;
     P.agg_pk = A.route == MSH_GROUP ? gc->agg_pk : W.share_agg;
-    P.tr_of = W.tr_of; P.d_words = W.d_words; P.dpk = W.dpk; P.e_pt = W.share_pt;
-    P.a_words = W.a_words; P.c_words = W.c_words; P.offsets = W.offsets;
-    P.tags = g->tags_long; P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
-    P.max_table_participants = JJS_MSIG_MAX_PARTICIPANTS;
-    P.long_tags = W.long_tags;
+    P.e_pt = W.share_pt;
     P.hash_lanes = 1;
     X.q_transcript = (const uint32_t*)A.qt; X.q_slot = (const uint32_t*)A.qs; X.q_z = (const uint8_t*)A.z;
     X.n_queries = Q; X.q_status = (uint8_t*)A.status;
@@ -138,82 +124,57 @@ static int msig_share_locked(const msh_call& A, hipStream_t st) {
     const int rc2 = end_shared(st);             // the slot's event covers whatever was queued, also when a step failed
     return rc ? rc : rc2;
 }
-// what every form looks at first (under the engine's mutex): 0 with go = false: nothing to do
+// what every form looks at first (under the engine's mutex, behind check_ready): JJS_OK with go = false: nothing to do
 static int msh_enter(msh_call& A, int format, bool& go) {
     go = false;
-    if (int rc = check_ready()) return rc;
     if (A.route == MSH_GROUP && !g_msig_groups.find(A.handle)) return fail(JJS_ERR_ARG, "unknown or destroyed signer group");
     if (A.route == MSH_KEYSET) {
         keyset_entry* k = nullptr;
         const keyset_copy* c = nullptr;
         if (int rc = msig_keyset_find(A.handle, g, k, c)) return rc;
     }
-    if (int rc = msh_format(format, A.fmt)) return rc;
+    if (int rc = msig_format(format, MSIG_FORMATS_POINTS | MSIG_FORMATS_WIRE, A.fmt)) return rc;
     go = A.B != 0 && (A.Q != 0 || A.sig_R != nullptr);
     return JJS_OK;
 }
 static int msig_share_dev(msh_call A, int format, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
     bool go = false;
     if (int rc = msh_enter(A, format, go)) return rc;
     if (!go) return JJS_OK;
     return no_throw([&] { return msig_share_locked(A, (hipStream_t)stream); });
 }
-// The same from host buffers, blocking, on the route of jjs_multisig_combine (msig_host_calls.h): the columns go whole into the
-// device's multisignature staging area, one such call at a time per device.
+// The same from host buffers, blocking, on the frame of staged_host_call.h.
+// parts: keys (PK, key_idx, or empty for a group), R, S, m, share_transcript, share_slot, z in; share_status, sig_R out
 static int msig_share_host(msh_call A, int format) {
-    device_state* dev = nullptr;
     size_t n = 0;
-    {
-        std::lock_guard<std::mutex> lock(L.mu);
-        bool go = false;
-        if (int rc = msh_enter(A, format, go)) return rc;
-        if (!go) return JJS_OK;
-        if (int rc = msh_rows(A, n)) return rc;
-        if ((n && (!A.R || !A.S || (A.route != MSH_GROUP && !A.keys))) || !A.m || (A.Q && (!A.qt || !A.qs || !A.z || !A.status)))
-            return fail(JJS_ERR_ARG, "null pointer");
-        dev = g;
-        ++g_blocking_calls;              // jjs_shutdown does not free `dev` before this call has left
-    }
-    blocking_call_leave leave_on_every_way_out;
-    std::lock_guard<std::mutex> big(dev->host_mu);
-    g = dev;
-    return no_throw([&]() -> int {
-        const size_t B = A.B, Q = A.Q, w = msig_point_bytes(A.fmt);
-        const size_t key_bytes = A.route == MSH_GROUP ? 0 : (A.route == MSH_KEYSET ? n * 4 : n * w);
-        // one area, laid out here (parts padded to 256 bytes, as msig_stage_in's): seven columns in, two out
-        const void* src[7] = {A.keys, A.R, A.S, A.m, A.qt, A.qs, A.z};
-        const size_t bytes[9] = {key_bytes, n * w, n * w, B * 32, Q * 4, Q * 4, Q * 32, Q, B * 64};
-        size_t off[9], total = 0;
-        for (int i = 0; i < 9; ++i) { off[i] = total; total += pad256(bytes[i] ? bytes[i] : 1); }
-        HIP_TRY(hipSetDevice(dev->device));
-        if (dev->msig_stage.capacity() < total) {
-            std::lock_guard<std::mutex> lock(L.mu);
-            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
-            if (int rc = dev->msig_stage.ensure(total)) return rc;
-        }
-        hipStream_t st = dev->ks_stream;
-        uint8_t* part[9];
-        for (int i = 0; i < 9; ++i) part[i] = dev->msig_stage + off[i];
-        for (int i = 0; i < 7; ++i)
-            if (bytes[i]) HIP_TRY(hipMemcpyAsync(part[i], src[i], bytes[i], hipMemcpyHostToDevice, st));
-        {
-            std::lock_guard<std::mutex> lock(L.mu);
-            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
+    return staged_host_call(
+        [&](bool& go) -> int {
+            if (int rc = msh_enter(A, format, go)) return rc;
+            if (!go) return JJS_OK;
+            if (int rc = msh_rows(A, n)) return rc;
+            if ((n && (!A.R || !A.S || (A.route != MSH_GROUP && !A.keys))) || !A.m || (A.Q && (!A.qt || !A.qs || !A.z || !A.status)))
+                return fail(JJS_ERR_ARG, "null pointer");
+            return JJS_OK;
+        },
+        [&] {
+            const size_t B = A.B, Q = A.Q, w = msig_point_bytes(A.fmt);
+            const size_t key_bytes = A.route == MSH_GROUP ? 0 : (A.route == MSH_KEYSET ? n * 4 : n * w);
+            return std::vector<stage_part>{{key_bytes, A.keys, nullptr}, {n * w, A.R, nullptr}, {n * w, A.S, nullptr}, {B * 32, A.m, nullptr},
+                                           {Q * 4, A.qt, nullptr}, {Q * 4, A.qs, nullptr}, {Q * 32, A.z, nullptr},
+                                           {Q, nullptr, A.status}, {B * 64, nullptr, A.sig_R}};
+        },
+        [&](uint8_t* const* p, hipStream_t st) -> int {
             // (a group or a set is looked up again by the call: it may have been destroyed, or registered anew, meanwhile)
             msh_call D = A;
-            D.keys = part[0]; D.R = part[1]; D.S = part[2]; D.m = part[3]; D.qt = part[4]; D.qs = part[5]; D.z = part[6];
-            D.status = part[7]; D.sig_R = A.sig_R ? part[8] : nullptr;
+            D.keys = p[0]; D.R = p[1]; D.S = p[2]; D.m = p[3]; D.qt = p[4]; D.qs = p[5]; D.z = p[6];
+            D.status = p[7]; D.sig_R = A.sig_R ? p[8] : nullptr;
             size_t n_now = 0;
             if (int rc = msh_rows(D, n_now)) return rc;
             if (n_now != n) return fail(JJS_ERR_ARG, "the signer group was destroyed during the call");
-            if (int rc = msig_share_locked(D, st)) return rc;
-        }
-        if (Q) HIP_TRY(hipMemcpyAsync(A.status, part[7], Q, hipMemcpyDeviceToHost, st));
-        if (A.sig_R) HIP_TRY(hipMemcpyAsync(A.sig_R, part[8], B * 64, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return JJS_OK;
-    });
+            return msig_share_locked(D, st);
+        });
 }
 static msh_call msh_make(int route, uint64_t handle, const void* keys, const void* R, const void* S, const void* m, const uint32_t* offsets,
                          size_t B, const void* qt, const void* qs, const void* z, size_t Q, void* status, void* sig_R) {

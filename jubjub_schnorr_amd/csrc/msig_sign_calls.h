@@ -26,14 +26,10 @@ static int msig_sign_locked(const ms_call& A, const uint32_t* offsets_host, size
     const uint8_t* pts[3] = {(const uint8_t*)A.PK, (const uint8_t*)A.R, (const uint8_t*)A.S};
     msig_sign_params G{};
     msig_params& P = G.M;
+    msig_params_common(P, W, B, n);
     P.m = (const uint8_t*)A.m;
-    P.n_transcripts = (uint32_t)B; P.n_total = n;
     P.agg_pk = W.sign_agg; P.sig_R = W.sign_rsa;
-    P.tr_of = W.tr_of; P.d_words = W.d_words; P.dpk = W.dpk; P.e_pt = W.e_pt;
-    P.a_words = W.a_words; P.c_words = W.c_words; P.offsets = W.offsets;
-    P.tags = g->tags_long; P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
-    P.max_table_participants = JJS_MSIG_MAX_PARTICIPANTS;
-    P.long_tags = W.long_tags;
+    P.e_pt = W.e_pt;
     P.hash_lanes = 1;
     G.pk_repeats = W.sign_flags; G.bad_enc = W.sign_flags + g->msig_sign_rows; G.dup_nonce = G.bad_enc + g->msig_sign_transcripts;
     G.signer_row = (const uint32_t*)A.signer_row;
@@ -93,73 +89,48 @@ int jjs_multisig_sign_dev(int format, const void* PK, const void* R, const void*
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
     ms_call A{};
-    if (int rc = msig_format(format, A.ext)) return rc;
+    int fmt = JJS_FORMAT_AFFINE;
+    if (int rc = msig_format(format, MSIG_FORMATS_POINTS, fmt)) return rc;
     if (n_transcripts == 0 || n_signing == 0) return JJS_OK;
+    A.ext = fmt == JJS_FORMAT_EXT;
     A.PK = PK; A.R = R; A.S = S; A.m = m; A.signer_row = signer_row; A.sk = sk; A.r = r; A.s = s; A.n_signing = n_signing;
     A.z_out = z_out; A.status = sign_status;
     return no_throw([&] { return msig_sign_locked(A, offsets_host, n_transcripts, (hipStream_t)stream); });
 }
 
-// The same from host buffers, blocking, on the route of jjs_multisig_combine (msig_host_calls.h): the columns go whole into the
-// device's multisignature staging area, one such call at a time per device.  The staged sk, r and s are cleared on the stream
-// behind the share pass, before the call returns.
+// The same from host buffers, blocking, on the frame of staged_host_call.h.  The staged sk, r and s are marked secret: the frame
+// clears them on the stream behind the share pass, before the call returns.
+// parts: PK, R, S, m, signer_row, sk, r, s in; z_out, sign_status out
 int jjs_multisig_sign(int format, const uint8_t* PK, const uint8_t* R, const uint8_t* S, const uint8_t* m, const uint32_t* offsets,
                       size_t n_transcripts, const uint32_t* signer_row, const uint8_t* sk, const uint8_t* r, const uint8_t* s, size_t n_signing,
                       uint8_t* z_out, uint8_t* sign_status) {
-    device_state* dev = nullptr;
-    bool ext = false;
+    const size_t B = n_transcripts, k = n_signing;
+    int fmt = JJS_FORMAT_AFFINE;
     size_t n = 0;
-    {
-        std::lock_guard<std::mutex> lock(L.mu);
-        if (int rc = check_ready()) return rc;
-        if (int rc = msig_format(format, ext)) return rc;
-        if (n_transcripts == 0 || n_signing == 0) return JJS_OK;
-        if (int rc = msig_check_offsets(offsets, n_transcripts, n)) return rc;
-        if (!signer_row && n_signing != n)
-            return fail(JJS_ERR_ARG, "without signer_row a call signs every row: %zu signing rows, %zu participant rows", n_signing, n);
-        if ((n && (!PK || !R || !S)) || !m || !sk || !r || !s || !z_out || !sign_status) return fail(JJS_ERR_ARG, "null pointer");
-        dev = g;
-        ++g_blocking_calls;              // jjs_shutdown does not free `dev` before this call has left
-    }
-    blocking_call_leave leave_on_every_way_out;
-    std::lock_guard<std::mutex> big(dev->host_mu);
-    g = dev;
-    return no_throw([&]() -> int {
-        const size_t B = n_transcripts, w = ext ? 96 : 64, k = n_signing;
-        // two rounds of the five-column staging would overlap: one area, laid out here (parts padded to 256 bytes, as msig_stage_in's)
-        const void* src[8] = {PK, R, S, m, signer_row, sk, r, s};
-        const size_t bytes[10] = {n * w, n * w, n * w, B * 32, signer_row ? k * 4 : 0, k * 32, k * 32, k * 32, k * 32, k};
-        size_t off[10], total = 0;
-        for (int i = 0; i < 10; ++i) { off[i] = total; total += pad256(bytes[i] ? bytes[i] : 1); }
-        HIP_TRY(hipSetDevice(dev->device));
-        if (dev->msig_stage.capacity() < total) {
-            std::lock_guard<std::mutex> lock(L.mu);
-            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
-            if (int rc = dev->msig_stage.ensure(total)) return rc;
-        }
-        hipStream_t st = dev->ks_stream;
-        uint8_t* part[10];
-        for (int i = 0; i < 10; ++i) part[i] = dev->msig_stage + off[i];
-        // whatever happens behind this point, the staged secrets (parts 5-7, adjacent) are cleared before the call returns
-        struct wipe {
-            uint8_t* at; size_t bytes; hipStream_t st;
-            ~wipe() { (void)hipMemsetAsync(at, 0, bytes, st); (void)hipStreamSynchronize(st); }
-        } wipe_secrets{part[5], off[8] - off[5], st};
-        for (int i = 0; i < 8; ++i)
-            if (bytes[i]) HIP_TRY(hipMemcpyAsync(part[i], src[i], bytes[i], hipMemcpyHostToDevice, st));
-        {
-            std::lock_guard<std::mutex> lock(L.mu);
-            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
+    return staged_host_call(
+        [&](bool& go) -> int {
+            if (int rc = msig_format(format, MSIG_FORMATS_POINTS, fmt)) return rc;
+            if (B == 0 || k == 0) return JJS_OK;
+            if (int rc = msig_check_offsets(offsets, B, n)) return rc;
+            if (!signer_row && k != n)
+                return fail(JJS_ERR_ARG, "without signer_row a call signs every row: %zu signing rows, %zu participant rows", k, n);
+            if ((n && (!PK || !R || !S)) || !m || !sk || !r || !s || !z_out || !sign_status) return fail(JJS_ERR_ARG, "null pointer");
+            go = true;
+            return JJS_OK;
+        },
+        [&] {
+            const size_t w = msig_point_bytes(fmt);
+            return std::vector<stage_part>{{n * w, PK, nullptr}, {n * w, R, nullptr}, {n * w, S, nullptr}, {B * 32, m, nullptr},
+                                           {signer_row ? k * 4 : 0, signer_row, nullptr}, {k * 32, sk, nullptr}, {k * 32, r, nullptr},
+                                           {k * 32, s, nullptr}, {k * 32, nullptr, z_out}, {k, nullptr, sign_status}};
+        },
+        [&](uint8_t* const* p, hipStream_t st) {
             ms_call A{};
-            A.ext = ext; A.PK = part[0]; A.R = part[1]; A.S = part[2]; A.m = part[3]; A.signer_row = signer_row ? part[4] : nullptr;
-            A.sk = part[5]; A.r = part[6]; A.s = part[7]; A.n_signing = k; A.z_out = part[8]; A.status = part[9];
-            if (int rc = msig_sign_locked(A, offsets, B, st)) return rc;
-        }
-        HIP_TRY(hipMemcpyAsync(z_out, part[8], k * 32, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(sign_status, part[9], k, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return JJS_OK;
-    });
+            A.ext = fmt == JJS_FORMAT_EXT; A.PK = p[0]; A.R = p[1]; A.S = p[2]; A.m = p[3]; A.signer_row = signer_row ? p[4] : nullptr;
+            A.sk = p[5]; A.r = p[6]; A.s = p[7]; A.n_signing = k; A.z_out = p[8]; A.status = p[9];
+            return msig_sign_locked(A, offsets, B, st);
+        },
+        stage_secrets{5, 3});
 }
 
 }  // extern "C"

@@ -53,12 +53,8 @@ static int msig_verify_locked(const mv_call& A, const uint32_t* offsets_host, si
     const msig_scratch W = msig_scratch_carve();
     msig_verify_keyset_params VK{};
     msig_params& P = VK.K.M;
-    P.n_transcripts = (uint32_t)B; P.n_total = n;
+    msig_params_common(P, W, B, n, false);
     P.agg_pk = (uint8_t*)A.agg_pk;
-    P.tr_of = W.tr_of; P.d_words = W.d_words; P.dpk = W.dpk; P.offsets = W.offsets;
-    P.tags = g->tags_long; P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
-    P.max_table_participants = JJS_MSIG_MAX_PARTICIPANTS;
-    P.long_tags = W.long_tags;
     P.hash_lanes = 1;
     VK.vec_status = (uint8_t*)A.vec_status; VK.poison = A.verify ? 1u : 0u;
     if (A.keyset) {
@@ -119,7 +115,7 @@ static int msig_verify_locked(const mv_call& A, const uint32_t* offsets_host, si
 }
 
 // a _dev entry point: the checks in front of the call, under the engine's mutex
-static int msig_verify_dev(mv_call A, const jjs_keyset* ks, int format, bool wire, const uint32_t* offsets_host, size_t n_transcripts, void* stream) {
+static int msig_verify_dev(mv_call A, const jjs_keyset* ks, int format, unsigned formats, const uint32_t* offsets_host, size_t n_transcripts, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
     if (ks) {
@@ -127,7 +123,7 @@ static int msig_verify_dev(mv_call A, const jjs_keyset* ks, int format, bool wir
         if (int rc = msig_keyset_find(*ks, g, k, A.c)) return rc;
         A.k = k;
     }
-    if (int rc = msig_call_format(format, wire, A.fmt)) return rc;
+    if (int rc = msig_format(format, formats, A.fmt)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (n_transcripts == 0) {
         if (A.verify && A.tally) HIP_TRY(hipMemsetAsync(A.tally, 0, 4 * sizeof(unsigned long long), s));
@@ -136,56 +132,50 @@ static int msig_verify_dev(mv_call A, const jjs_keyset* ks, int format, bool wir
     return no_throw([&] { return msig_verify_locked(A, offsets_host, n_transcripts, s); });
 }
 
-// a host-buffer entry point: blocking, as jjs_multisig_combine (msig_host_calls.h).  A's pointers are the caller's host buffers.
-static int msig_verify_host(mv_call A, const jjs_keyset* ks, int format, bool wire, const uint32_t* offsets, size_t n_transcripts, uint64_t* tally) {
-    device_state* dev = nullptr;
+// a host-buffer entry point: blocking, on the frame of staged_host_call.h.  A's pointers are the caller's host buffers.
+// parts: keys (PK or key_idx), u, R, m and an empty one in; agg_pk, status, tally, vec_status and an empty one out.  A wire call
+// uploads its u || R rows as one column in u's part, R's part is empty, and R = u's part + 32.
+static int msig_verify_host(mv_call A, const jjs_keyset* ks, int format, unsigned formats, const uint32_t* offsets, size_t n_transcripts, uint64_t* tally) {
+    const size_t B = n_transcripts;
     size_t n = 0;
-    {
-        std::lock_guard<std::mutex> lock(L.mu);
-        if (int rc = check_ready()) return rc;
-        if (ks) {
-            keyset_entry* k = nullptr;
-            if (int rc = msig_keyset_find(*ks, g, k, A.c)) return rc;
-        }
-        if (int rc = msig_call_format(format, wire, A.fmt)) return rc;
-        if (n_transcripts == 0) {
-            if (A.verify && tally) for (int k = 0; k < 4; ++k) tally[k] = 0;
+    return staged_host_call(
+        [&](bool& go) -> int {
+            if (ks) {
+                keyset_entry* k = nullptr;
+                if (int rc = msig_keyset_find(*ks, g, k, A.c)) return rc;
+            }
+            if (int rc = msig_format(format, formats, A.fmt)) return rc;
+            if (B == 0) {
+                if (A.verify && tally) for (int k = 0; k < 4; ++k) tally[k] = 0;
+                return JJS_OK;
+            }
+            if (int rc = msig_check_offsets(offsets, B, n)) return rc;
+            if ((n && !A.keys) || !A.agg_pk || (A.verify && (!A.u || !A.R || !A.m))) return fail(JJS_ERR_ARG, "null pointer");
+            go = true;
             return JJS_OK;
-        }
-        if (int rc = msig_check_offsets(offsets, n_transcripts, n)) return rc;
-        if ((n && !A.keys) || !A.agg_pk || (A.verify && (!A.u || !A.R || !A.m))) return fail(JJS_ERR_ARG, "null pointer");
-        dev = g;
-        ++g_blocking_calls;              // jjs_shutdown does not free `dev` before this call has left
-    }
-    blocking_call_leave leave_on_every_way_out;
-    std::lock_guard<std::mutex> big(dev->host_mu);
-    g = dev;
-    return no_throw([&]() -> int {
-        const size_t B = n_transcripts, w = msig_point_bytes(A.fmt), v = A.verify ? 1 : 0;
-        const void* src[5] = {A.keys, A.u, A.R, A.m, nullptr};                   // wire: A.u is the u || R rows, uploaded as one column
-        const size_t in_bytes[5] = {n * (A.keyset ? 4 : w), v * B * (wire ? 64 : 32), wire ? 0 : v * B * w, v * B * 32, 0};
-        const size_t out_bytes[5] = {B * 64, v * B, v * 32, (1 - v) * B, 0};
-        msig_stage St{};
-        if (int rc = msig_stage_in(dev, src, in_bytes, out_bytes, St)) return rc;
-        {
-            std::lock_guard<std::mutex> lock(L.mu);
-            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
+        },
+        [&] {
+            const bool wire = A.fmt == JJS_FORMAT_WIRE;
+            const size_t w = msig_point_bytes(A.fmt), v = A.verify ? 1 : 0;
+            return std::vector<stage_part>{{n * (A.keyset ? 4 : w), A.keys, nullptr}, {v * B * (wire ? 64 : 32), A.u, nullptr},
+                                           {wire ? 0 : v * B * w, A.R, nullptr}, {v * B * 32, A.m, nullptr}, {0, nullptr, nullptr},
+                                           {B * 64, nullptr, A.agg_pk}, {v * B, nullptr, A.status}, {v * 32, nullptr, tally},
+                                           {(1 - v) * B, nullptr, A.vec_status}, {0, nullptr, nullptr}};
+        },
+        [&](uint8_t* const* p, hipStream_t s) -> int {
             mv_call D = A;
             if (ks) {                    // (the set is looked up again: it may have been destroyed meanwhile)
                 keyset_entry* k = nullptr;
-                if (int rc = msig_keyset_find(*ks, dev, k, D.c)) return rc;
+                if (int rc = msig_keyset_find(*ks, g, k, D.c)) return rc;
                 D.k = k;
             }
-            D.keys = St.in[0]; D.u = St.in[1]; D.R = wire ? (const uint8_t*)St.in[1] + 32 : St.in[2]; D.m = St.in[3];
-            D.agg_pk = St.out[0];
-            D.status = A.status ? St.out[1] : nullptr;
-            D.tally = tally ? St.out[2] : nullptr;
-            D.vec_status = A.vec_status ? St.out[3] : nullptr;
-            if (int rc = msig_verify_locked(D, offsets, B, St.s)) return rc;
-        }
-        uint8_t* const dst[5] = {(uint8_t*)A.agg_pk, (uint8_t*)A.status, (uint8_t*)tally, (uint8_t*)A.vec_status, nullptr};
-        return msig_stage_out(St, dst, out_bytes);
-    });
+            D.keys = p[0]; D.u = p[1]; D.R = A.fmt == JJS_FORMAT_WIRE ? p[1] + 32 : p[2]; D.m = p[3];
+            D.agg_pk = p[5];
+            D.status = A.status ? p[6] : nullptr;
+            D.tally = tally ? p[7] : nullptr;
+            D.vec_status = A.vec_status ? p[8] : nullptr;
+            return msig_verify_locked(D, offsets, B, s);
+        });
 }
 }  // extern "C++"
 
@@ -195,52 +185,52 @@ int jjs_multisig_aggregate_pk_dev(int format, const void* PK, const uint32_t* of
                                   void* vec_status, void* stream) {
     mv_call A{};
     A.keys = PK; A.agg_pk = agg_pk; A.vec_status = vec_status;
-    return msig_verify_dev(A, nullptr, format, false, offsets_host, n_transcripts, stream);
+    return msig_verify_dev(A, nullptr, format, MSIG_FORMATS_POINTS, offsets_host, n_transcripts, stream);
 }
 int jjs_multisig_aggregate_pk(int format, const uint8_t* PK, const uint32_t* offsets, size_t n_transcripts, uint8_t* agg_pk,
                               uint8_t* vec_status) {
     mv_call A{};
     A.keys = PK; A.agg_pk = agg_pk; A.vec_status = vec_status;
-    return msig_verify_host(A, nullptr, format, false, offsets, n_transcripts, nullptr);
+    return msig_verify_host(A, nullptr, format, MSIG_FORMATS_POINTS, offsets, n_transcripts, nullptr);
 }
 int jjs_multisig_aggregate_pk_keyset_dev(jjs_keyset ks, const void* key_idx, const uint32_t* offsets_host, size_t n_transcripts,
                                          void* agg_pk, void* vec_status, void* stream) {
     mv_call A{};
     A.keyset = true; A.keys = key_idx; A.agg_pk = agg_pk; A.vec_status = vec_status;
-    return msig_verify_dev(A, &ks, JJS_FORMAT_AFFINE, false, offsets_host, n_transcripts, stream);
+    return msig_verify_dev(A, &ks, JJS_FORMAT_AFFINE, MSIG_FORMATS_POINTS, offsets_host, n_transcripts, stream);
 }
 int jjs_multisig_aggregate_pk_keyset(jjs_keyset ks, const uint32_t* key_idx, const uint32_t* offsets, size_t n_transcripts,
                                      uint8_t* agg_pk, uint8_t* vec_status) {
     mv_call A{};
     A.keyset = true; A.keys = key_idx; A.agg_pk = agg_pk; A.vec_status = vec_status;
-    return msig_verify_host(A, &ks, JJS_FORMAT_AFFINE, false, offsets, n_transcripts, nullptr);
+    return msig_verify_host(A, &ks, JJS_FORMAT_AFFINE, MSIG_FORMATS_POINTS, offsets, n_transcripts, nullptr);
 }
 
 int jjs_multisig_verify_dev(int format, const void* PK, const uint32_t* offsets_host, const void* u, const void* R, const void* m,
                             size_t n_transcripts, void* agg_pk, void* status, void* tally, void* stream) {
     mv_call A{};
     A.verify = true; A.keys = PK; A.u = u; A.R = R; A.m = m; A.agg_pk = agg_pk; A.status = status; A.tally = tally;
-    return msig_verify_dev(A, nullptr, format, false, offsets_host, n_transcripts, stream);
+    return msig_verify_dev(A, nullptr, format, MSIG_FORMATS_POINTS, offsets_host, n_transcripts, stream);
 }
 int jjs_multisig_verify(int format, const uint8_t* PK, const uint32_t* offsets, const uint8_t* u, const uint8_t* R, const uint8_t* m,
                         size_t n_transcripts, uint8_t* agg_pk, uint8_t* status, uint64_t tally[4]) {
     mv_call A{};
     A.verify = true; A.keys = PK; A.u = u; A.R = R; A.m = m; A.agg_pk = agg_pk; A.status = status;
-    return msig_verify_host(A, nullptr, format, false, offsets, n_transcripts, tally);
+    return msig_verify_host(A, nullptr, format, MSIG_FORMATS_POINTS, offsets, n_transcripts, tally);
 }
 int jjs_multisig_verify_keyset_dev(jjs_keyset ks, int format, const void* key_idx, const uint32_t* offsets_host, const void* u,
                                    const void* R, const void* m, size_t n_transcripts, void* agg_pk, void* status, void* tally,
                                    void* stream) {
     mv_call A{};
     A.keyset = true; A.verify = true; A.keys = key_idx; A.u = u; A.R = R; A.m = m; A.agg_pk = agg_pk; A.status = status; A.tally = tally;
-    return msig_verify_dev(A, &ks, format, false, offsets_host, n_transcripts, stream);
+    return msig_verify_dev(A, &ks, format, MSIG_FORMATS_POINTS, offsets_host, n_transcripts, stream);
 }
 int jjs_multisig_verify_keyset(jjs_keyset ks, int format, const uint32_t* key_idx, const uint32_t* offsets, const uint8_t* u,
                                const uint8_t* R, const uint8_t* m, size_t n_transcripts, uint8_t* agg_pk, uint8_t* status,
                                uint64_t tally[4]) {
     mv_call A{};
     A.keyset = true; A.verify = true; A.keys = key_idx; A.u = u; A.R = R; A.m = m; A.agg_pk = agg_pk; A.status = status;
-    return msig_verify_host(A, &ks, format, false, offsets, n_transcripts, tally);
+    return msig_verify_host(A, &ks, format, MSIG_FORMATS_POINTS, offsets, n_transcripts, tally);
 }
 
 // the wire forms: PK_w is N x 32, sig_w is B x 64 = u || R (the layout of jjs_verify_single_wire)
@@ -255,32 +245,32 @@ int jjs_multisig_aggregate_pk_wire_dev(const void* PK_w, const uint32_t* offsets
                                        void* stream) {
     mv_call A{};
     A.keys = PK_w; A.agg_pk = agg_pk; A.vec_status = vec_status;
-    return msig_verify_dev(A, nullptr, JJS_FORMAT_WIRE, true, offsets_host, n_transcripts, stream);
+    return msig_verify_dev(A, nullptr, JJS_FORMAT_WIRE, MSIG_FORMATS_WIRE, offsets_host, n_transcripts, stream);
 }
 int jjs_multisig_aggregate_pk_wire(const uint8_t* PK_w, const uint32_t* offsets, size_t n_transcripts, uint8_t* agg_pk, uint8_t* vec_status) {
     mv_call A{};
     A.keys = PK_w; A.agg_pk = agg_pk; A.vec_status = vec_status;
-    return msig_verify_host(A, nullptr, JJS_FORMAT_WIRE, true, offsets, n_transcripts, nullptr);
+    return msig_verify_host(A, nullptr, JJS_FORMAT_WIRE, MSIG_FORMATS_WIRE, offsets, n_transcripts, nullptr);
 }
 int jjs_multisig_verify_wire_dev(const void* PK_w, const uint32_t* offsets_host, const void* sig_w, const void* m, size_t n_transcripts,
                                  void* agg_pk, void* status, void* tally, void* stream) {
     mv_call A = mv_verify_wire_call(false, PK_w, sig_w, m, agg_pk, status, tally);
-    return msig_verify_dev(A, nullptr, JJS_FORMAT_WIRE, true, offsets_host, n_transcripts, stream);
+    return msig_verify_dev(A, nullptr, JJS_FORMAT_WIRE, MSIG_FORMATS_WIRE, offsets_host, n_transcripts, stream);
 }
 int jjs_multisig_verify_wire(const uint8_t* PK_w, const uint32_t* offsets, const uint8_t* sig_w, const uint8_t* m, size_t n_transcripts,
                              uint8_t* agg_pk, uint8_t* status, uint64_t tally[4]) {
     mv_call A = mv_verify_wire_call(false, PK_w, sig_w, m, agg_pk, status, nullptr);
-    return msig_verify_host(A, nullptr, JJS_FORMAT_WIRE, true, offsets, n_transcripts, tally);
+    return msig_verify_host(A, nullptr, JJS_FORMAT_WIRE, MSIG_FORMATS_WIRE, offsets, n_transcripts, tally);
 }
 int jjs_multisig_verify_keyset_wire_dev(jjs_keyset ks, const void* key_idx, const uint32_t* offsets_host, const void* sig_w, const void* m,
                                         size_t n_transcripts, void* agg_pk, void* status, void* tally, void* stream) {
     mv_call A = mv_verify_wire_call(true, key_idx, sig_w, m, agg_pk, status, tally);
-    return msig_verify_dev(A, &ks, JJS_FORMAT_WIRE, true, offsets_host, n_transcripts, stream);
+    return msig_verify_dev(A, &ks, JJS_FORMAT_WIRE, MSIG_FORMATS_WIRE, offsets_host, n_transcripts, stream);
 }
 int jjs_multisig_verify_keyset_wire(jjs_keyset ks, const uint32_t* key_idx, const uint32_t* offsets, const uint8_t* sig_w, const uint8_t* m,
                                     size_t n_transcripts, uint8_t* agg_pk, uint8_t* status, uint64_t tally[4]) {
     mv_call A = mv_verify_wire_call(true, key_idx, sig_w, m, agg_pk, status, nullptr);
-    return msig_verify_host(A, &ks, JJS_FORMAT_WIRE, true, offsets, n_transcripts, tally);
+    return msig_verify_host(A, &ks, JJS_FORMAT_WIRE, MSIG_FORMATS_WIRE, offsets, n_transcripts, tally);
 }
 
 }  // extern "C"

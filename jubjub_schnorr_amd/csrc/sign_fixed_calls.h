@@ -93,65 +93,34 @@ static int sf_dev(const sf_call& A, size_t n, void* stream) {
     if (int rc = sf_pointers(A, true)) return rc;
     return no_throw([&] { return sf_locked(A, n, (hipStream_t)stream); });
 }
-// The same from host buffers, blocking, on the route of jjs_sign_vargen_pt: the columns go whole into the device's multisignature
-// staging area, one such call at a time per device.  The staged sk and rnd are cleared on the stream behind the last kernel,
-// before the call returns.
+// The same from host buffers, blocking, on the frame of staged_host_call.h.  The staged sk and rnd are marked secret: the frame
+// clears them on the stream behind the last kernel, before the call returns.
+// parts: m, sk, rnd in; u_out, R_out, Rp_out, PK_out, PKp_out, sig_w, pk_w, status out (an output the caller does not ask for: empty)
 static int sf_host(const sf_call& H, size_t n) {
-    device_state* dev = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(L.mu);
-        if (int rc = check_ready()) return rc;
-        if (int rc = sf_shape(H.scheme, H.n_sk, n)) return rc;
-        if (n == 0) return JJS_OK;
-        if (int rc = sf_pointers(H, false)) return rc;
-        dev = g;
-        ++g_blocking_calls;              // jjs_shutdown does not free `dev` before this call has left
-    }
-    blocking_call_leave leave_on_every_way_out;
-    std::lock_guard<std::mutex> big(dev->host_mu);
-    g = dev;
-    return no_throw([&]() -> int {
-        const size_t nk = H.n_sk, dbl = H.scheme == JJS_SCHEME_DOUBLE ? 1 : 0;
-        // one area, laid out here (parts padded to 256 bytes): m, the secrets adjacent, then the outputs
-        constexpr int N_IN = 3, N_OUT = 8;
-        const void* src[N_IN] = {H.m, H.sk, H.rnd};
-        void* const dst[N_OUT] = {H.u_out, H.R_out, H.Rp_out, H.PK_out, H.PKp_out, H.sig_w, H.pk_w, H.status};
-        const size_t out_bytes[N_OUT] = {n * 32, n * 64, n * 64, nk * 64, nk * 64, n * (64 + 32 * dbl), nk * (32 + 32 * dbl), n};
-        size_t bytes[N_IN + N_OUT] = {H.sign ? n * 32 : 0, nk * 32, H.sign ? n * 32 : 0};
-        for (int j = 0; j < N_OUT; ++j) bytes[N_IN + j] = dst[j] ? out_bytes[j] : 0;
-        size_t off[N_IN + N_OUT + 1], total = 0;
-        for (int i = 0; i < N_IN + N_OUT; ++i) { off[i] = total; total += pad256(bytes[i] ? bytes[i] : 1); }
-        off[N_IN + N_OUT] = total;
-        HIP_TRY(hipSetDevice(dev->device));
-        if (dev->msig_stage.capacity() < total) {
-            std::lock_guard<std::mutex> lock(L.mu);
-            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
-            if (int rc = dev->msig_stage.ensure(total)) return rc;
-        }
-        hipStream_t st = dev->ks_stream;
-        uint8_t* part[N_IN + N_OUT];
-        for (int i = 0; i < N_IN + N_OUT; ++i) part[i] = dev->msig_stage + off[i];
-        // whatever happens behind this point, the staged secrets (parts 1-2, adjacent) are cleared before the call returns
-        struct wipe {
-            uint8_t* at; size_t bytes; hipStream_t st;
-            ~wipe() { (void)hipMemsetAsync(at, 0, bytes, st); (void)hipStreamSynchronize(st); }
-        } wipe_secrets{part[1], off[3] - off[1], st};
-        for (int i = 0; i < N_IN; ++i)
-            if (bytes[i]) HIP_TRY(hipMemcpyAsync(part[i], src[i], bytes[i], hipMemcpyHostToDevice, st));
-        {
-            std::lock_guard<std::mutex> lock(L.mu);
-            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
+    return staged_host_call(
+        [&](bool& go) -> int {
+            if (int rc = sf_shape(H.scheme, H.n_sk, n)) return rc;
+            if (n == 0) return JJS_OK;
+            go = true;
+            return sf_pointers(H, false);
+        },
+        [&] {
+            const size_t nk = H.n_sk, dbl = H.scheme == JJS_SCHEME_DOUBLE ? 1 : 0, in = H.sign ? n * 32 : 0;
+            auto out = [](void* dst, size_t bytes) { return stage_part{dst ? bytes : 0, nullptr, dst}; };
+            return std::vector<stage_part>{{in, H.m, nullptr}, {nk * 32, H.sk, nullptr}, {in, H.rnd, nullptr},
+                                           out(H.u_out, n * 32), out(H.R_out, n * 64), out(H.Rp_out, n * 64), out(H.PK_out, nk * 64),
+                                           out(H.PKp_out, nk * 64), out(H.sig_w, n * (64 + 32 * dbl)), out(H.pk_w, nk * (32 + 32 * dbl)),
+                                           out(H.status, n)};
+        },
+        [&](uint8_t* const* p, hipStream_t st) {
             sf_call A = H;
-            A.m = H.sign ? part[0] : nullptr; A.sk = part[1]; A.rnd = H.sign ? part[2] : nullptr;
-            void** const col[N_OUT] = {&A.u_out, &A.R_out, &A.Rp_out, &A.PK_out, &A.PKp_out, &A.sig_w, &A.pk_w, &A.status};
-            for (int j = 0; j < N_OUT; ++j) *col[j] = dst[j] ? part[N_IN + j] : nullptr;
-            if (int rc = sf_locked(A, n, st)) return rc;
-        }
-        for (int j = 0; j < N_OUT; ++j)
-            if (dst[j]) HIP_TRY(hipMemcpyAsync(dst[j], part[N_IN + j], bytes[N_IN + j], hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return JJS_OK;
-    });
+            A.m = H.sign ? p[0] : nullptr; A.sk = p[1]; A.rnd = H.sign ? p[2] : nullptr;
+            void** const col[8] = {&A.u_out, &A.R_out, &A.Rp_out, &A.PK_out, &A.PKp_out, &A.sig_w, &A.pk_w, &A.status};
+            for (int j = 0; j < 8; ++j)
+                if (*col[j]) *col[j] = p[3 + j];
+            return sf_locked(A, n, st);
+        },
+        stage_secrets{1, 2});
 }
 }  // extern "C++"
 

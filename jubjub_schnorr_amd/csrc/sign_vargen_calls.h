@@ -102,63 +102,32 @@ static int svg_dev(const svg_call& A, size_t n, void* stream) {
     if (int rc = svg_pointers(A, true)) return rc;
     return no_throw([&] { return svg_locked(A, n, (hipStream_t)stream); });
 }
-// The same from host buffers, blocking, on the route of jjs_multisig_sign: the columns go whole into the device's multisignature
-// staging area, one such call at a time per device.  The staged sk and rnd are cleared on the stream behind the last kernel,
-// before the call returns.
+// The same from host buffers, blocking, on the frame of staged_host_call.h.  The staged sk and rnd are marked secret: the frame
+// clears them on the stream behind the last kernel, before the call returns.
+// parts: Gen, m, sk, rnd in; u_out, R_out, PK_out, Gen_out, status out (an output the call does not have or the caller does not
+// ask for: empty)
 static int svg_host(const svg_call& H, size_t n) {
-    device_state* dev = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(L.mu);
-        if (int rc = check_ready()) return rc;
-        if (int rc = svg_shape(H.format, H.n_gen, n)) return rc;
-        if (n == 0) return JJS_OK;
-        if (int rc = svg_pointers(H, false)) return rc;
-        dev = g;
-        ++g_blocking_calls;              // jjs_shutdown does not free `dev` before this call has left
-    }
-    blocking_call_leave leave_on_every_way_out;
-    std::lock_guard<std::mutex> big(dev->host_mu);
-    g = dev;
-    return no_throw([&]() -> int {
-        const size_t ng = H.n_gen, w = svg_gen_width(H.format);
-        // one area, laid out here (parts padded to 256 bytes): the inputs, the secrets adjacent, then the outputs
-        const void* src[4] = {H.Gen, H.m, H.sk, H.rnd};
-        const size_t bytes[9] = {ng * w, H.sign ? n * 32 : 0, n * 32, H.sign ? n * 32 : 0, H.sign ? n * 32 : 0, H.sign ? n * 64 : 0,
-                                 H.PK_out ? n * 64 : 0, H.Gen_out ? ng * 64 : 0, n};
-        void* const dst[5] = {H.u_out, H.R_out, H.PK_out, H.Gen_out, H.status};
-        size_t off[10], total = 0;
-        for (int i = 0; i < 9; ++i) { off[i] = total; total += pad256(bytes[i] ? bytes[i] : 1); }
-        off[9] = total;
-        HIP_TRY(hipSetDevice(dev->device));
-        if (dev->msig_stage.capacity() < total) {
-            std::lock_guard<std::mutex> lock(L.mu);
-            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
-            if (int rc = dev->msig_stage.ensure(total)) return rc;
-        }
-        hipStream_t st = dev->ks_stream;
-        uint8_t* part[9];
-        for (int i = 0; i < 9; ++i) part[i] = dev->msig_stage + off[i];
-        // whatever happens behind this point, the staged secrets (parts 2-3, adjacent) are cleared before the call returns
-        struct wipe {
-            uint8_t* at; size_t bytes; hipStream_t st;
-            ~wipe() { (void)hipMemsetAsync(at, 0, bytes, st); (void)hipStreamSynchronize(st); }
-        } wipe_secrets{part[2], off[4] - off[2], st};
-        for (int i = 0; i < 4; ++i)
-            if (bytes[i]) HIP_TRY(hipMemcpyAsync(part[i], src[i], bytes[i], hipMemcpyHostToDevice, st));
-        {
-            std::lock_guard<std::mutex> lock(L.mu);
-            if (check_ready() != JJS_OK || g != dev) return fail(JJS_ERR_NOT_INIT, "the engine's devices changed during the call");
+    return staged_host_call(
+        [&](bool& go) -> int {
+            if (int rc = svg_shape(H.format, H.n_gen, n)) return rc;
+            if (n == 0) return JJS_OK;
+            go = true;
+            return svg_pointers(H, false);
+        },
+        [&] {
+            const size_t ng = H.n_gen, w = svg_gen_width(H.format), sn = H.sign ? n : 0;
+            return std::vector<stage_part>{{ng * w, H.Gen, nullptr}, {sn * 32, H.m, nullptr}, {n * 32, H.sk, nullptr}, {sn * 32, H.rnd, nullptr},
+                                           {sn * 32, nullptr, H.u_out}, {sn * 64, nullptr, H.R_out}, {H.PK_out ? n * 64 : 0, nullptr, H.PK_out},
+                                           {H.Gen_out ? ng * 64 : 0, nullptr, H.Gen_out}, {n, nullptr, H.status}};
+        },
+        [&](uint8_t* const* p, hipStream_t st) {
             svg_call A = H;
-            A.Gen = part[0]; A.m = H.sign ? part[1] : nullptr; A.sk = part[2]; A.rnd = H.sign ? part[3] : nullptr;
-            A.u_out = H.sign ? part[4] : nullptr; A.R_out = H.sign ? part[5] : nullptr;
-            A.PK_out = H.PK_out ? part[6] : nullptr; A.Gen_out = H.Gen_out ? part[7] : nullptr; A.status = part[8];
-            if (int rc = svg_locked(A, n, st)) return rc;
-        }
-        for (int j = 0; j < 5; ++j)
-            if (dst[j] && bytes[4 + j]) HIP_TRY(hipMemcpyAsync(dst[j], part[4 + j], bytes[4 + j], hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return JJS_OK;
-    });
+            A.Gen = p[0]; A.m = H.sign ? p[1] : nullptr; A.sk = p[2]; A.rnd = H.sign ? p[3] : nullptr;
+            A.u_out = H.sign ? p[4] : nullptr; A.R_out = H.sign ? p[5] : nullptr;
+            A.PK_out = H.PK_out ? p[6] : nullptr; A.Gen_out = H.Gen_out ? p[7] : nullptr; A.status = p[8];
+            return svg_locked(A, n, st);
+        },
+        stage_secrets{2, 2});
 }
 }  // extern "C++"
 
