@@ -55,13 +55,7 @@ template <class T> using device_mem = owned_mem<T, false>;
 template <class T> using pinned_mem = owned_mem<T, true>;
 
 // Grow-only buffers: the replacement is allocated first, the old buffer is retired with the bytes it had, then they swap.  No
-// call waits for the device here.
-size_t grown(size_t want) {              // the smallest of 2^k, 1.5 * 2^k that holds `want`: what is retired stays below what is live
-    size_t cap = 4096;
-    while (cap < want) cap <<= 1;
-    const size_t mid = cap / 4 * 3;
-    return mid >= want ? mid : cap;
-}
+// call waits for the device here.  The capacity a buffer takes: grown() of grown.h.
 // What differs from buffer to buffer, declared with the member: the capacity is counted in units (items, or bytes), never less
 // than min_units, and `cap` units are cap * unit_bytes + slack_bytes bytes.
 struct growth_rule { size_t min_units = 0, unit_bytes = 1, slack_bytes = 0; };

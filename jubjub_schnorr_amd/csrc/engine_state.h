@@ -251,12 +251,8 @@ struct device_state {
     device_mem<uint32_t> dlog_pow; // square-root tables (decode.h)
     device_mem<uint8_t> dlog_hash;
     device_mem<uint32_t> tags_long;// SAFE tags for long transcripts (multisig)
-    device_mem<uint8_t> msig;      // multisig scratch: grows in two dimensions (ensure_msig_scratch)
-    size_t msig_items = 0, msig_transcripts = 0;
-    size_t msig_ext_rows = 0;      // ... and a third: rows whose extended points an *_ext call normalises into it (0 until one asks)
-    size_t msig_ks_rows = 0, msig_ks_transcripts = 0;   // ... and the gathered keys of a key-set call (msig_keyset.h; 0 until one asks)
-    size_t msig_sign_rows = 0, msig_sign_transcripts = 0;   // ... and the flags and columns of a signing call (msig_sign.h; 0 until one asks)
-    size_t msig_share_queries = 0, msig_share_transcripts = 0;   // ... and the points, flags and columns of a verify_share call (msig_share.h; 0 until one asks)
+    device_mem<uint8_t> msig;      // multisig scratch (msig_scratch.h): grow-only, dimension by dimension (ensure_msig_scratch)
+    msig_caps msig_held;           // ... and what it holds room for
     int grid_msig = 0;
     int key_priority = 0;                // stream priority of the slots' key streams
     int table_priority = 0;              // ... and of their table streams (the lowest)
@@ -352,6 +348,18 @@ int grid_for(int resident, size_t n) {
     size_t want = (n + BLOCK - 1) / BLOCK;
     if (want < 1) want = 1;
     return (int)(want < (size_t)resident ? want : (size_t)resident);
+}
+// The schedule of msig_kernel's seven passes: the even ones run one lane per transcript, the odd ones one per share; 1, 2 and 4
+// have the hash chains.  msig_pass_grid sets P.hash_lanes for pass `pass` and gives its grid -- to launch_msig_pass, and to the
+// kernels that stand in for a pass (msig_keyset_delin_kernel for 1, msig_sign_final_kernel for 4).
+unsigned msig_pass_grid(msig_params& P, int pass) {
+    const size_t count = pass % 2 == 0 ? P.n_transcripts : P.n_total;
+    P.hash_lanes = pass == 1 || pass == 2 || pass == 4 ? msig_hash_lanes(count) : 1u;
+    return (unsigned)grid_for(g->grid_msig, count * P.hash_lanes);
+}
+void launch_msig_pass(msig_params& P, int pass, hipStream_t s) {
+    const dim3 grid(msig_pass_grid(P, pass));
+    hipLaunchKernelGGL(msig_kernel, grid, dim3(BLOCK), 0, s, P, pass);
 }
 
 #if defined(JJS_PROFILING)

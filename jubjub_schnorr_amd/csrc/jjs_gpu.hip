@@ -20,6 +20,8 @@
 //   verify_job.h       the arenas of the key-table path; a verification call in stages (begin, ingest, keys, hash, finish)
 //   (here)             device set-up and tear-down, the RCCL clique
 //   host_calls.h       the large blocking host-buffer calls: upload plan, staging copies, the pipeline
+//   (here)             the multisignature scratch (msig_scratch.h: its layout and growth, plain C++), the frame of the calls over it,
+//                      the schedule of msig_kernel's passes
 //   msig_host_calls.h  the blocking host-buffer forms of the multisignature calls
 //   msig_keyset_calls.h  the multisignature call against a registered key set, both forms
 //   msig_verify_calls.h  the verifier's half: aggregate_pk, and aggregate_pk followed by the single-scheme verification
@@ -77,6 +79,7 @@
 #include "msig_verify.h"
 #include "msig_sign.h"
 #include "msig_share.h"
+#include "msig_scratch.h"
 #include "batch_verdict.h"
 #include "keyset_verdict.h"
 #include "points_check.h"
@@ -830,73 +833,30 @@ int jjs_compress_dev(const void* affine, size_t n, void* out, void* stream) {
 }
 
 // ---- multisig: batch verify_share / combine -------------------------------------------
-// The device's multisignature scratch (g->msig, grow-only; sized for g->msig_items shares in g->msig_transcripts transcripts),
-// in words: tr_of (1), d_words (8), dpk and e_pt (EXT_WORDS each) per share, then a_words and c_words (8 each), the offsets
-// (1, and one more) and the long tags (18) per transcript.  Behind them, once an *_ext or *_wire call has asked for it (g->msig_ext_rows
-// rows; affine callers never pay for it): three columns of normalised or decoded points (64 bytes per row each) and the 9 words
-// of prefix product per row that normalize_lane keeps.  Behind those, once a key-set call (msig_keyset.h) has asked for it (g->msig_ks_rows
-// rows in g->msig_ks_transcripts transcripts; no other caller pays for it): the gathered key column (64 bytes per row), the
-// table index of every row (4) and the refused word of every transcript (4).  Behind those, once a signing call (msig_sign.h) has
-// asked for it (g->msig_sign_rows rows in g->msig_sign_transcripts transcripts; no other caller pays for it): the flag words of the
-// check pass -- pk_repeats (4) per row, bad_enc and dup_nonce (4 each) per transcript, one run of words that the call clears with
-// one memset -- and the two columns a signing call has no output for, pk_agg and RSa (64 bytes per transcript each).  Behind those,
-// once a verify_share call (msig_share.h) has asked for it (g->msig_share_queries queries in g->msig_share_transcripts transcripts;
-// no other caller pays for it): one extended point per query (EXT_WORDS words), the flag word of every transcript (4 bytes), and
-// the two columns such a call may have no output for, pk_agg and RSa (64 bytes per transcript each).
-struct msig_scratch {
-    uint32_t *tr_of, *d_words, *dpk, *e_pt, *a_words, *c_words, *offsets, *long_tags;
-    uint8_t* norm[3];
-    uint32_t* prefix;
-    uint8_t* ks_pk;
-    uint32_t *ks_row_key, *ks_refused;
-    uint32_t* sign_flags;                 // pk_repeats [rows], bad_enc [transcripts], dup_nonce [transcripts]
-    uint8_t *sign_agg, *sign_rsa;
-    uint32_t *share_pt, *share_bad;       // [queries][EXT_WORDS], [transcripts]
-    uint8_t *share_agg, *share_rsa;
-};
-constexpr size_t MSIG_EXT_ROW_BYTES = 3 * 64 + 9 * 4;
-static size_t msig_scratch_bytes(size_t items, size_t transcripts, size_t ext_rows, size_t ks_rows = 0, size_t ks_transcripts = 0,
-                                 size_t sign_rows = 0, size_t sign_transcripts = 0, size_t share_queries = 0, size_t share_transcripts = 0) {
-    return (share_queries ? share_queries * 4 * EXT_WORDS + share_transcripts * (4 + 128) + 128 : 0) + items * 4 * (1 + 8 + 2 * EXT_WORDS) + transcripts * 4 * (16 + 1 + 18) + 64 + (ext_rows ? ext_rows * MSIG_EXT_ROW_BYTES + 64 : 0) +
-           (ks_rows ? ks_rows * (64 + 4) + ks_transcripts * 4 + 128 : 0) + (sign_rows ? sign_rows * 4 + sign_transcripts * (8 + 128) + 128 : 0);
+// The device's multisignature scratch (g->msig, grow-only, holding room for g->msig_held): msig_scratch.h has its regions and its
+// growth.  It belongs to slot 0.
+static int ensure_msig_scratch(const msig_caps& need) {
+    const msig_caps caps = msig_caps_grown(g->msig_held, need);
+    if (caps == g->msig_held) return JJS_OK;
+    device_mem<uint8_t> fresh;
+    HIP_TRY(fresh.alloc(msig_scratch_layout(nullptr, caps).bytes));
+    g->msig.replace(std::move(fresh));
+    g->msig_held = caps;
+    return JJS_OK;
 }
-static msig_scratch msig_scratch_carve() {
-    msig_scratch W{};
-    uint32_t* w = reinterpret_cast<uint32_t*>(g->msig.get());
-    W.tr_of = w; w += g->msig_items;
-    W.d_words = w; w += 8 * g->msig_items;
-    W.dpk = w; w += EXT_WORDS * g->msig_items;
-    W.e_pt = w; w += EXT_WORDS * g->msig_items;
-    W.a_words = w; w += 8 * g->msig_transcripts;
-    W.c_words = w; w += 8 * g->msig_transcripts;
-    W.offsets = w; w += g->msig_transcripts + 1;
-    W.long_tags = w; w += 18 * g->msig_transcripts;
-    if (g->msig_ext_rows) {
-        uint8_t* q = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(w) + 63) & ~uintptr_t(63));
-        for (int k = 0; k < 3; ++k) { W.norm[k] = q; q += 64 * g->msig_ext_rows; }
-        W.prefix = reinterpret_cast<uint32_t*>(q);
-        w = W.prefix + 9 * g->msig_ext_rows;
-    }
-    if (g->msig_ks_rows) {
-        uint8_t* q = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(w) + 63) & ~uintptr_t(63));
-        W.ks_pk = q; q += 64 * g->msig_ks_rows;
-        W.ks_row_key = reinterpret_cast<uint32_t*>(q);
-        W.ks_refused = W.ks_row_key + g->msig_ks_rows;
-        w = W.ks_refused + g->msig_ks_transcripts;
-    }
-    if (g->msig_sign_rows) {
-        W.sign_flags = w; w += g->msig_sign_rows + 2 * g->msig_sign_transcripts;
-        W.sign_agg = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(w) + 63) & ~uintptr_t(63));
-        W.sign_rsa = W.sign_agg + 64 * g->msig_sign_transcripts;
-        w = reinterpret_cast<uint32_t*>(W.sign_rsa + 64 * g->msig_sign_transcripts);
-    }
-    if (g->msig_share_queries) {
-        W.share_pt = w; w += EXT_WORDS * g->msig_share_queries;
-        W.share_bad = w; w += g->msig_share_transcripts;
-        W.share_agg = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(w) + 63) & ~uintptr_t(63));
-        W.share_rsa = W.share_agg + 64 * g->msig_share_transcripts;
-    }
-    return W;
+extern "C++" {
+// The frame of a call on device columns over the scratch, on stream s (under the engine's mutex, g the device): queue(W) queues the
+// call's work given the carved scratch.  What a call refuses, it refuses before it comes here.
+template <class Queue>
+static int msig_scratch_call(const msig_caps& need, hipStream_t s, Queue&& queue) {
+    if (int rc = ensure_msig_scratch(need)) return rc;
+    const msig_scratch W = msig_scratch_layout(g->msig.get(), g->msig_held).W;
+    big_slot();
+    if (int rc = begin_shared(s)) return rc;
+    const int rc = queue(W);
+    sl = &g->slots[0];                          // the scratch's slot again, should the call have moved on (msig_verify_calls.h)
+    const int rc2 = end_shared(s);              // the slot's event covers whatever was queued, also when a step failed
+    return rc ? rc : rc2;
 }
 // What the calls over the scratch set alike in their msig_params.  a_c false: a verifier's call, which computes neither a nor c and
 // leaves their words unset -- as every field a call does not set stays: the kernels read those as flags.
@@ -908,35 +868,20 @@ static void msig_params_common(msig_params& P, const msig_scratch& W, size_t n_t
     P.max_table_participants = JJS_MSIG_MAX_PARTICIPANTS;
     P.long_tags = W.long_tags;
 }
-static int ensure_msig_scratch(size_t n, size_t n_transcripts, size_t ext_rows = 0, size_t ks_rows = 0, size_t ks_transcripts = 0,
-                               size_t sign_rows = 0, size_t sign_transcripts = 0, size_t share_queries = 0, size_t share_transcripts = 0) {
-    if (share_queries <= g->msig_share_queries && share_transcripts <= g->msig_share_transcripts && n <= g->msig_items && n_transcripts <= g->msig_transcripts && ext_rows <= g->msig_ext_rows && ks_rows <= g->msig_ks_rows &&
-        ks_transcripts <= g->msig_ks_transcripts && sign_rows <= g->msig_sign_rows && sign_transcripts <= g->msig_sign_transcripts)
-        return JJS_OK;
-    size_t ci = grown(n < 4096 ? 4096 : n), ct = grown(n_transcripts < 1024 ? 1024 : n_transcripts);
-    size_t ce = ext_rows ? grown(ext_rows < 4096 ? 4096 : ext_rows) : 0;
-    if (ci < g->msig_items) ci = g->msig_items;
-    if (ct < g->msig_transcripts) ct = g->msig_transcripts;
-    if (ce < g->msig_ext_rows) ce = g->msig_ext_rows;
-    size_t ck = ks_rows ? grown(ks_rows < 4096 ? 4096 : ks_rows) : 0, ckt = ks_rows ? grown(ks_transcripts < 1024 ? 1024 : ks_transcripts) : 0;
-    if (ck < g->msig_ks_rows) ck = g->msig_ks_rows;
-    if (ckt < g->msig_ks_transcripts) ckt = g->msig_ks_transcripts;
-    size_t cs = sign_rows ? grown(sign_rows < 4096 ? 4096 : sign_rows) : 0, cst = sign_rows ? grown(sign_transcripts < 1024 ? 1024 : sign_transcripts) : 0;
-    if (cs < g->msig_sign_rows) cs = g->msig_sign_rows;
-    if (cst < g->msig_sign_transcripts) cst = g->msig_sign_transcripts;
-    size_t cq = share_queries ? grown(share_queries < 4096 ? 4096 : share_queries) : 0;
-    size_t cqt = share_queries ? grown(share_transcripts < 1024 ? 1024 : share_transcripts) : 0;
-    if (cq < g->msig_share_queries) cq = g->msig_share_queries;
-    if (cqt < g->msig_share_transcripts) cqt = g->msig_share_transcripts;
-    device_mem<uint8_t> fresh;
-    HIP_TRY(fresh.alloc(msig_scratch_bytes(ci, ct, ce, ck, ckt, cs, cst, cq, cqt)));
-    g->msig.replace(std::move(fresh));
-    g->msig_items = ci; g->msig_transcripts = ct; g->msig_ext_rows = ce;
-    g->msig_ks_rows = ck; g->msig_ks_transcripts = ckt;
-    g->msig_sign_rows = cs; g->msig_sign_transcripts = cst;
-    g->msig_share_queries = cq; g->msig_share_transcripts = cqt;
-    return JJS_OK;
+// the key-set fields of a call against copy c of set k; `refused`: the word of every transcript that the gather flags
+static void msig_keyset_fill(msig_keyset_params& K, const keyset_entry& k, const keyset_copy& c, const void* key_idx, const msig_scratch& W,
+                             uint32_t* refused) {
+    K.key_idx = (const uint32_t*)key_idx; K.n_keys = k.n_keys;
+    K.keys = c.keys[0]; K.flags = c.flags[0]; K.tables = c.tables[0];
+    K.pk_col = W.ks_pk; K.row_key = W.ks_row_key; K.refused = refused;
 }
+// the signer-group fields (of msig_group_params, msig_share_params) of a call against copy c of group k
+template <class Params>
+static void msig_group_fill(Params& G, const msig_group_entry& k, const msig_group_copy& c) {
+    G.participants = k.participants;
+    G.d_words = c.d_words; G.tables = c.tables; G.tag_a = c.tag_a + 9;
+}
+}  // extern "C++"
 // The normalisation in front of the passes of an extended call: `cols` columns of n rows (96 bytes a point) into the scratch's
 // normalised columns, one item per row, in poison mode; col[] is re-aimed at the normalised columns.
 static int msig_normalize(const msig_scratch& W, const uint8_t** col, uint32_t cols, size_t n, hipStream_t s) {
@@ -1000,60 +945,50 @@ static int msig_combine_locked(int fmt, const void* z, const void* PK, const voi
     size_t n = 0;
     if (int rc = msig_check_offsets(offsets_host, n_transcripts, n)) return rc;
     if ((n && !all_ok(z, PK, R, S)) || !all_ok(m, agg_pk, sig_u, sig_R) || (n && !share_status)) return fail(JJS_ERR_ARG, "null or misaligned pointer");
-    if (int rc = ensure_msig_scratch(n, n_transcripts, fmt != JJS_FORMAT_AFFINE ? n : 0)) return rc;
-    const msig_scratch W = msig_scratch_carve();
-    const uint8_t* pts[3] = {(const uint8_t*)PK, (const uint8_t*)R, (const uint8_t*)S};
-    msig_params P{};
-    msig_params_common(P, W, n_transcripts, n);
-    P.z = (const uint8_t*)z; P.m = (const uint8_t*)m;
-    P.share_status = (uint8_t*)share_status; P.agg_pk = (uint8_t*)agg_pk; P.sig_u = (uint8_t*)sig_u; P.sig_R = (uint8_t*)sig_R;
-    P.transcript_status = (uint8_t*)transcript_status;
-    P.e_pt = W.e_pt;
-    big_slot();
-    if (int rc = begin_shared(s)) return rc;
-    auto queue = [&]() -> int {
+    msig_caps need;
+    need.rows = n; need.transcripts = n_transcripts;
+    if (fmt != JJS_FORMAT_AFFINE) need.ext_rows = n;
+    return msig_scratch_call(need, s, [&](const msig_scratch& W) -> int {
+        const uint8_t* pts[3] = {(const uint8_t*)PK, (const uint8_t*)R, (const uint8_t*)S};
+        msig_params P{};
+        msig_params_common(P, W, n_transcripts, n);
+        P.z = (const uint8_t*)z; P.m = (const uint8_t*)m;
+        P.share_status = (uint8_t*)share_status; P.agg_pk = (uint8_t*)agg_pk; P.sig_u = (uint8_t*)sig_u; P.sig_R = (uint8_t*)sig_R;
+        P.transcript_status = (uint8_t*)transcript_status;
+        P.e_pt = W.e_pt;
         HIP_TRY(hipMemcpyAsync(W.offsets, offsets_host, (n_transcripts + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         if (int rc = msig_ingest(fmt, W, pts, 3, n, s)) return rc;
         P.PK = pts[0]; P.R = pts[1]; P.S = pts[2];
-        for (int pass = 0; pass < 7; ++pass) {
-            const size_t count = (pass == 0 || pass == 2 || pass == 4 || pass == 6) ? n_transcripts : n;
-            // a pass with a hash chain and few items: eight lanes per item (multisig_core.h hash_lanes)
-            P.hash_lanes = (pass == 1 || pass == 2 || pass == 4) ? msig_hash_lanes(count) : 1u;
-            hipLaunchKernelGGL(msig_kernel, dim3(grid_for(g->grid_msig, count * P.hash_lanes)), dim3(BLOCK), 0, s, P, pass);
-        }
+        for (int pass = 0; pass < 7; ++pass) launch_msig_pass(P, pass, s);
         HIP_TRY(hipGetLastError());
         return JJS_OK;
-    };
-    const int rc = queue();
-    const int rc2 = end_shared(s);              // the slot's event covers whatever was queued, also when a step failed
-    return rc ? rc : rc2;
+    });
+}
+// the three formats of jjs_multisig_combine*_dev
+static int msig_combine_dev(int fmt, const void* z, const void* PK, const void* R, const void* S, const void* m, const uint32_t* offsets_host,
+                            size_t n_transcripts, void* share_status, void* transcript_status, void* agg_pk, void* sig_u, void* sig_R, void* stream) {
+    std::lock_guard<std::mutex> lock(L.mu);
+    if (int rc = check_ready()) return rc;
+    if (n_transcripts == 0) return JJS_OK;
+    return msig_combine_locked(fmt, z, PK, R, S, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk, sig_u, sig_R,
+                               (hipStream_t)stream);
 }
 int jjs_multisig_combine_dev(const void* z, const void* PK, const void* R, const void* S, const void* m,
                              const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
                              void* agg_pk, void* sig_u, void* sig_R, void* stream) {
-    std::lock_guard<std::mutex> lock(L.mu);
-    if (int rc = check_ready()) return rc;
-    if (n_transcripts == 0) return JJS_OK;
-    return msig_combine_locked(JJS_FORMAT_AFFINE, z, PK, R, S, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk, sig_u, sig_R,
-                               (hipStream_t)stream);
+    return msig_combine_dev(JJS_FORMAT_AFFINE, z, PK, R, S, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk, sig_u, sig_R, stream);
 }
 int jjs_multisig_combine_ext_dev(const void* z, const void* PK_ext, const void* R_ext, const void* S_ext, const void* m,
                                  const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
                                  void* agg_pk, void* sig_u, void* sig_R, void* stream) {
-    std::lock_guard<std::mutex> lock(L.mu);
-    if (int rc = check_ready()) return rc;
-    if (n_transcripts == 0) return JJS_OK;
-    return msig_combine_locked(JJS_FORMAT_EXT, z, PK_ext, R_ext, S_ext, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk,
-                               sig_u, sig_R, (hipStream_t)stream);
+    return msig_combine_dev(JJS_FORMAT_EXT, z, PK_ext, R_ext, S_ext, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk, sig_u, sig_R,
+                            stream);
 }
 int jjs_multisig_combine_wire_dev(const void* z, const void* PK_w, const void* R_w, const void* S_w, const void* m,
                                   const uint32_t* offsets_host, size_t n_transcripts, void* share_status, void* transcript_status,
                                   void* agg_pk, void* sig_u, void* sig_R, void* stream) {
-    std::lock_guard<std::mutex> lock(L.mu);
-    if (int rc = check_ready()) return rc;
-    if (n_transcripts == 0) return JJS_OK;
-    return msig_combine_locked(JJS_FORMAT_WIRE, z, PK_w, R_w, S_w, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk,
-                               sig_u, sig_R, (hipStream_t)stream);
+    return msig_combine_dev(JJS_FORMAT_WIRE, z, PK_w, R_w, S_w, m, offsets_host, n_transcripts, share_status, transcript_status, agg_pk, sig_u, sig_R,
+                            stream);
 }
 
 // The square-root tables of decode.h on the host, built once by dlog_table_entry after a cleared hash, as the device builds its

@@ -162,65 +162,61 @@ static int msig_group_combine_locked(jjs_msig_group h, int fmt, const void* z, c
     if (!all_ok(z, R, S, m, sig_u, sig_R) || !share_status) return fail(JJS_ERR_ARG, "null or misaligned pointer");
     const msig_group_copy* c = copy_for(*k, g);
     if (!c) return fail(JJS_ERR_ARG, "the signer group has no copy on this device");
-    if (int rc = ensure_msig_scratch(n, n_transcripts, fmt != JJS_FORMAT_AFFINE ? n : 0)) return rc;
-    const uint8_t* pts[2] = {(const uint8_t*)R, (const uint8_t*)S};
-    msig_group_params G{};
-    msig_params& P = G.M;
-    P.z = (const uint8_t*)z; P.m = (const uint8_t*)m;
-    P.n_transcripts = (uint32_t)n_transcripts; P.n_total = n;
-    P.share_status = (uint8_t*)share_status; P.sig_u = (uint8_t*)sig_u; P.sig_R = (uint8_t*)sig_R;
-    P.transcript_status = (uint8_t*)transcript_status;
-    P.agg_pk = c->agg_pk;                                            // read only: the group's
-    const msig_scratch W = msig_scratch_carve();
-    P.e_pt = W.e_pt; P.a_words = W.a_words; P.c_words = W.c_words;
-    P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
-    G.participants = k->participants;
-    G.d_words = c->d_words; G.tables = c->tables; G.tag_a = c->tag_a + 9;
-    G.by_participant = n_transcripts >= MSIG_GROUP_BY_PARTICIPANT_FROM ? 1u : 0u;
-#if defined(JJS_PROFILING)
-    if (g_keep_order) G.by_participant = 0;                          // A/B of the lane mapping (jjs_debug_force_path 0x1000)
-#endif
+    msig_caps need;
+    need.rows = n; need.transcripts = n_transcripts;
+    if (fmt != JJS_FORMAT_AFFINE) need.ext_rows = n;
     ++k->calls;
-    big_slot();
-    if (int rc = begin_shared(s)) return rc;
-    const int rc_norm = msig_ingest(fmt, W, pts, 2, n, s);
-    P.R = pts[0]; P.S = pts[1];
-    for (int pass = 0; pass < 5 && !rc_norm; ++pass) {
-        if (pass == 3) {
-            hipLaunchKernelGGL(msig_group_share_kernel, dim3(grid_for(g->grid_msig, n)), dim3(BLOCK), 0, s, G);
-            continue;
+    return msig_scratch_call(need, s, [&](const msig_scratch& W) -> int {
+        const uint8_t* pts[2] = {(const uint8_t*)R, (const uint8_t*)S};
+        msig_group_params G{};
+        msig_params& P = G.M;
+        P.z = (const uint8_t*)z; P.m = (const uint8_t*)m;
+        P.n_transcripts = (uint32_t)n_transcripts; P.n_total = n;
+        P.share_status = (uint8_t*)share_status; P.sig_u = (uint8_t*)sig_u; P.sig_R = (uint8_t*)sig_R;
+        P.transcript_status = (uint8_t*)transcript_status;
+        P.agg_pk = c->agg_pk;                                            // read only: the group's
+        P.e_pt = W.e_pt; P.a_words = W.a_words; P.c_words = W.c_words;
+        P.comb_g = g->comb_g; P.lane_ws = g->slots[0].workspace;
+        msig_group_fill(G, *k, *c);
+        G.by_participant = n_transcripts >= MSIG_GROUP_BY_PARTICIPANT_FROM ? 1u : 0u;
+#if defined(JJS_PROFILING)
+        if (g_keep_order) G.by_participant = 0;                          // A/B of the lane mapping (jjs_debug_force_path 0x1000)
+#endif
+        if (int rc = msig_ingest(fmt, W, pts, 2, n, s)) return rc;
+        P.R = pts[0]; P.S = pts[1];
+        // msig_group_kernel's own schedule: pass 1 runs one lane per share, the others one per transcript; 0 and 2 have the hash chains
+        for (int pass = 0; pass < 5; ++pass) {
+            if (pass == 3) {
+                hipLaunchKernelGGL(msig_group_share_kernel, dim3(grid_for(g->grid_msig, n)), dim3(BLOCK), 0, s, G);
+                continue;
+            }
+            const size_t count = pass == 1 ? n : n_transcripts;
+            P.hash_lanes = (pass == 0 || pass == 2) ? msig_hash_lanes(count) : 1u;
+            hipLaunchKernelGGL(msig_group_kernel, dim3(grid_for(g->grid_msig, count * P.hash_lanes)), dim3(BLOCK), 0, s, G, pass);
         }
-        const size_t count = pass == 1 ? n : n_transcripts;
-        // a pass with a hash chain and few items: eight lanes per item (multisig_core.h hash_lanes)
-        P.hash_lanes = (pass == 0 || pass == 2) ? msig_hash_lanes(count) : 1u;
-        hipLaunchKernelGGL(msig_group_kernel, dim3(grid_for(g->grid_msig, count * P.hash_lanes)), dim3(BLOCK), 0, s, G, pass);
-    }
-    const hipError_t e = hipGetLastError();
-    const int rc2 = end_shared(s);              // the slot's event covers whatever was queued, also when a step failed
-    if (rc_norm) return rc_norm;
-    if (e != hipSuccess) return fail(JJS_ERR_HIP, "launching the signer-group passes: %s", hipGetErrorString(e));
-    return rc2;
+        HIP_TRY(hipGetLastError());
+        return JJS_OK;
+    });
 }
 
-int jjs_msig_group_combine_dev(jjs_msig_group h, const void* z, const void* R, const void* S, const void* m, size_t n_transcripts,
-                               void* share_status, void* transcript_status, void* sig_u, void* sig_R, void* stream) {
+// the three formats of jjs_msig_group_combine*_dev
+static int msig_group_combine_dev(jjs_msig_group h, int fmt, const void* z, const void* R, const void* S, const void* m, size_t n_transcripts,
+                                  void* share_status, void* transcript_status, void* sig_u, void* sig_R, void* stream) {
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
-    return msig_group_combine_locked(h, JJS_FORMAT_AFFINE, z, R, S, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, (hipStream_t)stream);
+    return msig_group_combine_locked(h, fmt, z, R, S, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, (hipStream_t)stream);
+}
+int jjs_msig_group_combine_dev(jjs_msig_group h, const void* z, const void* R, const void* S, const void* m, size_t n_transcripts,
+                               void* share_status, void* transcript_status, void* sig_u, void* sig_R, void* stream) {
+    return msig_group_combine_dev(h, JJS_FORMAT_AFFINE, z, R, S, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, stream);
 }
 int jjs_msig_group_combine_ext_dev(jjs_msig_group h, const void* z, const void* R_ext, const void* S_ext, const void* m, size_t n_transcripts,
                                    void* share_status, void* transcript_status, void* sig_u, void* sig_R, void* stream) {
-    std::lock_guard<std::mutex> lock(L.mu);
-    if (int rc = check_ready()) return rc;
-    return msig_group_combine_locked(h, JJS_FORMAT_EXT, z, R_ext, S_ext, m, n_transcripts, share_status, transcript_status, sig_u, sig_R,
-                                     (hipStream_t)stream);
+    return msig_group_combine_dev(h, JJS_FORMAT_EXT, z, R_ext, S_ext, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, stream);
 }
 int jjs_msig_group_combine_wire_dev(jjs_msig_group h, const void* z, const void* R_w, const void* S_w, const void* m, size_t n_transcripts,
                                     void* share_status, void* transcript_status, void* sig_u, void* sig_R, void* stream) {
-    std::lock_guard<std::mutex> lock(L.mu);
-    if (int rc = check_ready()) return rc;
-    return msig_group_combine_locked(h, JJS_FORMAT_WIRE, z, R_w, S_w, m, n_transcripts, share_status, transcript_status, sig_u, sig_R,
-                                     (hipStream_t)stream);
+    return msig_group_combine_dev(h, JJS_FORMAT_WIRE, z, R_w, S_w, m, n_transcripts, share_status, transcript_status, sig_u, sig_R, stream);
 }
 
 }  // extern "C"

@@ -21,48 +21,38 @@ static int msig_keyset_combine_locked(const keyset_entry& k, const keyset_copy& 
     if ((n && (!all_ok(z, R, S) || !key_idx || (reinterpret_cast<uintptr_t>(key_idx) & 3u))) || !all_ok(m, agg_pk, sig_u, sig_R) ||
         (n && !share_status))
         return fail(JJS_ERR_ARG, "null or misaligned pointer");
-    if (int rc = ensure_msig_scratch(n, n_transcripts, fmt != JJS_FORMAT_AFFINE ? n : 0, n ? n : 1, n_transcripts)) return rc;
-    const msig_scratch W = msig_scratch_carve();
-    const uint8_t* pts[2] = {(const uint8_t*)R, (const uint8_t*)S};
-    msig_keyset_params K{};
-    msig_params& P = K.M;
-    msig_params_common(P, W, n_transcripts, n);
-    P.z = (const uint8_t*)z; P.m = (const uint8_t*)m;
-    P.share_status = (uint8_t*)share_status; P.agg_pk = (uint8_t*)agg_pk; P.sig_u = (uint8_t*)sig_u; P.sig_R = (uint8_t*)sig_R;
-    P.transcript_status = (uint8_t*)transcript_status;
-    P.e_pt = W.e_pt;
-    P.PK = W.ks_pk;
-    K.key_idx = (const uint32_t*)key_idx; K.n_keys = k.n_keys;
-    K.keys = c.keys[0]; K.flags = c.flags[0]; K.tables = c.tables[0];
-    K.pk_col = W.ks_pk; K.row_key = W.ks_row_key; K.refused = W.ks_refused;
-    big_slot();
-    if (int rc = begin_shared(s)) return rc;
-    auto queue = [&]() -> int {
+    msig_caps need;
+    need.rows = n; need.transcripts = n_transcripts;
+    if (fmt != JJS_FORMAT_AFFINE) need.ext_rows = n;
+    need.ks_rows = n ? n : 1; need.ks_transcripts = n_transcripts;
+    return msig_scratch_call(need, s, [&](const msig_scratch& W) -> int {
+        const uint8_t* pts[2] = {(const uint8_t*)R, (const uint8_t*)S};
+        msig_keyset_params K{};
+        msig_params& P = K.M;
+        msig_params_common(P, W, n_transcripts, n);
+        P.z = (const uint8_t*)z; P.m = (const uint8_t*)m;
+        P.share_status = (uint8_t*)share_status; P.agg_pk = (uint8_t*)agg_pk; P.sig_u = (uint8_t*)sig_u; P.sig_R = (uint8_t*)sig_R;
+        P.transcript_status = (uint8_t*)transcript_status;
+        P.e_pt = W.e_pt;
+        P.PK = W.ks_pk;
+        msig_keyset_fill(K, k, c, key_idx, W, W.ks_refused);
         HIP_TRY(hipMemcpyAsync(W.offsets, offsets_host, (n_transcripts + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(W.ks_refused, 0, n_transcripts * sizeof(uint32_t), s));
         if (int rc = msig_ingest(fmt, W, pts, 2, n, s)) return rc;
         P.R = pts[0]; P.S = pts[1];
         const dim3 per_share(grid_for(g->grid_msig, n)), per_transcript(grid_for(g->grid_msig, n_transcripts));
-        for (int pass = 0; pass < 7; ++pass) {
-            const size_t count = (pass == 0 || pass == 2 || pass == 4 || pass == 6) ? n_transcripts : n;
-            // a pass with a hash chain and few items: eight lanes per item (multisig_core.h hash_lanes)
-            P.hash_lanes = (pass == 1 || pass == 2 || pass == 4) ? msig_hash_lanes(count) : 1u;
-            if (pass == 1) {
-                hipLaunchKernelGGL(msig_keyset_delin_kernel, dim3(grid_for(g->grid_msig, n * P.hash_lanes)), dim3(BLOCK), 0, s, K);
-            } else if (pass == 5) {
-                hipLaunchKernelGGL(msig_keyset_share_kernel, per_share, dim3(BLOCK), 0, s, K);
-            } else {
-                hipLaunchKernelGGL(msig_kernel, dim3(grid_for(g->grid_msig, count * P.hash_lanes)), dim3(BLOCK), 0, s, P, pass);
-            }
-            if (pass == 0) hipLaunchKernelGGL(msig_keyset_gather_kernel, per_share, dim3(BLOCK), 0, s, K);   // behind the map: it reads tr_of
-        }
+        launch_msig_pass(P, 0, s);
+        hipLaunchKernelGGL(msig_keyset_gather_kernel, per_share, dim3(BLOCK), 0, s, K);   // behind the map: it reads tr_of
+        const dim3 delin(msig_pass_grid(P, 1));
+        hipLaunchKernelGGL(msig_keyset_delin_kernel, delin, dim3(BLOCK), 0, s, K);        // pass 1 over the set's tables
+        for (int pass = 2; pass < 5; ++pass) launch_msig_pass(P, pass, s);
+        const dim3 shares(msig_pass_grid(P, 5));
+        hipLaunchKernelGGL(msig_keyset_share_kernel, shares, dim3(BLOCK), 0, s, K);       // pass 5 over the set's tables
+        launch_msig_pass(P, 6, s);
         hipLaunchKernelGGL(msig_keyset_refuse_kernel, per_transcript, dim3(BLOCK), 0, s, K);
         HIP_TRY(hipGetLastError());
         return JJS_OK;
-    };
-    const int rc = queue();
-    const int rc2 = end_shared(s);              // the slot's event covers whatever was queued, also when a step failed
-    return rc ? rc : rc2;
+    });
 }
 
 static int msig_keyset_combine_dev(jjs_keyset ks, int format, unsigned formats, const void* key_idx, const void* z, const void* R, const void* S, const void* m,

@@ -46,65 +46,61 @@ static int msig_share_locked(const msh_call& A, hipStream_t st) {
         if (int rc = msig_keyset_find(A.handle, g, ks, kc)) return rc;
     }
     const bool keyset = A.route == MSH_KEYSET;
-    if (int rc = ensure_msig_scratch(n, B, A.fmt != JJS_FORMAT_AFFINE ? n : 0, keyset ? (n ? n : 1) : 0, keyset ? B : 0, 0, 0, Q ? Q : 1, B)) return rc;
-    const msig_scratch W = msig_scratch_carve();
-    const uint8_t* pts[3] = {(const uint8_t*)A.keys, (const uint8_t*)A.R, (const uint8_t*)A.S};
-    const uint32_t n_pts = A.route == MSH_INLINE ? 3u : 2u;
-    const uint8_t** cols = A.route == MSH_INLINE ? pts : pts + 1;
-    msig_share_params X{};
-    msig_params& P = X.M;
-    msig_params_common(P, W, B, n);
-    P.m = (const uint8_t*)A.m;
-    P.sig_R = A.sig_R ? (uint8_t*)A.sig_R : W.share_rsa;
-    P.agg_pk = A.route == MSH_GROUP ? gc->agg_pk : W.share_agg;
-    P.e_pt = W.share_pt;
-    P.hash_lanes = 1;
-    X.q_transcript = (const uint32_t*)A.qt; X.q_slot = (const uint32_t*)A.qs; X.q_z = (const uint8_t*)A.z;
-    X.n_queries = Q; X.q_status = (uint8_t*)A.status;
-    X.bad = W.share_bad;
-    X.check_pk = A.route == MSH_INLINE ? 1u : 0u;
-    X.d_words = W.d_words;
-    if (A.route == MSH_GROUP) {
-        X.participants = grp->participants;
-        X.d_words = gc->d_words; X.tables = gc->tables; X.tag_a = gc->tag_a + 9;
-        ++grp->calls;
-    } else if (keyset) {
-        X.tables = kc->tables[0]; X.row_key = W.ks_row_key;
-    }
-    big_slot();
-    if (int rc = begin_shared(st)) return rc;
-    auto queue = [&]() -> int {
+    msig_caps need;
+    need.rows = n; need.transcripts = B;
+    if (A.fmt != JJS_FORMAT_AFFINE) need.ext_rows = n;
+    if (keyset) { need.ks_rows = n ? n : 1; need.ks_transcripts = B; }
+    need.share_queries = Q ? Q : 1; need.share_transcripts = B;
+    if (grp) ++grp->calls;
+    return msig_scratch_call(need, st, [&](const msig_scratch& W) -> int {
+        const uint8_t* pts[3] = {(const uint8_t*)A.keys, (const uint8_t*)A.R, (const uint8_t*)A.S};
+        const uint32_t n_pts = A.route == MSH_INLINE ? 3u : 2u;
+        const uint8_t** cols = A.route == MSH_INLINE ? pts : pts + 1;
+        msig_share_params X{};
+        msig_params& P = X.M;
+        msig_params_common(P, W, B, n);
+        P.m = (const uint8_t*)A.m;
+        P.sig_R = A.sig_R ? (uint8_t*)A.sig_R : W.share_rsa;
+        P.agg_pk = A.route == MSH_GROUP ? gc->agg_pk : W.share_agg;
+        P.e_pt = W.share_pt;
+        X.q_transcript = (const uint32_t*)A.qt; X.q_slot = (const uint32_t*)A.qs; X.q_z = (const uint8_t*)A.z;
+        X.n_queries = Q; X.q_status = (uint8_t*)A.status;
+        X.bad = W.share_bad;
+        X.check_pk = A.route == MSH_INLINE ? 1u : 0u;
+        X.d_words = W.d_words;
+        if (A.route == MSH_GROUP) {
+            msig_group_fill(X, *grp, *gc);
+        } else if (keyset) {
+            X.tables = kc->tables[0]; X.row_key = W.ks_row_key;
+        }
         if (A.route != MSH_GROUP) HIP_TRY(hipMemcpyAsync(W.offsets, A.offsets_host, (B + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(W.share_bad, 0, B * sizeof(uint32_t), st));
         if (int rc = msig_ingest(A.fmt, W, cols, n_pts, n, st)) return rc;
         P.R = pts[1]; P.S = pts[2];
         P.PK = keyset ? W.ks_pk : pts[0];
-        const dim3 per_row(grid_for(g->grid_msig, n)), per_transcript(grid_for(g->grid_msig, B));
-        const uint32_t hl_rows = msig_hash_lanes(n), hl_transcripts = msig_hash_lanes(B);
+        const dim3 per_row(grid_for(g->grid_msig, n));
+        const uint32_t hl_transcripts = msig_hash_lanes(B);
         // the front of the route's combine call: a_words, and for ragged transcripts the map, d_words and pk_agg
         if (A.route == MSH_GROUP) {
             msig_group_params G{};
             G.M = P; G.M.hash_lanes = hl_transcripts;
-            G.participants = X.participants; G.d_words = X.d_words; G.tables = X.tables; G.tag_a = X.tag_a;
+            msig_group_fill(G, *grp, *gc);
             hipLaunchKernelGGL(msig_group_kernel, dim3(grid_for(g->grid_msig, B * hl_transcripts)), dim3(BLOCK), 0, st, G, 0);
         } else {
-            hipLaunchKernelGGL(msig_kernel, per_transcript, dim3(BLOCK), 0, st, P, 0);
+            launch_msig_pass(P, 0, st);
             if (keyset) {
                 msig_keyset_params K{};
-                K.M = P; K.M.hash_lanes = hl_rows;
-                K.key_idx = (const uint32_t*)A.keys; K.n_keys = ks->n_keys;
-                K.keys = kc->keys[0]; K.flags = kc->flags[0]; K.tables = kc->tables[0];
-                K.pk_col = W.ks_pk; K.row_key = W.ks_row_key; K.refused = W.share_bad;      // the gather flags the transcript itself
+                K.M = P;
+                msig_keyset_fill(K, *ks, *kc, A.keys, W, W.share_bad);                           // the gather flags the transcript itself
+                const dim3 delin(msig_pass_grid(K.M, 1));                                        // (the gather, too, sees pass 1's hash_lanes)
                 if (n) {
                     hipLaunchKernelGGL(msig_keyset_gather_kernel, per_row, dim3(BLOCK), 0, st, K);
-                    hipLaunchKernelGGL(msig_keyset_delin_kernel, dim3(grid_for(g->grid_msig, n * hl_rows)), dim3(BLOCK), 0, st, K);
+                    hipLaunchKernelGGL(msig_keyset_delin_kernel, delin, dim3(BLOCK), 0, st, K);
                 }
             } else if (n) {
-                P.hash_lanes = hl_rows;
-                hipLaunchKernelGGL(msig_kernel, dim3(grid_for(g->grid_msig, n * hl_rows)), dim3(BLOCK), 0, st, P, 1);
+                launch_msig_pass(P, 1, st);
             }
-            P.hash_lanes = hl_transcripts;
-            hipLaunchKernelGGL(msig_kernel, dim3(grid_for(g->grid_msig, B * hl_transcripts)), dim3(BLOCK), 0, st, P, 2);
+            launch_msig_pass(P, 2, st);
         }
         P.hash_lanes = 1;
         if (n) hipLaunchKernelGGL(msig_share_check_kernel, per_row, dim3(BLOCK), 0, st, X);          // behind the map: it reads tr_of
@@ -119,10 +115,7 @@ static int msig_share_locked(const msh_call& A, hipStream_t st) {
         }
         HIP_TRY(hipGetLastError());
         return JJS_OK;
-    };
-    const int rc = queue();
-    const int rc2 = end_shared(st);             // the slot's event covers whatever was queued, also when a step failed
-    return rc ? rc : rc2;
+    });
 }
 // what every form looks at first (under the engine's mutex, behind check_ready): JJS_OK with go = false: nothing to do
 static int msh_enter(msh_call& A, int format, bool& go) {

@@ -21,50 +21,40 @@ static int msig_sign_locked(const ms_call& A, const uint32_t* offsets_host, size
     if ((n && !all_ok(A.PK, A.R, A.S)) || !all_ok(A.m, A.sk, A.r, A.s, A.z_out) || !A.status || (reinterpret_cast<uintptr_t>(A.signer_row) & 3u))
         return fail(JJS_ERR_ARG, "null or misaligned pointer");
     const size_t B = n_transcripts;
-    if (int rc = ensure_msig_scratch(n, B, A.ext ? n : 0, 0, 0, n ? n : 1, B)) return rc;
-    const msig_scratch W = msig_scratch_carve();
-    const uint8_t* pts[3] = {(const uint8_t*)A.PK, (const uint8_t*)A.R, (const uint8_t*)A.S};
-    msig_sign_params G{};
-    msig_params& P = G.M;
-    msig_params_common(P, W, B, n);
-    P.m = (const uint8_t*)A.m;
-    P.agg_pk = W.sign_agg; P.sig_R = W.sign_rsa;
-    P.e_pt = W.e_pt;
-    P.hash_lanes = 1;
-    G.pk_repeats = W.sign_flags; G.bad_enc = W.sign_flags + g->msig_sign_rows; G.dup_nonce = G.bad_enc + g->msig_sign_transcripts;
-    G.signer_row = (const uint32_t*)A.signer_row;
-    G.sk = (const uint8_t*)A.sk; G.r = (const uint8_t*)A.r; G.s = (const uint8_t*)A.s;
-    G.n_signing = A.n_signing;
-    G.z_out = (uint8_t*)A.z_out; G.status = (uint8_t*)A.status;
-    big_slot();
-    if (int rc = begin_shared(st)) return rc;
-    auto queue = [&]() -> int {
+    msig_caps need;
+    need.rows = n; need.transcripts = B;
+    if (A.ext) need.ext_rows = n;
+    need.sign_rows = n ? n : 1; need.sign_transcripts = B;
+    return msig_scratch_call(need, st, [&](const msig_scratch& W) -> int {
+        const uint8_t* pts[3] = {(const uint8_t*)A.PK, (const uint8_t*)A.R, (const uint8_t*)A.S};
+        msig_sign_params G{};
+        msig_params& P = G.M;
+        msig_params_common(P, W, B, n);
+        P.m = (const uint8_t*)A.m;
+        P.agg_pk = W.sign_agg; P.sig_R = W.sign_rsa;
+        P.e_pt = W.e_pt;
+        G.pk_repeats = W.pk_repeats; G.bad_enc = W.bad_enc; G.dup_nonce = W.dup_nonce;
+        G.signer_row = (const uint32_t*)A.signer_row;
+        G.sk = (const uint8_t*)A.sk; G.r = (const uint8_t*)A.r; G.s = (const uint8_t*)A.s;
+        G.n_signing = A.n_signing;
+        G.z_out = (uint8_t*)A.z_out; G.status = (uint8_t*)A.status;
         HIP_TRY(hipMemcpyAsync(W.offsets, offsets_host, (B + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(W.sign_flags, 0, (g->msig_sign_rows + 2 * g->msig_sign_transcripts) * sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetAsync(W.pk_repeats, 0, W.sign_flag_words * sizeof(uint32_t), st));
         if (A.ext && n)
             if (int rc = msig_normalize(W, pts, 3, n, st)) return rc;
         P.PK = pts[0]; P.R = pts[1]; P.S = pts[2];
-        const dim3 per_row(grid_for(g->grid_msig, n)), per_transcript(grid_for(g->grid_msig, B));
-        hipLaunchKernelGGL(msig_kernel, per_transcript, dim3(BLOCK), 0, st, P, 0);
+        launch_msig_pass(P, 0, st);
         if (n) {
-            hipLaunchKernelGGL(msig_sign_check_kernel, per_row, dim3(BLOCK), 0, st, G);       // behind the map: it reads tr_of
-            for (int pass = 1; pass < 5; ++pass) {
-                const size_t count = (pass == 2 || pass == 4) ? B : n;
-                // a pass with a hash chain and few items: eight lanes per item (multisig_core.h hash_lanes)
-                P.hash_lanes = pass != 3 ? msig_hash_lanes(count) : 1u;
-                const dim3 grid(grid_for(g->grid_msig, count * P.hash_lanes));
-                if (pass < 4) hipLaunchKernelGGL(msig_kernel, grid, dim3(BLOCK), 0, st, P, pass);
-                else hipLaunchKernelGGL(msig_sign_final_kernel, grid, dim3(BLOCK), 0, st, P);
-            }
+            hipLaunchKernelGGL(msig_sign_check_kernel, dim3(grid_for(g->grid_msig, n)), dim3(BLOCK), 0, st, G);   // behind the map: it reads tr_of
+            for (int pass = 1; pass < 4; ++pass) launch_msig_pass(P, pass, st);
+            const dim3 closing(msig_pass_grid(P, 4));
+            hipLaunchKernelGGL(msig_sign_final_kernel, closing, dim3(BLOCK), 0, st, P);           // pass 4 without a column of shares
             P.hash_lanes = 1;
         }
         hipLaunchKernelGGL(msig_sign_share_kernel, dim3(grid_for(g->grid_msig, A.n_signing)), dim3(BLOCK), 0, st, G);
         HIP_TRY(hipGetLastError());
         return JJS_OK;
-    };
-    const int rc = queue();
-    const int rc2 = end_shared(st);             // the slot's event covers whatever was queued, also when a step failed
-    return rc ? rc : rc2;
+    });
 }
 }  // extern "C++"
 

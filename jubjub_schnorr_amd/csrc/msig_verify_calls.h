@@ -48,28 +48,23 @@ static int msig_verify_locked(const mv_call& A, const uint32_t* offsets_host, si
         return fail(JJS_ERR_ARG, "null or misaligned pointer");
     const size_t B = n_transcripts;
     const bool ingest = A.fmt != JJS_FORMAT_AFFINE, wire = A.fmt == JJS_FORMAT_WIRE;
-    const size_t ext_rows = !ingest ? 0 : (A.keyset ? (A.verify ? B : 0) : (A.verify && B > n ? B : n));
-    if (int rc = A.keyset ? ensure_msig_scratch(n, B, ext_rows, n ? n : 1, B) : ensure_msig_scratch(n, B, ext_rows)) return rc;
-    const msig_scratch W = msig_scratch_carve();
-    msig_verify_keyset_params VK{};
-    msig_params& P = VK.K.M;
-    msig_params_common(P, W, B, n, false);
-    P.agg_pk = (uint8_t*)A.agg_pk;
-    P.hash_lanes = 1;
-    VK.vec_status = (uint8_t*)A.vec_status; VK.poison = A.verify ? 1u : 0u;
-    if (A.keyset) {
-        msig_keyset_params& K = VK.K;
-        P.PK = W.ks_pk;
-        K.key_idx = (const uint32_t*)A.keys; K.n_keys = A.k->n_keys;
-        K.keys = A.c->keys[0]; K.flags = A.c->flags[0]; K.tables = A.c->tables[0];
-        K.pk_col = W.ks_pk; K.row_key = W.ks_row_key; K.refused = W.ks_refused;
-    } else {
-        VK.K.refused = W.a_words;          // the inline form: a verifier's call computes no `a`, its words hold the refused flags
-    }
-    const uint8_t *pk = A.keyset ? nullptr : (const uint8_t*)A.keys, *r = (const uint8_t*)A.R, *u = (const uint8_t*)A.u;
-    big_slot();
-    if (int rc = begin_shared(s)) return rc;
-    auto queue = [&]() -> int {
+    msig_caps need;
+    need.rows = n; need.transcripts = B;
+    if (ingest) need.ext_rows = A.keyset ? (A.verify ? B : 0) : (A.verify && B > n ? B : n);
+    if (A.keyset) { need.ks_rows = n ? n : 1; need.ks_transcripts = B; }
+    return msig_scratch_call(need, s, [&](const msig_scratch& W) -> int {
+        msig_verify_keyset_params VK{};
+        msig_params& P = VK.K.M;
+        msig_params_common(P, W, B, n, false);
+        P.agg_pk = (uint8_t*)A.agg_pk;
+        VK.vec_status = (uint8_t*)A.vec_status; VK.poison = A.verify ? 1u : 0u;
+        if (A.keyset) {
+            P.PK = W.ks_pk;
+            msig_keyset_fill(VK.K, *A.k, *A.c, A.keys, W, W.ks_refused);
+        } else {
+            VK.K.refused = W.a_words;          // the inline form: a verifier's call computes no `a`, its words hold the refused flags
+        }
+        const uint8_t *pk = A.keyset ? nullptr : (const uint8_t*)A.keys, *r = (const uint8_t*)A.R, *u = (const uint8_t*)A.u;
         HIP_TRY(hipMemcpyAsync(W.offsets, offsets_host, (B + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(VK.K.refused, 0, B * sizeof(uint32_t), s));
         if (ingest && !A.keyset)
@@ -83,23 +78,24 @@ static int msig_verify_locked(const mv_call& A, const uint32_t* offsets_host, si
         }
         if (!A.keyset) P.PK = pk;
         const dim3 per_row(grid_for(g->grid_msig, n)), per_vector(grid_for(g->grid_msig, B));
-        hipLaunchKernelGGL(msig_kernel, per_vector, dim3(BLOCK), 0, s, P, 0);
+        launch_msig_pass(P, 0, s);
         if (n) {
-            // behind the map: both read tr_of
-            if (A.keyset) hipLaunchKernelGGL(msig_keyset_gather_kernel, per_row, dim3(BLOCK), 0, s, VK.K);
-            else hipLaunchKernelGGL(msig_verify_check_kernel, per_row, dim3(BLOCK), 0, s, mv_of(VK));
-            // the hash pass: eight lanes per row when the call has few (multisig_core.h hash_lanes)
-            P.hash_lanes = msig_hash_lanes(n);
-            const dim3 hashing(grid_for(g->grid_msig, n * P.hash_lanes));
-            if (A.keyset) hipLaunchKernelGGL(msig_keyset_delin_kernel, hashing, dim3(BLOCK), 0, s, VK.K);
-            else hipLaunchKernelGGL(msig_kernel, hashing, dim3(BLOCK), 0, s, P, 1);
+            // the gather or the check, behind the map (both read tr_of), then pass 1
+            if (A.keyset) {
+                hipLaunchKernelGGL(msig_keyset_gather_kernel, per_row, dim3(BLOCK), 0, s, VK.K);
+                const dim3 delin(msig_pass_grid(P, 1));
+                hipLaunchKernelGGL(msig_keyset_delin_kernel, delin, dim3(BLOCK), 0, s, VK.K);
+            } else {
+                hipLaunchKernelGGL(msig_verify_check_kernel, per_row, dim3(BLOCK), 0, s, mv_of(VK));
+                launch_msig_pass(P, 1, s);
+            }
             P.hash_lanes = 1;
         }
         hipLaunchKernelGGL(msig_verify_sum_kernel, per_vector, dim3(BLOCK), 0, s, mv_of(VK));
         HIP_TRY(hipGetLastError());
         if (!A.verify) return JJS_OK;
-        // the verification stage: the resident single-scheme affine call on (u, R, agg_pk, m), in a slot of its own (build_call
-        // moves sl), on the same stream, under this hold of the mutex
+        // The verification stage: the resident single-scheme affine call on (u, R, agg_pk, m), in a slot of its own (build_call moves
+        // sl; the frame puts it back), on the same stream, under this hold of the mutex.
         const void* d[4] = {u, r, A.agg_pk, A.m};
         staged_call C;
         if (int rc = build_call(SHAPES[JJS_SCHEME_SINGLE][JJS_FORMAT_AFFINE], d, B, A.status, A.tally, s, C)) return rc;
@@ -107,11 +103,7 @@ static int msig_verify_locked(const mv_call& A, const uint32_t* offsets_host, si
         hipLaunchKernelGGL(msig_verify_clear_kernel, per_vector, dim3(BLOCK), 0, s, mv_of(VK));
         HIP_TRY(hipGetLastError());
         return JJS_OK;
-    };
-    const int rc = queue();
-    sl = &g->slots[0];                          // the scratch's slot again: its event covers the verification and the clear pass,
-    const int rc2 = end_shared(s);              // and whatever was queued when a step failed
-    return rc ? rc : rc2;
+    });
 }
 
 // a _dev entry point: the checks in front of the call, under the engine's mutex
