@@ -1072,6 +1072,52 @@ int jjs_public_keys_fixed(int scheme, const uint8_t* sk, size_t n, uint8_t* PK_o
  * serves (UINT64_MAX: none).  Negative return: an error code. */
 int jjs_debug_sign_fixed_limits(uint64_t out[2]);
 
+/* ---- Poseidon digests of ragged inputs (csrc/digest.h) ----
+ * What a caller who holds payloads calls before the first verify, sign or multisig call: out[i] is
+ * dusk_poseidon::Hash::digest(Domain::Other, &item_i)[0] and, with JJS_DIGEST_TRUNCATED in flags, Hash::digest_truncated
+ * (the low 250 bits) -- 32 bytes, canonical, little endian: the `m` column of every other call as it stands.  It equals
+ * oracle/jjs_oracle.py poseidon_digest(item i) bit for bit.
+ * Input: `in` is ONE column of elements, the items back to back.  offsets_host == NULL: every item has k elements.  Otherwise
+ * offsets_host holds n + 1 words in HOST memory that start at 0 and never decrease, item i is elements [offsets[i],
+ * offsets[i + 1]) and k is ignored (the convention of the multisignature calls); the words are read before the call returns.
+ * format: JJS_DIGEST_CANONICAL, elements of 32 bytes little endian, each < q; JJS_DIGEST_WIDE, elements of 64 bytes little
+ * endian reduced mod q (BlsScalar::from_bytes_wide, the reference's own way from bytes to a field element, src/nonce.rs:98-99).
+ * status: nullable, n bytes, any alignment.  0, or 3 when a canonical-format element of the item is >= q; such an item gets a
+ * zero row, with or without a status column, and touches no other item.  The wide format never gives 3.
+ * -1: a format other than the two, a flag bit other than bit 0, a NULL `in` or `out`, a misaligned device pointer, offsets that
+ * do not start at 0 or that decrease, an item of no elements (k == 0 too: no vector of the reference pins the empty absorb), an
+ * item of more than 2^31 - 1 elements (the SAFE tag encodes 0x80000000 | length), more than 2^32 - 1 items.  -4 before
+ * jjs_init, before any argument is looked at.  n == 0 returns 0 and writes nothing.  `out` must not overlap `in`.
+ * _dev: device pointers, 16-byte aligned (status: any alignment), asynchronous on `stream`.  A uniform call uploads nothing; a
+ * ragged call uploads its offsets and an order of its items into grow-only scratch and is ordered with the signing calls as they
+ * order themselves.  No call allocates once that scratch has reached its shape; jjs_trim frees it.  The host form is blocking,
+ * asks no alignment and takes the route of jjs_multisig_sign, one such call at a time per device.
+ * Two routes, chosen by n alone: up to the limit jjs_debug_digest_limits reports, eight lanes share an item's permutations
+ * (the latency route); beyond, an item has one lane (the throughput route), and the lanes of a ragged call take the items by
+ * their count of sponge blocks, longest first, so that a wave's lanes end together.  Both give the same bytes.  Lengths up to
+ * 1 027 take their SAFE tag from a table; a longer item's tag is computed on the device, once per item.
+ * Rates (profiles/r22_digest.jsonl, the record of tools/digest_rate.py: one MI355X, resident inputs, 5 rounds, medians, every side in
+ * a process of its own, this commit's library and the parent's alternating; ms per call).  k = 5 truncated against the parent's
+ * jjs_challenge_single_dev: 0.271 against 0.485 at one item and 0.276 / 0.461 at 1 024 (0.56-0.60x: the eight-lane route), 0.506 /
+ * 0.515 at 2^16, 5.79 / 5.73 at 2^20 (1.01x, spreads 0.21 and 0.23; 181 M digests/s).  k = 16 against the parent's
+ * jjs_debug_poseidon_dev: 0.533 / 0.976 at one item, 0.526 / 0.900 at 1 024, 0.923 / 0.938 at 2^16, 10.99 / 10.10 at 2^20 (1.09x,
+ * beyond the spreads of 0.06: the canonical one-lane kernel holds three waves per SIMD where that kernel holds four; 95 M digests/s).
+ * Routes forced in turn: eight lanes 0.55-0.66x of one lane up to 8 192 items, level at 16 384, 1.7-4.2x from 32 768 on.  2^18 ragged
+ * items of 1-131 elements: 15.2 ms with the order against 25.0 in input order (0.61x); with one item of 1 031 among them 66 against
+ * 70 ms (spreads 8-11): that item's 258 permutations on one lane outlast the rest of the call either way.  oracle poseidon_any on 16
+ * threads: 6.6 s for 2^20 items of 5, 13.1 s for 2^20 of 16 (1 100x the call).
+ */
+#define JJS_DIGEST_CANONICAL 0   /* elements n_el x 32 B little endian, each < q              */
+#define JJS_DIGEST_WIDE      1   /* elements n_el x 64 B little endian, reduced mod q         */
+#define JJS_DIGEST_TRUNCATED 1   /* flags bit 0: keep the low 250 bits (digest_truncated)     */
+int jjs_digest_dev(int format, int flags, const void* in, const uint32_t* offsets_host, size_t k, size_t n,
+                   void* out, void* status, void* stream);
+int jjs_digest(int format, int flags, const uint8_t* in, const uint32_t* offsets, size_t k, size_t n,
+               uint8_t* out, uint8_t* status);
+/* [0] the largest n the eight-lanes-per-item route serves, [1] the lanes of the one-lane-per-item kernel's grid on the current
+ * device (a call of more items takes a second trip through its grid-stride loop).  Negative return: an error code. */
+int jjs_debug_digest_limits(uint64_t out[2]);
+
 /* ---- primitives exposed for parity tests ------------------------------------------------------ */
 /* out[i] = a[i] * b[i] mod q (canonical bytes in and out) */
 int jjs_debug_fq_mul_dev(const void* a, const void* b, size_t n, void* out, void* stream);

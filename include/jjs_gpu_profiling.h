@@ -28,7 +28,8 @@ int jjs_debug_skip_phases(unsigned mask);
  * any size, 0x4000 = the per-item path and its tally at any size, plus (w << 16) = the MSM's window width w (8-16; 0 by
  * size); for jjs_sign_vargen_pt* with one generator for the call: 0x8000 = the shared-generator route at any n,
  * 0x200000 = the per-item route at any n; for jjs_sign_fixed* with one key for the call (n_sk == 1): 0x400000 = the keyed
- * route at any n, 0x800000 = the per-item route at any n. */
+ * route at any n, 0x800000 = the per-item route at any n; for jjs_digest*: 0x1000000 = eight lanes per item at any n,
+ * 0x2000000 = one lane per item at any n, 0x4000000 = the lanes of a ragged call take the items in input order. */
 int jjs_debug_force_path(int which);
 /* Test mode for boxes with one GPU: a later jjs_init(k) with k above the visible device count creates k logical
  * devices (own stream, tables, workspace, staging each) that share the visible cards round-robin; the tallies are

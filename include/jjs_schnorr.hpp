@@ -1421,4 +1421,40 @@ class SignerGroup {
 };
 }  // namespace multisig
 
+// ---- Poseidon digests (include/jjs_gpu.h jjs_digest) ----
+// `dusk_poseidon::Hash::digest(Domain::Other, &payload)[0]` and `Hash::digest_truncated(Domain::Other, &payload)[0]` over the
+// header's BlsScalar: how a caller who holds payloads makes the `message` of every verify and sign call above.  Blocking host-buffer
+// calls.  An empty payload is refused (EngineError: the engine defines no digest of no elements); a scalar >= q -- bytes
+// `BlsScalar::from_bytes` refuses -- gives nullopt.
+namespace poseidon {
+// one digest per payload, in one call; nullopt for a payload with a non-canonical scalar
+inline std::vector<std::optional<BlsScalar>> digest_batch(const std::vector<std::vector<BlsScalar>>& payloads, bool truncated = false) {
+    const size_t n = payloads.size();
+    std::vector<uint32_t> offsets(n + 1, 0);
+    size_t total = 0;
+    for (size_t i = 0; i < n; ++i) {
+        total += payloads[i].size();
+        if (total > 0xffffffffull) throw std::length_error("jjs::poseidon::digest_batch: more than 2^32 - 1 scalars");
+        offsets[i + 1] = static_cast<uint32_t>(total);
+    }
+    detail::Soa in(total, 32), out(n, 32);
+    for (size_t i = 0, e = 0; i < n; ++i)
+        for (const BlsScalar& x : payloads[i]) in.put(e++, 0, x);
+    std::vector<uint8_t> status(n);
+    const int rc = jjs_digest(JJS_DIGEST_CANONICAL, truncated ? JJS_DIGEST_TRUNCATED : 0, in.data(), offsets.data(), 0, n, out.data(), status.data());
+    if (rc != JJS_OK) throw EngineError(rc, "jjs_digest");
+    std::vector<std::optional<BlsScalar>> digests(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (status[i] != JJS_STATUS_OK) continue;
+        BlsScalar d;
+        std::memcpy(d.data(), out.data() + 32 * i, 32);
+        digests[i] = d;
+    }
+    return digests;
+}
+inline std::optional<BlsScalar> digest(const std::vector<BlsScalar>& payload) { return digest_batch({payload}, false)[0]; }
+// the low 250 bits: a JubJubScalar
+inline std::optional<JubJubScalar> digest_truncated(const std::vector<BlsScalar>& payload) { return digest_batch({payload}, true)[0]; }
+}  // namespace poseidon
+
 }  // namespace jjs

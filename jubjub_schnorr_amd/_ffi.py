@@ -141,6 +141,9 @@ SIGNATURES = {
     "jjs_public_keys_fixed_dev": [_I, _P, _Z, _P, _P, _P, _P, _P],
     "jjs_public_keys_fixed": [_I, _P, _Z, _P, _P, _P, _P],
     "jjs_debug_sign_fixed_limits": [_P],
+    "jjs_digest_dev": [_I, _I, _P, _P, _Z, _Z, _P, _P, _P],
+    "jjs_digest": [_I, _I, _P, _P, _Z, _Z, _P, _P],
+    "jjs_debug_digest_limits": [_P],
     "jjs_verify_all_single": [_P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_double": [_P, _P, _P, _P, _P, _P, _Z, _P, _P],
     "jjs_verify_all_vargen": [_P, _P, _P, _P, _P, _Z, _P, _P],

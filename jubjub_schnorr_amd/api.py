@@ -252,6 +252,67 @@ class Engine:
         the canonical affine points."""
         return self._points_check("signatures", scheme, cols, fmt, want_points)
 
+    _DIGEST_FORMATS = {"canonical": (0, 32), "wide": (1, 64)}
+
+    def digest(self, inputs, lengths=None, *, truncated: bool = False, fmt: str = "canonical"):
+        """`Hash::digest(Domain::Other, &item)[0]` of n items (`digest_truncated` with `truncated`): jjs_digest(_dev).  fmt:
+        "canonical", elements of 32 bytes little endian below q, or "wide", elements of 64 bytes reduced mod q
+        (`BlsScalar::from_bytes_wide`).  inputs: the elements of every item back to back, (n_el, w); `lengths` is then the length
+        of every item (an int) or one length per item (a sequence: a ragged call).  With lengths=None the inputs are (n, k, w): n
+        items of k elements.  Returns (digests (n, 32), status (n,)): status 3 and a zero row for an item with a canonical element
+        >= q, else 0.  The digests are the `m` column of every verify, sign and multisig call.  Torch CUDA tensors: asynchronous
+        on the current stream; numpy arrays or bytes: blocking."""
+        if fmt not in self._DIGEST_FORMATS:
+            raise ValueError(f"fmt {fmt!r}: canonical or wide")
+        fid, w = self._DIGEST_FORMATS[fmt]
+        dev = _is_torch(inputs)
+        if isinstance(inputs, (bytes, bytearray, memoryview)):
+            inputs = np.frombuffer(inputs, np.uint8).reshape(-1, w)
+        if not dev:
+            inputs = np.ascontiguousarray(inputs, dtype=np.uint8)
+        offsets, k = None, 0
+        if lengths is None:
+            if len(inputs.shape) != 3 or inputs.shape[2] != w:
+                raise ValueError(f"expected shape (n, k, {w}) when lengths is None, got {tuple(inputs.shape)}")
+            n, k = int(inputs.shape[0]), int(inputs.shape[1])
+        else:
+            if len(inputs.shape) != 2 or inputs.shape[1] != w:
+                raise ValueError(f"expected shape (n_el, {w}), got {tuple(inputs.shape)}")
+            if np.ndim(lengths) == 0:
+                k = int(lengths)
+                if k < 1 or inputs.shape[0] % k:
+                    raise ValueError(f"{inputs.shape[0]} elements are no whole number of items of {k}")
+                n = int(inputs.shape[0]) // k
+            else:
+                lens = np.asarray(lengths, dtype=np.int64)
+                n = len(lens)
+                if n and (lens.min() < 1 or int(lens.sum()) != inputs.shape[0] or int(lens.sum()) >= 2**32):
+                    raise ValueError("lengths: at least 1 each, and their sum the number of elements")
+                offsets = np.zeros(n + 1, np.uint32)
+                np.cumsum(lens, out=offsets[1:], dtype=np.uint32)
+        off_p = offsets.ctypes.data_as(ctypes.c_void_p) if offsets is not None else None
+        flags = 1 if truncated else 0
+        if not dev:
+            out, status = np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+            _ffi.check(self._lib.jjs_digest(fid, flags, inputs.ctypes.data_as(ctypes.c_void_p), off_p, k, n,
+                                            out.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.c_void_p)), "jjs_digest")
+            return out, status
+        import torch
+        if not (inputs.is_cuda and inputs.dtype == torch.uint8 and inputs.is_contiguous()):
+            raise ValueError("expected a contiguous uint8 CUDA tensor")
+        out = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=inputs.device)[:n]
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=inputs.device)[:n]
+        _ffi.check(self._lib.jjs_digest_dev(fid, flags, ctypes.c_void_p(inputs.data_ptr()), off_p, k, n, ctypes.c_void_p(out.data_ptr()),
+                                            ctypes.c_void_p(status.data_ptr()), self._stream()), "jjs_digest_dev")
+        return out, status
+
+    def digest_limits(self) -> dict:
+        """jjs_debug_digest_limits: the largest n whose items take eight lanes each, and the lanes of the one-lane-per-item
+        kernel's grid (a call of more items takes a second trip through it)."""
+        out = (ctypes.c_uint64 * 2)()
+        _ffi.check(self._lib.jjs_debug_digest_limits(out), "jjs_debug_digest_limits")
+        return {"coop_max_items": int(out[0]), "grid_lanes": int(out[1])}
+
     def verify_wire(self, scheme: str, sig, pk, m, want_status: bool = True):
         """Batch verify from the reference's wire formats (torch CUDA uint8 tensors): sig (n, 64|96|64) =
         u || R [|| R'], pk (n, 32|64|64) compressed, m (n, 32).  Points are decoded on the device; an

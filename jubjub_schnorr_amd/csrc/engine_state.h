@@ -280,6 +280,12 @@ struct device_state {
                                          // used in the order of slot 0's event, grows under the engine's mutex; jjs_trim frees it
     grow_only<uint8_t> sign_key;         // jjs_sign_fixed* with one key for the call: the record of the keyed route's pre-pass (sign_fixed.h,
                                          // bytes); used and grown as sign_tables; jjs_trim frees it
+    grow_only<uint8_t> digest_scratch;   // jjs_digest* of ragged items: the offsets and the order of a call (digest_calls.h, bytes); used in the
+                                         // order of slot 0's event, grows under the engine's mutex; jjs_trim frees it
+    std::vector<uint32_t> digest_order;  // ... and the host words the order is formed in (under the engine's mutex).  Pageable memory, rewritten
+                                         // by the next ragged call without a wait: hipMemcpyAsync stages a pageable source before it returns,
+                                         // which is what the offsets_host uploads of the multisignature calls rely on as well
+    int grid_digest = 0;                 // blocks of digest_kernel / digest_coop_kernel resident at once
     grow_only<uint8_t> msig_stage;       // the blocking host-buffer multisig and signing calls (staged_host_call.h): their columns and
                                          // outputs (bytes), on ks_stream under host_mu; it grows under the engine's mutex as well, which
                                          // jjs_memory_stats reads it under; jjs_trim frees it

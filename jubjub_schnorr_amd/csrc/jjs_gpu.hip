@@ -29,6 +29,7 @@
 //   msig_share_calls.h  verify_share on its own: single shares by transcript and slot, inline, by signer group and by key set
 //   sign_vargen_calls.h  var-generator signing and key derivation with the generator as a point, both forms (test material)
 //   sign_fixed_calls.h  signing and key derivation with a SecretKey in the single and double schemes, both forms (test material)
+//   digest_calls.h     Poseidon digests of ragged inputs, both forms: the routes, the order of a ragged call's items
 //   host_lanes.h       the small ones (included among the entry points, behind the table of call shapes): staging lanes
 //                      outside the engine's mutex, calls of several threads in one launch
 //   (here)             the table of call shapes and the staged_call builder it drives; the extern "C" entry points
@@ -83,6 +84,7 @@
 #include "batch_verdict.h"
 #include "keyset_verdict.h"
 #include "points_check.h"
+#include "digest.h"
 #include "jjs_sponge_tags_long.inc"
 
 using namespace jjs;
@@ -94,6 +96,7 @@ namespace {
 #include "keyset_verdict_kernels.h"
 #include "keyset_add_kernels.h"
 #include "keyset_remove_kernels.h"
+#include "digest_kernels.h"
 #include "device_owners.h"
 #include "engine_state.h"
 #include "verify_job.h"
@@ -171,6 +174,17 @@ int init_device(device_state& d, int ordinal) {
         if (per_cu_f < least) least = per_cu_f;
         d.grid_sign_fixed = prop.multiProcessorCount * (least < 1 ? 1 : least);
         if (d.grid_sign_fixed > lanes_blocks) d.grid_sign_fixed = lanes_blocks;
+    }
+    {   // the digest kernels (digest.h): one grid for the four, the lanes resident at once
+        int per_cu_d = 0, least = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&least, digest_kernel<DG_CANONICAL>, BLOCK, 0));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, digest_kernel<DG_WIDE>, BLOCK, 0));
+        if (per_cu_d < least) least = per_cu_d;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, digest_coop_kernel<DG_CANONICAL>, BLOCK, 0));
+        if (per_cu_d < least) least = per_cu_d;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, digest_coop_kernel<DG_WIDE>, BLOCK, 0));
+        if (per_cu_d < least) least = per_cu_d;
+        d.grid_digest = prop.multiProcessorCount * (least < 1 ? 1 : least);
     }
     for (int i = 0; i < N_SLOTS; ++i) {
         call_slot& c = d.slots[i];
@@ -753,6 +767,7 @@ int jjs_trim(void) {
         free_retired(*d);
         HIP_TRY(d->sign_tables.free());                        // the tables of a signing call's shared generator
         HIP_TRY(d->sign_key.free());                           // the key record of a signing call with one key
+        HIP_TRY(d->digest_scratch.free());                     // the offsets and the order of a ragged digest call
         HIP_TRY(d->msig_stage.free());                         // the staging of the host-buffer multisig calls (host_mu is held)
         for (call_slot& c : d->slots) {
             if (!c.key_pool) continue;
@@ -776,7 +791,7 @@ int jjs_memory_stats(uint64_t out[JJS_MEMORY_STATS]) {
     }
     for (const host_lane& l : g->lanes) lanes += l.dev.reported_bytes() + l.pinned.reported_bytes();
     out[JJS_MEMORY_KEY_POOLS] = pool;
-    out[JJS_MEMORY_SLOT_BUFFERS] = slots + g->sign_tables.reported_bytes() + g->sign_key.reported_bytes();
+    out[JJS_MEMORY_SLOT_BUFFERS] = slots + g->sign_tables.reported_bytes() + g->sign_key.reported_bytes() + g->digest_scratch.reported_bytes();
     out[JJS_MEMORY_HOST_STAGING] = lanes + g->stage.reported_bytes() + g->pinned.reported_bytes() + g->msig_stage.reported_bytes();
     out[JJS_MEMORY_RETIRED] = g->retired_bytes;
     return JJS_OK;
@@ -1121,6 +1136,7 @@ int jjs_public_keys_dev(const void* sk, size_t n, void* PK_out, void* PKp_out, v
 
 #include "sign_vargen_calls.h"
 #include "sign_fixed_calls.h"
+#include "digest_calls.h"
 
 // ---- debug primitives ------------------------------------------------------------------------------
 int jjs_debug_fq_mul_dev(const void* a, const void* b, size_t n, void* out, void* stream) {
@@ -1183,6 +1199,8 @@ int jjs_debug_force_path(int which) {
     g_force_verdict = (which & 0x2000) ? 1 : ((which & 0x4000) ? 2 : 0);   // jjs_verify_all_*: 0x2000 the verdict algorithm, 0x4000 the per-item path
     g_force_sign_shared = (which & 0x8000) ? 1 : ((which & 0x200000) ? 2 : 0);   // jjs_sign_vargen_pt* with one generator: 0x8000 the shared-generator route at any n, 0x200000 the per-item route
     g_force_sign_keyed = (which & 0x400000) ? 1 : ((which & 0x800000) ? 2 : 0);   // jjs_sign_fixed* with one key: 0x400000 the keyed route at any n, 0x800000 the per-item route
+    g_force_digest_route = (which & 0x1000000) ? 1 : ((which & 0x2000000) ? 2 : 0);   // jjs_digest*: 0x1000000 eight lanes per item at any n, 0x2000000 one lane
+    g_digest_keep_order = (which & 0x4000000) != 0;                                 // ... 0x4000000: ragged items in input order
     g_force_msm_window = (which >> 16) & 31;                                // ... and bits 16-20 its window width (8-16; 0 by size)
     return JJS_OK;
 }

@@ -309,6 +309,7 @@ def main():
           "#define JJS_FR_INV32 0x%08xu  // -r^-1 mod 2^32" % ((-pow(R_ORDER, -1, 1 << 32)) % (1 << 32)),
           "JJS_CONST uint32_t JJS_R2[9] = %s;  // R'^2 mod q" % limbs29(MONT * MONT % Q),
           "JJS_CONST uint32_t JJS_ONE[9] = %s;  // R' mod q" % limbs29(MONT),
+          "JJS_CONST uint32_t JJS_TWO256[9] = %s;  // 2^256 R' mod q: the high half of a 512-bit value (csrc/digest.h)" % limbs29(mont(1 << 256)),
           "JJS_CONST uint32_t JJS_D[9] = %s;" % limbs29(mont(D)),
           "JJS_CONST uint32_t JJS_D2[9] = %s;  // 2d" % limbs29(mont(2 * D)),
           "JJS_CONST uint32_t JJS_G[2][9] = {%s, %s};" % (limbs29(mont(G[0])), limbs29(mont(G[1]))),
