@@ -157,6 +157,16 @@ int jjs_path_stats(uint64_t out[JJS_PATH_STATS]);
  *   jjs_reserve(scheme, format, n_items, host_buffers) allocates what a verification call of that scheme (JJS_SCHEME_*),
  *   input format (JJS_FORMAT_*) and at most n_items items needs, in every call slot such a call can land in; with
  *   host_buffers != 0 also the staging of the blocking host-buffer entry point of that shape (for every driven device).
+ *   A reserve may come from any thread at any time, also beside live calls of any kind; no call then sees a buffer replaced
+ *   under it, and every call's statuses are what they would have been.  What such a reserve guarantees:
+ *     - it never waits for the device and frees nothing (what it replaces is kept until jjs_trim / jjs_shutdown);
+ *     - a staging lane of the small host-buffer calls (at most 16 384 items) that is in use when the reserve comes keeps its
+ *       areas and grows to the reserved size when it is next opened, by the call that opens it: after a reserve beside live
+ *       host-buffer calls up to eight later calls, one per lane that was busy, may still allocate.  Lanes that were idle,
+ *       and so every lane of a reserve at start-up, hold the size when the reserve returns;
+ *     - a reserve of more than 16 384 items sizes what a large host-buffer call (more than 16 384 items, one driven device) uses
+ *       while it runs; it waits for such a call in progress to return, as jjs_trim does, and the next one starts behind it.
+ *       Resident calls and small host-buffer calls of other threads go on meanwhile.
  * jjs_trim() waits for the devices to go idle and frees the retired buffers and the key-table pools (which come back,
  * at the size they had, with the next call that takes the key tables).  jjs_memory_stats: bytes held, by kind. */
 #define JJS_SCHEME_SINGLE 0

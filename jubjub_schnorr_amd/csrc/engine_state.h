@@ -169,6 +169,10 @@ struct host_lane {
     event_owner done;                 // end of the launch in progress on the lane
     grow_only<uint8_t> dev{{size_t(1) << 20}};            // device area: the columns of the launch, its statuses (bytes)
     grow_only<uint8_t, true> pinned{{size_t(1) << 20}};   // pinned host area, same layout
+    // The two areas are replaced only while the lane is FREE (its members copy into them, upload from them and read their statuses
+    // from them outside the engine's mutex): by the call that opens the lane, and by jjs_reserve -- which leaves the size it wants
+    // here when it finds the lane busy, for the lane's next open (reserve_lane)
+    size_t reserved_bytes = 0;
     // the launch that is being put together / runs on the lane
     enum : int { FREE = 0, OPEN = 1, LAUNCHED = 2, DONE = 3 };
     int state = FREE;

@@ -254,6 +254,9 @@ int run_host_block(device_state* dev, const call_shape& S, const host_col* cols,
         if (int rc = build_call(S, in, nl, st, g->tally, g->stream, J.C)) return rc;
         if (b.unlocked) { sl->host_owned = true; b.owned = sl; }
     }
+    // From here on an unlocked call sizes and feeds its slot without the engine's mutex (the key pool below, job_begin's buffers):
+    // the slot is this call's alone -- pick_slot and jjs_path_stats pass a host_owned slot by, and jjs_reserve and jjs_trim, which
+    // size or free every slot, hold this device's host_mu, as this call does, whenever they reach a slot such a call can own.
     bool late = false;
     for (size_t k = 0; k < n_cols; ++k) late = late || cols[k].group == COLS_LATE;
     late = late && !J.C.wire && !small_path_applies(J.C.P) && key_path_applies(J.C.P) && ensure_key_pool(J.C.P) == JJS_OK;
@@ -432,7 +435,8 @@ int run_host_block(device_state* dev, const call_shape& S, const host_col* cols,
     return JJS_OK;
 }
 
-// jjs_reserve: the device arena and the pinned staging a block of nl items of shape S needs (current device)
+// jjs_reserve: the device arena and the pinned staging a block of nl items of shape S needs (current device).  run_host_block reads
+// both anew for every piece, under host_mu alone when the call is unlocked: the caller holds host_mu as well as the engine's mutex.
 int reserve_host_block(const call_shape& S, size_t nl) {
     size_t bytes = 0, largest = 256;
     for (size_t k = 0; k < S.n_cols; ++k) bytes += pad256(nl * S.col[k].width);

@@ -28,11 +28,21 @@ static size_t lane_cap_for(const device_state* dev, int scheme, int format, size
     while (cap < want) cap <<= 1;
     return cap < COMBINE_CAP_ITEMS ? cap : COMBINE_CAP_ITEMS;
 }
+// Under the engine's mutex, of a lane that is FREE: nobody is copying into its areas, uploading from them or reading statuses
+// from them, so they may be replaced.  At least what a reserve has asked of the lane while it was busy (reserve_lane).
 static int ensure_lane(host_lane& lane, size_t bytes) {
+    if (bytes < lane.reserved_bytes) bytes = lane.reserved_bytes;
     if (!lane.stream) HIP_TRY(lane.stream.create(hipStreamNonBlocking));
     if (!lane.done) HIP_TRY(lane.done.create(hipEventDisableTiming));
     if (int rc = lane.dev.ensure(bytes)) return rc;
     return lane.pinned.ensure(bytes);
+}
+// jjs_reserve (under the engine's mutex): a lane that is FREE grows now.  A busy one keeps its areas -- its members use them
+// outside the mutex until the last of them has left -- and grows when it is next opened: the reserve waits for no call and no
+// call ever sees its lane's areas change.
+static int reserve_lane(host_lane& lane, size_t bytes) {
+    if (lane.reserved_bytes < bytes) lane.reserved_bytes = bytes;
+    return lane.state == host_lane::FREE ? ensure_lane(lane, bytes) : JJS_OK;
 }
 // The end of a lane launch: small calls last half a millisecond, and a thread that sleeps on the stream pays the wake-up on
 // top (tens to hundreds of microseconds on an idle core), so it polls the launch's event for LANE_SPIN_US first.

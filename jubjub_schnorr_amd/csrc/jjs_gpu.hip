@@ -695,9 +695,26 @@ int jjs_verify_vargen_ext(const uint8_t* u, const uint8_t* R, const uint8_t* PK,
 // ---- pre-sizing and trimming ------------------------------------------------------------------------------------
 // What a call of this shape and size would allocate on first use, allocated now, in EVERY slot (and lane) such a call can
 // land in: a service calls this once per call shape at start-up and no later call of at most that size allocates.
+// BESIDE LIVE CALLS it replaces nothing a call uses outside the engine's mutex:
+//   - a lane that is not FREE keeps its areas and grows at its next open (host_lanes.h reserve_lane);
+//   - a large host-buffer call (one device: run_host under host_mu) reads the device's staging anew for every piece, and sizes and
+//     feeds the slot it owns -- a medium or the second big one -- without the mutex: a reserve that reaches either, i.e. one of
+//     more items than a lane or a small slot takes, holds host_mu of every device first, in jjs_trim's order.  It then waits for
+//     such a call in progress to return, never for the device: nothing here synchronises or frees.
 int jjs_reserve(int scheme, int format, size_t n_items, int host_buffers) {
+    std::vector<device_state*> devs;
+    std::vector<std::unique_lock<std::mutex>> big;
+    if (n_items > (LANE_MAX_ITEMS < SMALL_SLOT_ITEMS ? LANE_MAX_ITEMS : SMALL_SLOT_ITEMS)) {
+        {
+            std::lock_guard<std::mutex> lock(L.mu);
+            if (int rc = check_ready()) return rc;
+            devs = L.devs;
+        }
+        try { for (device_state* d : devs) big.emplace_back(d->host_mu); } catch (...) { return fail(JJS_ERR_HIP, "host-side failure"); }
+    }
     std::lock_guard<std::mutex> lock(L.mu);
     if (int rc = check_ready()) return rc;
+    if (!big.empty() && devs != L.devs) return fail(JJS_ERR_NOT_INIT, "the engine was re-initialised during the call");
     if (scheme < 0 || scheme > 2 || format < 0 || format > 2) return fail(JJS_ERR_ARG, "scheme / format out of range");
     if (n_items == 0) return JJS_OK;
     const call_shape& S = SHAPES[scheme][format];
@@ -734,7 +751,7 @@ int jjs_reserve(int scheme, int format, size_t n_items, int host_buffers) {
                 if (targets.size() == 1 && per <= LANE_MAX_ITEMS) {
                     const lane_layout Y = lane_layout_for(S, lane_cap_for(nullptr, scheme, format, call_items));
                     for (host_lane& l : d->lanes)
-                        if (int r = ensure_lane(l, Y.total)) return r;
+                        if (int r = reserve_lane(l, Y.total)) return r;
                 } else {
                     if (int r = reserve_host_block(S, per)) return r;
                 }
